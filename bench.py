@@ -11,9 +11,20 @@ equal-work cameras (`equal_work_*`), with two views per rank whose gradients acc
 (`compute_only_*`: what N independent GPUs would deliver -- the reference point for scaling efficiency on THIS workload).
 Prints ONE JSON line on rank 0.
 
-Order inside a run: W warm-up steps, K steps timed "at start" (`clock_ramp`: the GPU's clock governor is still ramping
-there), the auxiliary passes of the same step (pipelined / one-view forms at N > 1, the reference-binning pass), then W warm-up
-steps again and the K timed steps `value` is computed from, then the per-stage pass (`stages_ms`).
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what `value` / `ms_per_step` need: set-up, the clock ramp
+(untimed steps, at least RAMP_S seconds of them: the GPU's clock governor needs that much continuous work to reach its
+sustained clock, the one a training run spends its time at), W warm-up steps, the K timed steps, and the line.
+
+`--full` adds everything else, as rounds 1-6 ran it, in this order: W warm-up steps, K steps timed "at start" (`clock_ramp`: the
+governor is still ramping there), the auxiliary passes of the same step (pipelined / one-view forms at N > 1, the reference-
+binning pass), then W warm-up steps again and the K timed steps `value` is computed from (every fourth backward blend
+bracketed by HIP events for `roofline`), the same K steps again with per-step events (`median_ms_per_step`), then the
+per-stage pass (`stages_ms`), and at N = 1 the caller levels and the CPU baseline.
+
+--dump-outputs DIR writes what the last timed step handed its caller -- colour, radii, observe, the G-buffer and the gradient of
+every input -- as DIR/<name>.npy in float32: an array of more than DUMP_CAP elements as a fixed, seeded sample of its
+Gaussians or pixels (output_sample).  The inputs are generated from --seed, so two runs with the same arguments compare
+output for output.
 
   --config c3            BASELINE.json configs[2]: 1M Gaussians, 1920x1080, feature_count 9 (material G-buffers) -- the
                          configuration the metric is quoted on; the default at N = 1
@@ -24,7 +35,7 @@ steps again and the K timed steps `value` is computed from, then the per-stage p
   --config c4            configs[3]: the full train.py loop at DTU scan24's size on a SUBSTITUTE scene (the dataset is not on the
                          box): 49 views 777x581 through the COLMAP loader at -r 2, ~30 k -> past 300 k points, geometry stage with
                          lambda_depth_normal 0.015 and the multi-view term; prints training iterations/s (N = 1 only)
-At N = 1 the line also carries `cpu_baseline` (the oracle timed on this box's host cores), `render_level_ms`,
+With --full at N = 1 the line also carries `cpu_baseline` (the oracle timed on this box's host cores), `render_level_ms`,
 `train_step_ms` and `material_step_ms` (render(), a full geometry-stage and a full material-stage training iteration around
 the same op).
 """
@@ -48,6 +59,26 @@ SIMDS = 1024           # 256 CUs x 4 SIMDs
 CONFIGS = {  # name -> (Gaussians, width, height, feature_count)
     "c1": (10_000, 256, 256, 10), "c2": (500_000, 1920, 1080, 5), "c3": (1_000_000, 1920, 1080, 9),
     "c5": (2_000_000, 1920, 1080, 9)}
+# plain run: untimed steps ahead of the warm-up until the GPU has worked this long without a pause.  The governor takes the
+# shader clock from idle to ~2350 MHz in about 0.4 s of continuous work and the ALU-bound blend kernels follow it
+# (profiles/r04_clock_ramp.txt: the first ~30 steps of a process fall from 1.70 to 1.37 ms)
+RAMP_S = 0.5
+DUMP_CAP = 1 << 20  # --dump-outputs: elements per array (at most 12 arrays x 4 MiB of float32 = 48 MiB in all)
+DUMP_SEED = 0
+
+
+def output_sample(t, P):
+    """--dump-outputs: tensor -> float32 numpy array.  Up to DUMP_CAP elements the whole array; beyond that a fixed sample drawn
+    with DUMP_SEED, in ascending index order: whole rows of the Gaussians (leading dimension P) or, for an image (C, H, W), every
+    channel of the sampled pixels.  The sample depends on the shape only, so runs with the same arguments take the same elements."""
+    import numpy as np
+    t = t.detach()
+    if t.numel() > DUMP_CAP:
+        rows = t.reshape(P, -1) if t.shape[0] == P else t.reshape(t.shape[0], -1).t()
+        k = max(1, DUMP_CAP // rows.shape[1])
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rows.shape[0], size=k, replace=False))
+        t = rows.index_select(0, torch.from_numpy(idx).to(t.device))
+    return t.float().cpu().numpy()
 
 
 def kernel_source_hash():
@@ -352,10 +383,18 @@ def self_launch(n):
 
 
 def main():
+    def positive(s):
+        if int(s) < 1:
+            raise argparse.ArgumentTypeError("must be at least 1")
+        return int(s)
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=50)
+    ap.add_argument("--steps", type=positive, default=200, help="timed steps (K)")
+    ap.add_argument("--warmup", type=int, default=50, help="untimed warm-up steps right before the timed ones (W)")
+    ap.add_argument("--full", action="store_true", help="everything besides the headline: the at-start timing, the reference-binning "
+                    "pass, the side timings at N > 1, roofline, median and per-stage times, the caller levels and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy "
+                    "(float32; a seeded sample of the larger arrays, see output_sample)")
     ap.add_argument("--config", default=None, choices=sorted(CONFIGS) + ["c4"], help="BASELINE.json configuration (see the module docstring); default c3 on one GPU, c5 on several")
     ap.add_argument("--c4-iterations", type=int, default=5000, help="--config c4: training iterations (the reference runs 30000; the schedule is compressed)")
     ap.add_argument("--gaussians", type=int, default=None)
@@ -363,8 +402,8 @@ def main():
     ap.add_argument("--height", type=int, default=None)
     ap.add_argument("--fc", type=int, default=None, help="feature_count (9 = --material stage)")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-caller-levels", action="store_true", help="skip render_level_ms / train_step_ms / material_step_ms")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-caller-levels", action="store_true", help="--full: skip render_level_ms / train_step_ms / material_step_ms")
     ap.add_argument("--dp-mode", default="auto", choices=["auto", "allreduce", "rs_ag"],
                     help="auto: reduce-scatter + all-gather from 4 ranks on (every link of the xGMI mesh busy), all-reduce below")
     ap.add_argument("--equal-work", action="store_true",
@@ -383,7 +422,7 @@ def main():
                     help="views every rank renders per step of the HEADLINE (default 1: the metric's step, north_star's form); with more "
                          "than one their gradients ACCUMULATE and one reduction follows the last view (exact sums, no stale gradients; the "
                          "collective is paid once per that many views).  The two-view form is timed beside the headline at N > 1 anyway")
-    ap.add_argument("--no-reference-binning", action="store_true", help="skip the second timing of the same workload in reference-binning mode")
+    ap.add_argument("--no-reference-binning", action="store_true", help="--full: skip the second timing of the same workload in reference-binning mode")
     a = ap.parse_args()
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -404,6 +443,8 @@ def main():
     if a.config == "c4":
         if world != 1:
             raise SystemExit("bench.py --config c4 is a single-GPU run")
+        if a.dump_outputs:
+            raise SystemExit("bench.py --config c4: --dump-outputs covers the rasterizer step of the other configurations only")
         return bench_c4(a)
     ndev = torch.cuda.device_count()
     backend = os.environ.get("GS2M_DIST_BACKEND", "nccl")  # "gloo": functional check of the N > 1 path on one GPU
@@ -492,7 +533,7 @@ def main():
         while pending:
             pending.pop(0).wait()
 
-    def step(pipelined=False, family=None, views=None, reduce=True):
+    def step(pipelined=False, family=None, views=None, reduce=True, keep=False):
         sts = sts_f[family or head]
         nv = views or VPR
         for t in leaves:
@@ -525,6 +566,8 @@ def main():
                 drain()
         info["radii"] = radii
         info["R"] = color.grad_fn.num_rendered if hasattr(color.grad_fn, "num_rendered") else None
+        if keep:  # --dump-outputs: what the caller received in this step (the gradients stay in the leaves until the next step)
+            info["outputs"] = {"color": color, "radii": radii, "observe": observe, "buffer": buffer}
 
     def fence():
         drain()
@@ -533,11 +576,11 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
-    def timed(pipelined=False, **kw):
+    def timed(pipelined=False, keep_last=False, **kw):
         fence()
         t0 = time.perf_counter()
-        for _ in range(a.steps):
-            step(pipelined, **kw)
+        for k in range(a.steps):
+            step(pipelined, keep=keep_last and k == a.steps - 1, **kw)
         fence()
         ms = (time.perf_counter() - t0) / a.steps * 1e3
         if world > 1:
@@ -553,15 +596,22 @@ def main():
     import gc
     gc.collect()
     gc.freeze()
+    if not a.full:
+        # Plain run: the clock ramp (RAMP_S), in place of the passes --full times ahead of its headline.  Without the collective:
+        # the ranks may take different numbers of steps here; the first step (code objects, allocator growth) is not counted.
+        step(reduce=False)
+        t_ramp = time.perf_counter()
+        while time.perf_counter() - t_ramp < RAMP_S:
+            step(reduce=False)
     for _ in range(a.warmup):
         step()
-    # The position rounds 1-3 timed at: right after the warm-up, i.e. inside the clock governor's ramp (sclk takes about half
+    # --full: the position rounds 1-3 timed at: right after the warm-up, i.e. inside the clock governor's ramp (sclk takes about half
     # a second of continuous work to reach 2400 MHz, tools/clock_trace.py; the ALU-bound blend kernels run by the clock ratio
     # slower until then).  Kept as `ms_per_step_at_start`; the auxiliary passes below all run the same step, and the headline
     # region is timed after them, again behind W warm-up steps, at the clock a training run of 30k steps spends its time at.
-    ms_start = timed(False)
+    ms_start = timed(False) if a.full else None
     beside = {}
-    if world > 1:  # beside the headline, same run, each behind two untimed steps of its own form
+    if world > 1 and a.full:  # beside the headline, same run, each behind two untimed steps of its own form
         other = "arc" if head == "ring" else "ring"
         for key, kw in (("pipelined", dict(pipelined=True)), ("equal_work" if other == "arc" else "camera_ring", dict(family=other)),
                         ("accumulate_v2", dict(views=2)), ("compute_only", dict(reduce=False))):
@@ -575,7 +625,7 @@ def main():
     # runs the default mode: a result-identical, order-preserving SUBSET of that list (tiles the alpha >= 1/255 ellipse cannot
     # reach are not emitted).
     ref_binning = None
-    if world == 1 and not a.no_reference_binning:
+    if world == 1 and a.full and not a.no_reference_binning:
         gs2m_native.lib().gs2m_set_reference_binning(1)
         for _ in range(max(3, a.warmup // 2)):
             step()
@@ -587,44 +637,53 @@ def main():
                        "num_rendered": int(info["R"]) if info["R"] is not None else -1}
         gs2m_native.lib().gs2m_set_reference_binning(0)
 
-    # The headline: W untimed warm-up steps, then exactly K timed ones.
-    # HIP events on the launch stream around the dominant kernel (the backward blend) inside the timed region.  An event pair
+    # The headline: W untimed warm-up steps (a plain run has taken them above), then exactly K timed ones.
+    # --full: HIP events on the launch stream around the dominant kernel (the backward blend) inside the timed region.  An event pair
     # leaves ~6 us of bubble on the stream on either side of the kernel it brackets (kernel trace: the only gaps of the step), so
     # every BRACKET_EVERY-th launch is bracketed -- `roofline.launches_bracketed` of the K x views launches -- and the other
     # stages are timed in the untimed pass below
     BRACKET_EVERY = 4
-    for _ in range(a.warmup):
-        step()
-    gs2m_native.profile_mode(3, every=BRACKET_EVERY)
-    ms = timed(False)
-    blend = gs2m_native.profile_collect()
-    gs2m_native.profile_mode(0)
-    # the same K steps once more with an event between them: per-step times, for the median beside the mean (an event is a
-    # marker on the launch stream; the steps run back to back as before, minus ~1 us of marker per step)
-    evs = [torch.cuda.Event(enable_timing=True) for _ in range(a.steps + 1)]
-    fence()
-    evs[0].record()
-    for k in range(a.steps):
-        step()
-        evs[k + 1].record()
-    fence()
-    per_step = sorted(evs[k].elapsed_time(evs[k + 1]) for k in range(a.steps))
-    ms_median = per_step[len(per_step) // 2] if a.steps % 2 else 0.5 * (per_step[a.steps // 2 - 1] + per_step[a.steps // 2])
+    if a.full:
+        for _ in range(a.warmup):
+            step()
+        gs2m_native.profile_mode(3, every=BRACKET_EVERY)
+    ms = timed(False, keep_last=bool(a.dump_outputs))
+    if a.full:
+        blend = gs2m_native.profile_collect()
+        gs2m_native.profile_mode(0)
+    dumped = None
+    if a.dump_outputs and rank == 0:  # sampled now: the next step reuses the gradients' memory
+        grad_names = ["means3D", "means2D", "shs_dc" if sh_rest is not None else "shs", "opacities", "scales", "rotations", "features", "shs_rest"]
+        dumped = {k: output_sample(v, P) for k, v in info.pop("outputs").items()}
+        dumped.update({"grad_" + n: output_sample(t.grad, P) for n, t in zip(grad_names, leaves) if t.grad is not None})
+    if a.full:
+        # the same K steps once more with an event between them: per-step times, for the median beside the mean (an event is a
+        # marker on the launch stream; the steps run back to back as before, minus ~1 us of marker per step)
+        evs = [torch.cuda.Event(enable_timing=True) for _ in range(a.steps + 1)]
+        fence()
+        evs[0].record()
+        for k in range(a.steps):
+            step()
+            evs[k + 1].record()
+        fence()
+        per_step = sorted(evs[k].elapsed_time(evs[k + 1]) for k in range(a.steps))
+        ms_median = per_step[len(per_step) // 2] if a.steps % 2 else 0.5 * (per_step[a.steps // 2 - 1] + per_step[a.steps // 2])
 
-    # untimed: per-stage breakdown of the same step, right behind the headline region (same clock).  Every stage is bracketed by
-    # HIP events of its own: a bracket also sees the dispatch latency that back-to-back kernels overlap with their predecessor's
-    # tail, so the stage times add up to slightly MORE than ms_per_step (by about 2-4 us per bracket).
-    STAGE_STEPS = 5
-    gs2m_native.profile_mode(2)
-    for _ in range(STAGE_STEPS):
-        step()
-    fence()
-    stages = gs2m_native.profile_collect()
-    gs2m_native.profile_mode(0)
+        # untimed: per-stage breakdown of the same step, right behind the headline region (same clock).  Every stage is bracketed by
+        # HIP events of its own: a bracket also sees the dispatch latency that back-to-back kernels overlap with their predecessor's
+        # tail, so the stage times add up to slightly MORE than ms_per_step (by about 2-4 us per bracket).
+        STAGE_STEPS = 5
+        gs2m_native.profile_mode(2)
+        for _ in range(STAGE_STEPS):
+            step()
+        fence()
+        stages = gs2m_native.profile_collect()
+        gs2m_native.profile_mode(0)
 
     if rank == 0:
         V = int((info["radii"] > 0).sum().item())
         R = int(info["R"]) if info["R"] is not None else -1
+    if rank == 0 and a.full:
         Tn = ((W + 15) // 16) * ((H + 15) // 16)
         ab = S.algo_bytes(P, V, R, W * H, Tn, fc)
         k_ms = {"blend_bwd": blend["blend_bwd"][0] / max(blend["blend_bwd"][1], 1),            # live, timed region
@@ -664,12 +723,13 @@ def main():
             if ctr.get("GRBM_GUI_ACTIVE") and ctr.get("SQ_VALU_MFMA_BUSY_CYCLES") is not None:
                 # matrix-pipe busy cycles per SIMD over the kernel's cycles (GRBM_GUI_ACTIVE is summed over the 8 XCDs)
                 roof["counters"]["mfma_busy_share"] = round(ctr["SQ_VALU_MFMA_BUSY_CYCLES"] / SIMDS / (ctr["GRBM_GUI_ACTIVE"] / 8.0), 4)
+    if rank == 0:
         out = {
             # BASELINE.json's metric is quoted on C3 (1M Gaussians, 1080p); other configurations say what they ran
             "metric": ("train views/s (fwd+bwd raster) at 1M Gaussians 1080p" if (P, W, H) == (1_000_000, 1920, 1080) else
                        f"train views/s (fwd+bwd raster) at {P} Gaussians {W}x{H}"),
             "value": round(world * VPR * 1e3 / ms, 3), "unit": "views/s", "n_gpus": world, "steps": a.steps,
-            "warmup": a.warmup, "ms_per_step": round(ms, 4), "median_ms_per_step": round(ms_median, 4), "higher_is_better": True, "scaling": "weak",
+            "warmup": a.warmup, "ms_per_step": round(ms, 4), "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": (f"BASELINE configs[{ {'c1': 0, 'c2': 1, 'c3': 2, 'c5': 4}[a.config]}] ({a.config}): " if preset else "custom: ")
                                    + f"{P} synthetic Gaussians (SH deg 3), 1 camera {W}x{H} per GPU, feature_count={fc}, fwd+bwd at the op boundary"
@@ -681,11 +741,13 @@ def main():
                                    + (f" [ring position {a.ring_position}: NOT the metric's camera]" if world == 1 and a.ring_position else ""),
                        "gaussians": P, "visible": V, "num_rendered": R, "width": W, "height": H, "feature_count": fc,
                        "parallelism": f"view-parallel x{world}", "views_per_rank": VPR},
-            "roofline": roof,
+        }
+        if a.full:
+            out["median_ms_per_step"] = round(ms_median, 4)
+            out["roofline"] = roof
             # stage TOTALS per step (a stage with two launches per step -- ranges + quadrant lists -- counts both); each stage is
             # its own event bracket, dispatch latency included: the sum exceeds ms_per_step by a few us per bracket
-            "stages_ms": {k: round(v[0] / STAGE_STEPS, 5) for k, v in stages.items() if not k.startswith("unused")},
-        }
+            out["stages_ms"] = {k: round(v[0] / STAGE_STEPS, 5) for k, v in stages.items() if not k.startswith("unused")}
         if ref_binning is not None:
             out["reference_binning_ms_per_step"] = ref_binning["ms_per_step"]
             out["reference_binning"] = ref_binning
@@ -695,17 +757,23 @@ def main():
         if "compute_only" in beside:
             out["scaling_efficiency_vs_compute_only"] = round(beside["compute_only"][0] / ms, 4)  # = value / (what N independent GPUs deliver on this workload)
         out["views_per_step"] = world * VPR
-        # the same K steps timed right behind the first W warm-up steps (where rounds 1-3 timed): inside the governor's clock ramp
-        out["clock_ramp"] = {"ms_per_step_at_start": round(ms_start, 4), "value_at_start": round(world * VPR * 1e3 / ms_start, 3),
-                             "steps_before_headline": "W warm-up + K at-start + reference-binning pass (3 + K) + W warm-up",
-                             "note": "sclk reaches 2400 MHz after ~0.5 s of continuous work (tools/clock_trace.py); "
-                                     "`value` is timed after that, `value_at_start` before"}
-    if world == 1 and rank == 0:
+        if a.full:
+            # the same K steps timed right behind the first W warm-up steps (where rounds 1-3 timed): inside the governor's clock ramp
+            out["clock_ramp"] = {"ms_per_step_at_start": round(ms_start, 4), "value_at_start": round(world * VPR * 1e3 / ms_start, 3),
+                                 "steps_before_headline": "W warm-up + K at-start + reference-binning pass (3 + K) + W warm-up",
+                                 "note": "sclk reaches 2400 MHz after ~0.5 s of continuous work (tools/clock_trace.py); "
+                                         "`value` is timed after that, `value_at_start` before"}
+    if world == 1 and rank == 0 and a.full:
         torch.cuda.empty_cache()
         if not a.no_caller_levels:
             out.update(caller_levels(P, W, H, a.seed, dev))
         if not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(P, W, H, fc, a.seed)
+    if dumped is not None:
+        import numpy as np
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for name, arr in dumped.items():
+            np.save(os.path.join(a.dump_outputs, name + ".npy"), arr)
     if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:

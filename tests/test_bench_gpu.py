@@ -1,5 +1,6 @@
 """bench.py's one-line JSON contract (metric / value / unit / n_gpus / steps / warmup / ms_per_step / higher_is_better / scaling /
-vs_baseline / dtype / data / config.workload + roofline + cpu_baseline), on a short run."""
+vs_baseline / dtype / data / config.workload; with --full also roofline + cpu_baseline and the rest), on short runs; and what a
+plain run leaves out and writes with --dump-outputs."""
 import json
 import os
 import subprocess
@@ -12,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_line_has_the_contract_fields():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "8"], capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "8", "--full"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1]
     d = json.loads(line)
@@ -46,7 +47,7 @@ def test_bench_two_ranks_share_one_gpu_over_gloo():
     port = 29700 + os.getpid() % 200
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--gaussians", "30000", "--width", "320", "--height", "192"], capture_output=True, text=True, timeout=400, env=env)
+                        "--gaussians", "30000", "--width", "320", "--height", "192", "--full"], capture_output=True, text=True, timeout=400, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]
     assert len(lines) == 1, "rank 0 prints ONE line"
@@ -67,12 +68,12 @@ def test_bench_two_ranks_share_one_gpu_over_gloo():
 
 
 def test_bench_gpus_2_as_typed_starts_its_own_ranks():
-    """`python bench.py --gpus 2 --steps 3 --warmup 2` exactly as the driver would type it -- no launcher, WORLD_SIZE unset:
+    """`python bench.py --gpus 2 --steps 3 --warmup 2 --full` as the driver would type it -- no launcher, WORLD_SIZE unset:
     bench.py starts `torch.distributed.run` as a child before it touches the GPU, relays rank 0's line and the child's
     exit code (BASELINE configs[4]; here both ranks share the box's one GPU over gloo)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(GS2M_DIST_BACKEND="gloo", GS2M_BENCH_WATCHDOG_S="500")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--full"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]
@@ -82,3 +83,38 @@ def test_bench_gpus_2_as_typed_starts_its_own_ranks():
     assert d["config"]["views_per_rank"] == 1 and d["views_per_step"] == 2
     for key in ("pipelined", "equal_work", "accumulate_v2", "compute_only"):
         assert d[key + "_ms_per_step"] > 0 and d[key + "_value"] > 0, key
+
+
+FULL_ONLY = ("median_ms_per_step", "roofline", "stages_ms", "clock_ramp", "reference_binning", "reference_binning_ms_per_step",
+             "cpu_baseline", "render_level_ms", "train_step_ms", "material_step_ms")
+OUTPUTS = ("color", "radii", "observe", "buffer", "grad_means3D", "grad_means2D", "grad_shs", "grad_opacities", "grad_scales",
+           "grad_rotations", "grad_features")
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run prints the headline only, takes exactly --steps timed steps and, with --dump-outputs, writes what the last
+    timed step computed; two runs with the same arguments render the same inputs (small workload: the whole arrays)."""
+    import numpy as np
+    import helpers as Hh
+    lines, dumps = [], []
+    for run in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--gaussians", "20000",
+               "--width", "320", "--height", "192", "--dump-outputs", str(tmp_path / run)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads([l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1]))
+        dumps.append({n: np.load(tmp_path / run / (n + ".npy")) for n in OUTPUTS})
+    d = lines[0]
+    assert d["steps"] == 4 and d["warmup"] == 2 and d["n_gpus"] == 1 and d["unit"] == "views/s" and d["dtype"] == "f32"
+    assert d["higher_is_better"] is True and abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-2 * d["value"]
+    assert not [k for k in FULL_ONLY if k in d], "a plain run leaves these to --full"
+    a, b = dumps
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(n + ".npy" for n in OUTPUTS)
+    assert sum(x.nbytes for x in a.values()) <= 64e6 and all(x.dtype == np.float32 for x in a.values())
+    assert a["color"].shape == (3, 192, 320) and a["radii"].shape == (20000,) and a["grad_shs"].shape == (20000, 16, 3)
+    assert (a["radii"] > 0).sum() == d["config"]["visible"] and np.abs(a["grad_means3D"]).max() > 0
+    assert np.array_equal(a["radii"], b["radii"]) and np.array_equal(a["observe"], b["observe"])
+    Hh.assert_image_close("color", a["color"], b["color"])
+    Hh.assert_image_close("buffer", a["buffer"], b["buffer"], scale=10.0)
+    for n in OUTPUTS[4:]:
+        Hh.assert_grad_close(n[5:], a[n], b[n])

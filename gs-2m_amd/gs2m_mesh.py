@@ -1,0 +1,449 @@
+"""Mesh extraction: TSDF depth fusion and marching cubes on the GPU (csrc/tsdf.hip, include/gs2m_mesh.h).
+
+Drop-ins for the three functions the reference's render.py imports from utils/mesh_utils.py -- `fuse_depths`,
+`post_process_mesh`, `write_mesh` -- and the volume behind them, `TSDFVolume`, which follows Open3D's legacy
+ScalableTSDFVolume as DESIGN.md §9 writes it down (16^3-voxel blocks, allocation from the stride-4 back-projected depth,
+per-voxel projective TSDF, marching cubes with shared vertices).  Fusion and extraction run in HIP kernels; the volume's
+memory is torch tensors owned here (the library allocates nothing).  The blocks live in a dense block-index table over a
+box fixed at creation: `fuse_depths` derives it from the depth maps (or `bounds`).
+
+    python gs-2m_amd/gs2m_mesh.py --ply point_cloud.ply -s SCENE -o OUT [--dtu]
+writes OUT/tsdf_mesh.ply, OUT/tsdf_post.ply and OUT/config.json as render.py --extract_mesh does.
+"""
+import argparse
+import ctypes as C
+import json
+import math
+import os
+import sys
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+if _HERE not in sys.path:
+    sys.path.insert(0, _HERE)
+
+import numpy as np
+import torch
+
+import gs2m_native as N
+
+BLOCK = 16
+POOL_FULL = 1  # include/gs2m_mesh.h GS2M_TSDF_POOL_FULL
+
+
+class TriangleMesh:
+    """vertices (V, 3) float32, triangles (F, 3) int32, vertex_colors (V, 3) float32 in [0, 1]: numpy arrays, so
+    `len(mesh.vertices)` and `np.asarray(mesh.triangles)` work as on Open3D's mesh."""
+
+    def __init__(self, vertices=None, triangles=None, vertex_colors=None):
+        self.vertices = np.zeros((0, 3), np.float32) if vertices is None else np.ascontiguousarray(vertices, dtype=np.float32)
+        self.triangles = np.zeros((0, 3), np.int32) if triangles is None else np.ascontiguousarray(triangles, dtype=np.int32)
+        self.vertex_colors = (np.zeros((len(self.vertices), 3), np.float32) if vertex_colors is None
+                              else np.ascontiguousarray(vertex_colors, dtype=np.float32))
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr())
+
+
+def _host_mat(m):
+    """(4, 4) -> HOST float[16] row major, fp32."""
+    a = np.ascontiguousarray(np.asarray(m, dtype=np.float32).reshape(4, 4))
+    return (C.c_float * 16)(*a.reshape(-1).tolist())
+
+
+def c2w_of(w2c):
+    """The camera-to-world matrix the touch rule uses: the fp64 inverse of the W2C matrix, rounded to fp32."""
+    return np.linalg.inv(np.asarray(w2c, dtype=np.float64)).astype(np.float32)
+
+
+class TSDFVolume:
+    """A TSDF volume over the world box [domain_min, domain_max] (cut to whole blocks of 16 * voxel_length).
+
+    integrate(depth (H, W), color (H, W, 3) uint8 or float in [0, 1], fx, fy, cx, cy, w2c (4, 4)) fuses one view;
+    extract_triangle_mesh() runs marching cubes.  Depths <= 0 or above `depth_trunc` are empty.  `ignored_points`: points of
+    the integrated views whose trunc box left the domain (counted, not fused)."""
+
+    def __init__(self, voxel_length, sdf_trunc, depth_trunc, domain_min, domain_max, device="cuda", capacity=256):
+        self.voxel = float(np.float32(voxel_length))
+        self.trunc = float(np.float32(sdf_trunc))
+        self.depth_trunc = float(np.float32(depth_trunc))
+        self.device = torch.device(device)
+        L = BLOCK * self.voxel
+        lo = [math.floor(float(a) / L) for a in domain_min]
+        hi = [math.floor(float(b) / L) for b in domain_max]
+        self.dom = [lo[0], lo[1], lo[2], hi[0] - lo[0] + 1, hi[1] - lo[1] + 1, hi[2] - lo[2] + 1]
+        self._dom = (C.c_int * 6)(*self.dom)
+        if min(self.dom[3:]) <= 0:
+            raise ValueError(f"gs2m_mesh: empty domain {domain_min} .. {domain_max}")
+        self.index_bytes = 4 * self.dom[3] * self.dom[4] * self.dom[5]
+        self.ignored_points = 0
+        tb = C.c_longlong()
+        N.check(N.lib().gs2m_tsdf_workspace_bytes(self._dom, 0, C.byref(tb), None), "gs2m_tsdf_workspace_bytes")
+        with N.device_guard(self.device):
+            self.index = torch.full((self.dom[3] * self.dom[4] * self.dom[5],), -1, dtype=torch.int32, device=self.device)
+            self.state = torch.zeros(4, dtype=torch.int32, device=self.device)
+            self.touch_ws = torch.zeros(tb.value, dtype=torch.uint8, device=self.device)
+        self.n_blocks = 0
+        self.capacity = 0
+        self._grow(max(1, int(capacity)))
+
+    def _grow(self, capacity):
+        """A pool of `capacity` blocks holding the current ones (zero-filled beyond them)."""
+        n, d = self.n_blocks, self.device
+        with N.device_guard(d):
+            coords = torch.zeros((capacity, 3), dtype=torch.int32, device=d)
+            tsdf = torch.zeros((capacity, BLOCK ** 3), dtype=torch.float32, device=d)
+            weight = torch.zeros_like(tsdf)
+            color = torch.zeros((capacity, 3, BLOCK ** 3), dtype=torch.float32, device=d)
+            if n:
+                coords[:n] = self.block_coords[:n]
+                tsdf[:n] = self.tsdf[:n]
+                weight[:n] = self.weight[:n]
+                color[:n] = self.color[:n]
+            self.block_coords, self.tsdf, self.weight, self.color = coords, tsdf, weight, color
+            self.touched = torch.zeros(capacity, dtype=torch.int32, device=d)
+        self.capacity = capacity
+
+    def _image(self, depth, color):
+        d = torch.as_tensor(depth).to(self.device, torch.float32).contiguous()
+        c = torch.as_tensor(color).to(self.device)
+        if c.dim() == 3 and c.shape[0] == 3 and c.shape[-1] != 3:
+            c = c.permute(1, 2, 0)
+        c = c.float() if c.dtype == torch.uint8 else c.float() * 255.0
+        H, W = d.shape
+        if tuple(c.shape) != (H, W, 3):
+            raise ValueError(f"gs2m_mesh: color {tuple(c.shape)} does not match depth {(H, W)}")
+        return d, c.contiguous()
+
+    def integrate(self, depth, color, fx, fy, cx, cy, w2c):
+        d, c = self._image(depth, color)
+        H, W = d.shape
+        w2c = np.asarray(w2c.detach().cpu() if torch.is_tensor(w2c) else w2c, dtype=np.float32).reshape(4, 4)
+        c2w = _host_mat(c2w_of(w2c))
+        w2c_h = _host_mat(w2c)
+        L = N.lib()
+        fx, fy, cx, cy = (float(np.float32(x)) for x in (fx, fy, cx, cy))
+        with N.device_guard(self.device):
+            s = N.stream_ptr(self.device)
+            info = (C.c_int * 4)()
+            while True:
+                rc = N.check(L.gs2m_tsdf_touch(self._dom, self.voxel, self.trunc, W, H, _ptr(d), self.depth_trunc, fx, fy, cx, cy,
+                                               c2w, self.capacity, _ptr(self.state), _ptr(self.index), _ptr(self.block_coords),
+                                               _ptr(self.touched), _ptr(self.touch_ws), info, C.c_void_p(s)), "gs2m_tsdf_touch")
+                if rc != POOL_FULL:
+                    break
+                self._grow(max(int(info[0]), 2 * self.capacity))  # nothing but the ignored count was written: repeat
+            self.ignored_points += int(info[3])
+            self.n_blocks = int(info[0])
+            N.check(L.gs2m_tsdf_integrate(self.voxel, self.trunc, W, H, _ptr(d), _ptr(c), self.depth_trunc, fx, fy, cx, cy, w2c_h,
+                                          int(info[1]), _ptr(self.touched), _ptr(self.block_coords), _ptr(self.tsdf),
+                                          _ptr(self.weight), _ptr(self.color), C.c_void_p(s)), "gs2m_tsdf_integrate")
+        return int(info[1])
+
+    def extract_triangle_mesh(self):
+        L, n = N.lib(), self.n_blocks
+        if n == 0:
+            return TriangleMesh()
+        mb = C.c_longlong()
+        N.check(L.gs2m_tsdf_workspace_bytes(self._dom, n, None, C.byref(mb)), "gs2m_tsdf_workspace_bytes")
+        with N.device_guard(self.device):
+            s = C.c_void_p(N.stream_ptr(self.device))
+            ws = torch.empty(mb.value, dtype=torch.uint8, device=self.device)
+            tot = (C.c_longlong * 2)()
+            N.check(L.gs2m_tsdf_mesh_count(self._dom, n, _ptr(self.index), _ptr(self.block_coords), _ptr(self.tsdf),
+                                           _ptr(self.weight), _ptr(ws), tot, s), "gs2m_tsdf_mesh_count")
+            V, F = int(tot[0]), int(tot[1])
+            verts = torch.empty((max(V, 1), 3), dtype=torch.float32, device=self.device)
+            cols = torch.empty_like(verts)
+            tris = torch.empty((max(F, 1), 3), dtype=torch.int32, device=self.device)
+            N.check(L.gs2m_tsdf_mesh_emit(self._dom, self.voxel, n, _ptr(self.index), _ptr(self.block_coords), _ptr(self.tsdf),
+                                          _ptr(self.color), _ptr(ws), V, F, _ptr(verts), _ptr(cols), _ptr(tris), s),
+                    "gs2m_tsdf_mesh_emit")
+            return TriangleMesh(verts[:V].cpu().numpy(), tris[:F].cpu().numpy(), cols[:V].cpu().numpy())
+
+    def state_arrays(self):
+        """Tests: (block coords (n, 3) int32 -- read back through gs2m_tsdf_block_coords --, tsdf (n, 4096), weight (n, 4096),
+        color (n, 3, 4096) on 0..255), slot order, numpy."""
+        n = self.n_blocks
+        coords = np.zeros((n, 3), np.int32)
+        with N.device_guard(self.device):
+            N.check(N.lib().gs2m_tsdf_block_coords(n, _ptr(self.block_coords), coords.ctypes.data_as(C.c_void_p),
+                                                   C.c_void_p(N.stream_ptr(self.device))), "gs2m_tsdf_block_coords")
+        return coords, self.tsdf[:n].cpu().numpy(), self.weight[:n].cpu().numpy(), self.color[:n].cpu().numpy()
+
+
+# ---- render.py's drop-ins ---------------------------------------------------------------------------------------------
+
+def quantize_depth_mm(depth):
+    """The reference's `(depth * 1000).astype(np.uint16)` read back with depth_scale 1000, as fp32 torch ops: whole
+    millimetres, truncated.  Deliberate difference: depths >= 65.536 (and negative ones) become 0 instead of wrapping."""
+    q = torch.trunc(depth * 1000.0)
+    q = torch.where((q >= 0) & (q < 65536.0), q, torch.zeros_like(q))
+    return q / 1000.0
+
+
+def _view_w2c(view):
+    return view.world_view_transform.transpose(0, 1).detach().cpu().double().numpy()
+
+
+def _points_from_depth(view, depth):
+    """loss_utils._get_points_from_depth at scale 1: camera rays times depth, to world space with the view's R, T."""
+    rays = view.get_rays()
+    pts = (rays * depth[..., None]).reshape(-1, 3)
+    R = torch.as_tensor(np.asarray(view.R), dtype=torch.float32, device=depth.device)
+    T = torch.as_tensor(np.asarray(view.T), dtype=torch.float32, device=depth.device)
+    return (pts - T) @ R.transpose(-1, -2)
+
+
+def _load_color(view, idx, render_dir, colors):
+    if colors is not None:
+        return colors[idx]
+    from PIL import Image
+    name = getattr(view, "image_name", None) or f"{idx:05d}.png"
+    stem = name.rsplit(".", 1)[0]
+    return torch.from_numpy(np.asarray(Image.open(os.path.join(str(render_dir), f"{stem}.png")).convert("RGB"), dtype=np.uint8).copy())
+
+
+def fuse_depths(tsdf_depths, views, render_dir, max_depth, voxel_size, sdf_trunc, bounds=None, colors=None, quantize=True,
+                device="cuda"):
+    """utils/mesh_utils.py fuse_depths: every view's depth (tsdf_depths (N, H, W)) masked -- by the view's alpha_mask
+    (< 0.5 -> 0) when `bounds` is None and the view has one, else to the points inside `bounds` (3, 2) --, quantised to whole
+    millimetres (`quantize`), fused with the colour read from render_dir/<stem>.png (or colors[i]: (H, W, 3) uint8 / float in
+    [0, 1], or (3, H, W) float) up to `max_depth`.  The volume's domain: `bounds`, or the box of all back-projected points
+    (computed on the device), padded by sdf_trunc and one block (the block absorbs the fp32 rounding of the touch rule's
+    floor((p -/+ trunc) / L) at the box's faces).  -> TSDFVolume."""
+    dev = torch.device(device)
+    depths = []
+    for idx, view in enumerate(views):
+        d = torch.as_tensor(tsdf_depths[idx]).to(dev, torch.float32).clone()
+        h, w = d.shape
+        if bounds is not None:
+            b = torch.as_tensor(np.asarray(bounds, dtype=np.float32), device=dev)
+            pts = _points_from_depth(view, d)
+            out = ((pts[:, 0] < b[0, 0]) | (pts[:, 0] > b[0, 1]) | (pts[:, 1] < b[1, 0]) | (pts[:, 1] > b[1, 1]) |
+                   (pts[:, 2] < b[2, 0]) | (pts[:, 2] > b[2, 1]))
+            d[out.reshape(h, w)] = 0
+        elif getattr(view, "alpha_mask", None) is not None:
+            d[torch.as_tensor(view.alpha_mask).to(dev).squeeze() < 0.5] = 0
+        depths.append((quantize_depth_mm(d) if quantize else d).contiguous())
+    trunc, L = float(np.float32(sdf_trunc)), BLOCK * float(np.float32(voxel_size))
+    if bounds is not None:
+        b = np.asarray(bounds, dtype=np.float64)
+        lo, hi = b[:, 0], b[:, 1]
+    else:
+        lo, hi = _depth_aabb(depths, views, float(np.float32(max_depth)), dev)
+        if lo is None:
+            lo = hi = np.zeros(3)
+    lo, hi = lo - trunc - L, hi + trunc + L
+    vol = TSDFVolume(voxel_size, sdf_trunc, max_depth, lo, hi, device=dev)
+    for idx, view in enumerate(views):
+        vol.integrate(depths[idx], _load_color(view, idx, render_dir, colors), view.Fx, view.Fy, view.Cx, view.Cy, _view_w2c(view))
+    return vol
+
+
+def _depth_aabb(depths, views, depth_trunc, dev):
+    """The AABB of every view's stride-4 back-projected points (gs2m_tsdf_points_aabb), or (None, None) when there is none."""
+    key = torch.tensor([2 ** 31 - 1] * 3 + [-2 ** 31] * 3, dtype=torch.int32, device=dev)
+    with N.device_guard(dev):
+        s = C.c_void_p(N.stream_ptr(dev))
+        for d, view in zip(depths, views):
+            H, W = d.shape
+            N.check(N.lib().gs2m_tsdf_points_aabb(W, H, _ptr(d), depth_trunc, float(view.Fx), float(view.Fy), float(view.Cx),
+                                                  float(view.Cy), _host_mat(c2w_of(_view_w2c(view))), _ptr(key), s),
+                    "gs2m_tsdf_points_aabb")
+        k = key.cpu().numpy().astype(np.int32)
+    if k[0] > k[3]:
+        return None, None
+    bits = np.where(k >= 0, k, k ^ np.int32(0x7FFFFFFF)).astype(np.int32)
+    f = bits.view(np.float32).astype(np.float64)
+    return f[:3], f[3:]
+
+
+def cluster_connected_triangles(mesh):
+    """Open3D's TriangleMesh.cluster_connected_triangles: triangles sharing an edge are connected.
+    -> (cluster index per triangle, triangles per cluster)."""
+    from scipy.sparse import coo_matrix
+    from scipy.sparse.csgraph import connected_components
+    t = np.asarray(mesh.triangles, dtype=np.int64)
+    F = len(t)
+    if F == 0:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64)
+    e = np.sort(np.stack([t[:, [0, 1]], t[:, [1, 2]], t[:, [2, 0]]], axis=1).reshape(-1, 2), axis=1)
+    key = e[:, 0] * (int(t.max()) + 1) + e[:, 1]
+    owner = np.repeat(np.arange(F), 3)
+    order = np.argsort(key, kind="stable")
+    ks, os_ = key[order], owner[order]
+    same = ks[1:] == ks[:-1]
+    g = coo_matrix((np.ones(int(same.sum())), (os_[:-1][same], os_[1:][same])), shape=(F, F))
+    n, labels = connected_components(g, directed=False)
+    return labels, np.bincount(labels, minlength=n)
+
+
+def post_process_mesh(mesh, cluster_to_keep=1):
+    """utils/mesh_utils.py post_process_mesh: keep the clusters of at least max(cluster_to_keep-th largest, 50) triangles,
+    then drop unreferenced vertices and degenerate triangles (two equal vertex ids).  cluster_to_keep beyond the number of
+    clusters keeps them all (the reference's numpy indexing would raise)."""
+    t = np.asarray(mesh.triangles, dtype=np.int32)
+    if len(t) == 0:
+        return TriangleMesh(np.zeros((0, 3), np.float32), t, np.zeros((0, 3), np.float32))
+    labels, counts = cluster_connected_triangles(mesh)
+    nth = np.sort(counts)[-min(int(cluster_to_keep), len(counts))]
+    keep = counts[labels] >= max(int(nth), 50)
+    t = t[keep]
+    used = np.zeros(len(mesh.vertices), bool)
+    used[t.reshape(-1)] = True
+    remap = np.cumsum(used) - 1
+    t = remap[t].astype(np.int32)
+    t = t[(t[:, 0] != t[:, 1]) & (t[:, 1] != t[:, 2]) & (t[:, 2] != t[:, 0])]
+    return TriangleMesh(np.asarray(mesh.vertices)[used], t, np.asarray(mesh.vertex_colors)[used])
+
+
+_PLY_VERTEX = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+_PLY_FACE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
+
+
+def write_mesh(file, mesh):
+    """Binary little-endian PLY: float x y z, uchar red green blue (colour * 255 rounded to nearest), int32 face lists."""
+    v = np.asarray(mesh.vertices, dtype=np.float32).reshape(-1, 3)
+    c = np.asarray(mesh.vertex_colors, dtype=np.float64).reshape(-1, 3)
+    t = np.asarray(mesh.triangles, dtype=np.int32).reshape(-1, 3)
+    va = np.zeros(len(v), _PLY_VERTEX)
+    for k, n in enumerate("xyz"):
+        va[n] = v[:, k]
+    for k, n in enumerate(("red", "green", "blue")):
+        va[n] = np.clip(np.rint(c[:, k] * 255.0), 0, 255).astype(np.uint8) if len(c) else 0
+    fa = np.zeros(len(t), _PLY_FACE)
+    fa["n"] = 3
+    fa["v"] = t
+    head = ("ply\nformat binary_little_endian 1.0\ncomment gs2m_mesh TSDF mesh\n"
+            f"element vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\n"
+            "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+            f"element face {len(t)}\nproperty list uchar int vertex_indices\nend_header\n")
+    with open(str(file), "wb") as f:
+        f.write(head.encode("ascii"))
+        f.write(va.tobytes())
+        f.write(fa.tobytes())
+
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "<i2", "int16": "<i2", "ushort": "<u2",
+              "uint16": "<u2", "int": "<i4", "int32": "<i4", "uint": "<u4", "uint32": "<u4", "float": "<f4", "float32": "<f4",
+              "double": "<f8", "float64": "<f8"}
+
+
+def read_mesh(file):
+    """Binary little-endian PLY with a vertex element (x y z, optional red green blue uchar, other scalar properties
+    skipped) and a triangle face element (list uchar|int int|uint) -> TriangleMesh."""
+    with open(str(file), "rb") as f:
+        data = f.read()
+    end = data.index(b"end_header\n") + len(b"end_header\n")
+    lines = data[:end].decode("ascii").split("\n")
+    if "format binary_little_endian 1.0" not in lines:
+        raise ValueError(f"{file}: not a binary little-endian PLY")
+    elems = []
+    for ln in lines:
+        p = ln.split()
+        if not p:
+            continue
+        if p[0] == "element":
+            elems.append([p[1], int(p[2]), []])
+        elif p[0] == "property":
+            elems[-1][2].append(p[1:])
+    off, verts, tris, cols = end, None, None, None
+    for name, n, props in elems:
+        if props and props[0][0] == "list":
+            cnt, idx = _PLY_TYPES[props[0][1]], _PLY_TYPES[props[0][2]]
+            dt = np.dtype([("n", cnt), ("v", idx, (3,))])
+            a = np.frombuffer(data, dt, n, off)
+            if n and not np.all(a["n"] == 3):
+                raise ValueError(f"{file}: only triangle faces are read")
+            off += dt.itemsize * n
+            if name == "face":
+                tris = a["v"].astype(np.int32)
+            continue
+        dt = np.dtype([(q[1], _PLY_TYPES[q[0]]) for q in props])
+        a = np.frombuffer(data, dt, n, off)
+        off += dt.itemsize * n
+        if name == "vertex":
+            verts = np.stack([a[k].astype(np.float32) for k in "xyz"], axis=1) if n else np.zeros((0, 3), np.float32)
+            if "red" in a.dtype.names:
+                cols = np.stack([a[k].astype(np.float32) / 255.0 for k in ("red", "green", "blue")], axis=1)
+    return TriangleMesh(verts, tris if tris is not None else np.zeros((0, 3), np.int32), cols)
+
+
+# ---- command line: render.py --extract_mesh for a saved model ---------------------------------------------------------
+
+def render_views(gaussians, views, render_dir, device="cuda"):
+    """Depth and the SH colour of every view with this repository's render(); the colours are saved as render_dir/<stem>.png
+    as render.py saves them (torchvision.utils.save_image rounding).  -> (N, H, W) depths on the device."""
+    from PIL import Image
+    from gaussian_renderer import render
+    from gs2m_scene import PipelineParams
+    os.makedirs(render_dir, exist_ok=True)
+    bg = torch.zeros(3, device=device)
+    depths = []
+    with torch.no_grad():
+        for k, view in enumerate(views):
+            if getattr(view, "image_name", None) is None:
+                view.image_name = f"{k:05d}.png"
+            out = render(view, gaussians, PipelineParams(), bg, material_stage=True)  # as render.py: the depth map needs the G-buffer
+            depths.append(out["depth_map"].squeeze(0).float().clone())
+            img = out["render"].clamp(0.0, 1.0).mul(255).add_(0.5).clamp_(0, 255).permute(1, 2, 0).to(torch.uint8).cpu().numpy()
+            Image.fromarray(img).save(os.path.join(render_dir, view.image_name.rsplit(".", 1)[0] + ".png"))
+    return torch.stack(depths)
+
+
+def extract_mesh(gaussians, views, cameras_extent, out_dir, max_depth=-1.0, voxel_size=-1.0, sdf_trunc=-1.0, num_clusters=1,
+                 bounds=None, device="cuda"):
+    """render.py's --extract_mesh path: render, fuse, extract; writes out_dir/{config.json, tsdf_mesh.ply, tsdf_post.ply}.
+    -> (raw mesh, post-processed mesh)."""
+    os.makedirs(out_dir, exist_ok=True)
+    max_depth = max_depth if max_depth > 0 else 2.0 * cameras_extent
+    voxel_size = voxel_size if voxel_size > 0 else max_depth / 1024.0
+    sdf_trunc = sdf_trunc if sdf_trunc > 0 else 4.0 * voxel_size
+    with open(os.path.join(out_dir, "config.json"), "w") as f:
+        json.dump({"max_depth": max_depth, "voxel_size": voxel_size, "sdf_trunc": sdf_trunc}, f, indent=4)
+    render_dir = os.path.join(out_dir, "renders")
+    depths = render_views(gaussians, views, render_dir, device)
+    vol = fuse_depths(depths, views, render_dir, max_depth, voxel_size, sdf_trunc, bounds, device=device)
+    mesh = vol.extract_triangle_mesh()
+    write_mesh(os.path.join(out_dir, "tsdf_mesh.ply"), mesh)
+    post = post_process_mesh(mesh, num_clusters)
+    write_mesh(os.path.join(out_dir, "tsdf_post.ply"), post)
+    print(f"[>] {len(mesh.vertices)} vertices / {len(mesh.triangles)} triangles raw, {len(post.vertices)} / {len(post.triangles)} "
+          f"post-processed; {vol.n_blocks} blocks, {vol.ignored_points} points outside the domain -> {out_dir}")
+    return mesh, post
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="TSDF mesh of a trained model (render.py --extract_mesh)")
+    ap.add_argument("--ply", required=True, help="the model's point_cloud.ply")
+    ap.add_argument("--source-path", "-s", required=True, help="COLMAP-format dataset (or NeRF-synthetic with --blender)")
+    ap.add_argument("--blender", action="store_true")
+    ap.add_argument("--split", choices=("train", "test"), default="train",
+                    help="test: transforms_test.json (--blender) or every 8th COLMAP image (the reference's llffhold)")
+    ap.add_argument("--resolution", "-r", type=int, default=1)
+    ap.add_argument("--output", "-o", required=True)
+    ap.add_argument("--max_depth", type=float, default=-1.0)
+    ap.add_argument("--voxel_size", type=float, default=-1.0)
+    ap.add_argument("--sdf_trunc", type=float, default=-1.0)
+    ap.add_argument("--num_clusters", type=int, default=1)
+    ap.add_argument("--dtu", action="store_true", help="render.py's DTU preset: 5.0 / 0.002 / 0.008 / 1")
+    ap.add_argument("--sh-degree", type=int, default=3)
+    a = ap.parse_args(argv)
+    if a.dtu:
+        a.max_depth, a.voxel_size, a.sdf_trunc, a.num_clusters = 5.0, 0.002, 4.0 * 0.002, 1
+    import gs2m_train as T
+    from gs2m_model import GaussianModel
+    if a.blender:
+        cams, _, _, _, extent = T.load_blender_dataset(a.source_path, "transforms_test.json" if a.split == "test" else "transforms_train.json")
+    else:
+        cams, _, _, _, extent = T.load_colmap_dataset(a.source_path, resolution=a.resolution)
+        if a.split == "test":
+            cams = cams[::8]
+    model = GaussianModel(a.sh_degree)
+    model.load_ply(a.ply)
+    extract_mesh(model, cams, extent, a.output, a.max_depth, a.voxel_size, a.sdf_trunc, a.num_clusters)
+
+
+if __name__ == "__main__":
+    main()

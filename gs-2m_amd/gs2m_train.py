@@ -509,6 +509,8 @@ if __name__ == "__main__":
     ap.add_argument("--c4-splat", type=float, default=None)
     ap.add_argument("--c4-grain", type=float, default=None)
     ap.add_argument("--c4-fx", type=float, default=None)
+    ap.add_argument("--extract-mesh", default=None, metavar="DIR", help="after training: TSDF mesh of the training views into DIR "
+                    "(tsdf_mesh.ply, tsdf_post.ply, config.json; gs2m_mesh.extract_mesh with render.py's defaults)")
     a = ap.parse_args()
     if a.c4:
         if a.c4_detail is not None:
@@ -543,3 +545,7 @@ if __name__ == "__main__":
     print({k: (round(v, 4) if isinstance(v, float) else v) for k, v in st.items() if k not in ("pbr_loss", "lighting", "mv_loss")})
     if a.save_ply:
         model.save_ply(a.save_ply)
+    if a.extract_mesh:
+        import gs2m_mesh
+        cams, _, _, _, extent = scene or synthetic_scene(a.true_gaussians, a.views, a.width, a.height)
+        gs2m_mesh.extract_mesh(model, cams, extent, a.extract_mesh)

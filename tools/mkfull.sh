@@ -6,7 +6,10 @@ C=/root/repo/gs-2m_amd/csrc
 D=$C/variants/full_$1
 mkdir -p $D
 objs=""
-for f in api preprocess binning tile_sort radix_sort blend_fwd_q blend_bwd_q gaussian_bwd knn render_ops optim ssim texture cubemap mvs loss_ops; do
+# every translation unit the library links, as csrc/Makefile lists them (SRCS)
+units=$(sed -n 's/^SRCS = //p' $C/Makefile | sed 's/\.hip//g')
+[ -n "$units" ] || { echo "no SRCS in $C/Makefile" >&2; exit 1; }
+for f in $units; do
   objs="$objs $D/$f.o"
   echo "$D/$f.o: $C/$f.hip; /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -fPIC -ffp-contract=off -fno-slp-vectorize -std=c++17 -Wno-inline-asm -I$C $2 -c $C/$f.hip -o $D/$f.o"
 done > $D/rules.txt

@@ -21,7 +21,12 @@ EXPORTS = ("gs2m_raster_forward", "gs2m_raster_backward", "gs2m_raster_mark_visi
            "gs2m_affine_mean", "gs2m_densification_stats", "gs2m_edge_gradient", "gs2m_image_loss_backward", "gs2m_image_loss_forward", "gs2m_loss_workspace_bytes", "gs2m_mv_geo_loss_backward", "gs2m_mv_geo_loss_forward", "gs2m_mv_take_backward", "gs2m_mv_take_forward", "gs2m_ncc_tail_backward", "gs2m_ncc_tail_forward", "gs2m_subset_thin", "gs2m_subset_remove", "gs2m_pbr_inputs_backward", "gs2m_pbr_inputs_forward", "gs2m_plane_loss_backward", "gs2m_plane_loss_forward", "gs2m_ssim_backward_uniform", "gs2m_tv_loss_backward", "gs2m_tv_loss_forward",
            # include/gs2m_mesh.h (TSDF fusion and marching cubes)
            "gs2m_tsdf_workspace_bytes", "gs2m_tsdf_points_aabb", "gs2m_tsdf_touch", "gs2m_tsdf_integrate", "gs2m_tsdf_mesh_count",
-           "gs2m_tsdf_mesh_emit", "gs2m_tsdf_block_coords")
+           "gs2m_tsdf_mesh_emit", "gs2m_tsdf_block_coords",
+           # include/gs2m_eval.h (DTU mesh evaluation)
+           "gs2m_eval_transform", "gs2m_eval_sample_workspace_bytes", "gs2m_eval_sample_rows", "gs2m_eval_sample_count",
+           "gs2m_eval_sample_emit", "gs2m_eval_gather", "gs2m_eval_grid_bytes", "gs2m_eval_grid_build", "gs2m_eval_thin_workspace_bytes",
+           "gs2m_eval_thin", "gs2m_eval_filter", "gs2m_eval_above_plane", "gs2m_eval_scan_workspace_bytes", "gs2m_eval_compact",
+           "gs2m_eval_nearest", "gs2m_eval_masked_mean")
 
 STAGES = ("preprocess", "unused1", "scan", "emit", "tile_sort", "lists", "blend_fwd", "unused7", "blend_bwd",
           "gaussian_bwd")
@@ -233,6 +238,25 @@ def lib():
     L.gs2m_tsdf_mesh_emit.restype = i
     L.gs2m_tsdf_block_coords.argtypes = [i, p, p, p]
     L.gs2m_tsdf_block_coords.restype = i
+    d = C.c_double
+    for name, args in (("gs2m_eval_transform", [ll, p, d, p, p, p]),
+                       ("gs2m_eval_sample_workspace_bytes", [ll, ll, p, p]),
+                       ("gs2m_eval_sample_rows", [ll, p, ll, p, d, p, p, p]),
+                       ("gs2m_eval_sample_count", [ll, ll, p, p, p, p]),
+                       ("gs2m_eval_sample_emit", [ll, p, ll, p, ll, p, p, ll, p, p]),
+                       ("gs2m_eval_gather", [ll, p, p, p, p]),
+                       ("gs2m_eval_grid_bytes", [ll, p, p]),
+                       ("gs2m_eval_grid_build", [ll, p, d, p, p, p]),
+                       ("gs2m_eval_thin_workspace_bytes", [ll, p]),
+                       ("gs2m_eval_thin", [ll, p, p, d, p, p, p, p]),
+                       ("gs2m_eval_filter", [ll, p, p, p, p, d, p, p, p, p]),
+                       ("gs2m_eval_above_plane", [ll, p, p, p, p]),
+                       ("gs2m_eval_scan_workspace_bytes", [ll, p]),
+                       ("gs2m_eval_compact", [ll, p, p, i, p, p, p, p]),
+                       ("gs2m_eval_nearest", [ll, p, ll, d, p, d, p, p]),
+                       ("gs2m_eval_masked_mean", [ll, p, d, p, p, p, p])):
+        getattr(L, name).argtypes = args
+        getattr(L, name).restype = i
     _lib = L
     return L
 

@@ -300,7 +300,7 @@ static int forward_impl(gs2m_alloc_fn geometry_alloc, void* geometry_user, gs2m_
             // stable sort of (tile id, emission slot) on the tile bits: every tile's span comes out in index order; the last pass
             // also records every tile's range (identifyTileRanges, rasterizer_impl.cu:108-129)
             HIP_TRY(gs2m_radix_sort_pairs(b.temp, b.temp_bytes, b.keys_unsorted, nullptr, b.sort_keyA, b.sort_valA, b.tile_keys, b.slot_sorted,
-                                          (size_t)R, tile_bits, true, s, SideSum{nullptr, nullptr, nullptr}, im.ranges_raw, g.tile_hist));
+                                          (size_t)R, tile_bits, true, s, im.ranges_raw, g.tile_hist));
         }
     } else {
         HIP_TRY(gs2m_zero_async(im.ranges_raw, tiles * 2 * sizeof(uint32_t), s));

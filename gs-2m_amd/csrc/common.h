@@ -78,6 +78,7 @@ struct HeavyUnit {      // 80 bytes per unit, at the end of the binning buffer
 #define ROW_FEAT 11
 
 static inline size_t gs2m_align_up(size_t x, size_t a = GS2M_ALIGN) { return (x + a - 1) & ~(a - 1); }
+static inline int gs2m_status(hipError_t e) { return e == hipSuccess ? GS2M_OK : GS2M_ERR_HIP; }
 
 // Round 5: no global sort.  Gaussians are binned in INDEX order (count -> scan -> fill, binning.hip) and every tile's span is
 // sorted by (depth, id) on chip (tile_sort.hip); rows of a Gaussian's gradient partials are numbered in index order too.
@@ -226,24 +227,13 @@ BinningState gs2m_carve_binning(char* base, size_t R, size_t temp_bytes, size_t 
 size_t gs2m_binning_temp_bytes(size_t R, int tile_bits);
 ImageState gs2m_carve_image(char* base, size_t N, size_t tiles);
 
-// hand-written onesweep radix sort (radix_sort.hip).  Rounds 1-4 sorted the Gaussians by depth and the instances by tile with
-// it; since round 5 the rasterizer buckets by tile and sorts each tile on chip (binning.hip, tile_sort.hip), and the only
-// user left is distCUDA2's Morton order (knn.hip).
+// hand-written onesweep radix sort of (u32 key, u32 value) pairs (radix_sort.hip).  Users: the stable sort of the emitted
+// instances by tile (api.hip: digit histogram from emit_kernel through ext_hist, tile ranges out through range_raw), distCUDA2's
+// Morton order (knn.hip) and the grid buckets of the DTU evaluation (mesh_eval.hip).
 size_t gs2m_radix_temp_bytes(size_t n, int total_bits);
-struct SideBuckets {
-    const uint32_t* tt;
-    uint32_t* buckets;
-    uint32_t* supers;
-};
-struct SideSum {
-    const uint32_t* tt;
-    uint32_t* acc;
-    uint32_t* landing;
-};
 hipError_t gs2m_radix_sort_pairs(void* temp, size_t temp_bytes, const uint32_t* kin, const uint32_t* vin, uint32_t* kA,
                                  uint32_t* vA, uint32_t* kB, uint32_t* vB, size_t n, int total_bits, bool prezeroed, hipStream_t s,
-                                 SideSum sum = SideSum{nullptr, nullptr, nullptr}, uint32_t* range_raw = nullptr,
-                                 const uint32_t* ext_hist = nullptr, SideBuckets sb = SideBuckets{nullptr, nullptr, nullptr});
+                                 uint32_t* range_raw = nullptr, const uint32_t* ext_hist = nullptr);
 #define GS2M_HIST_COPIES 8
 #define GS2M_HIST_COPY_WORDS 1024
 void gs2m_radix_plan(int total_bits, int* npass, int bits[4], int shift[4]);
@@ -310,30 +300,10 @@ void gs2m_launch_mark_visible(int P, const float* means3D, const float* viewmatr
 __device__ __forceinline__ float u2f(uint32_t u) { return __uint_as_float(u); }
 __device__ __forceinline__ uint32_t f2u(float f) { return __float_as_uint(f); }
 
-// DPP cross-lane move (gfx9 encodings).  Lanes masked off by row_mask/bank_mask get 0.
-template <int CTRL, int ROW_MASK = 0xF, int BANK_MASK = 0xF>
-__device__ __forceinline__ float dpp_mov0(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, BANK_MASK, false));
-}
-#define DPP_QUAD_XOR1 0xB1     // quad_perm [1,0,3,2]
-#define DPP_QUAD_XOR2 0x4E     // quad_perm [2,3,0,1]
+// DPP control words (gfx9 encodings) of the cross-lane exchanges in tile_sort.hip
 #define DPP_QUAD_PERM(a, b, c, d) ((a) | ((b) << 2) | ((c) << 4) | ((d) << 6))
 #define DPP_ROW_HALF_MIRROR 0x141
 #define DPP_ROW_MIRROR 0x140
-#define DPP_ROW_BCAST15 0x142
-#define DPP_ROW_BCAST31 0x143
-#define DPP_ROW_SHR(n) (0x110 + (n))
-
-// Sum over the 64 lanes of a wave; the total is valid in lanes 48..63 (row 3).
-__device__ __forceinline__ float wave_sum_row3(float v) {
-    v += dpp_mov0<DPP_QUAD_XOR1>(v);
-    v += dpp_mov0<DPP_QUAD_XOR2>(v);
-    v += dpp_mov0<DPP_ROW_HALF_MIRROR>(v);
-    v += dpp_mov0<DPP_ROW_MIRROR>(v);
-    v += dpp_mov0<DPP_ROW_BCAST15, 0xA>(v);
-    v += dpp_mov0<DPP_ROW_BCAST31, 0xC>(v);
-    return v;
-}
 
 // Workgroup barrier that is safe at loop headers.  hipcc (ROCm 7.2, gfx950) emitted a bare
 // `s_barrier` for a __syncthreads() at the top of a loop whose back edge ends in LDS stores: the
@@ -344,10 +314,6 @@ __device__ __forceinline__ float wave_sum_row3(float v) {
 __device__ __forceinline__ void gs2m_sync() {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __syncthreads();
-}
-__device__ __forceinline__ int gs2m_sync_count(bool pred) {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    return __syncthreads_count(pred);
 }
 __device__ __forceinline__ int gs2m_sync_or(bool pred) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -365,14 +331,36 @@ __device__ __forceinline__ bool gs2m_heavy(uint32_t cnt, uint32_t crowded) {
     return cnt >= (light > crowded ? GS2M_HEAVY_TILES_CROWDED : GS2M_HEAVY_TILES) && cnt < (1u << 29);
 }
 
-// Inclusive prefix sum over the 64 lanes of a wave (u32).
-__device__ __forceinline__ uint32_t wave_inclusive_scan_u32(uint32_t v, int lane) {
+// Inclusive prefix sum over the 64 lanes of a wave (T: uint32_t or unsigned long long).
+template <typename T>
+__device__ __forceinline__ T gs2m_wave_inclusive_scan(T v, int lane) {
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
-        uint32_t t = __shfl_up(v, d, 64);
+        const T t = __shfl_up(v, d, 64);
         if (lane >= d) v += t;
     }
     return v;
+}
+__device__ __forceinline__ uint32_t wave_inclusive_scan_u32(uint32_t v, int lane) { return gs2m_wave_inclusive_scan(v, lane); }
+
+// Exclusive prefix sum of one value per thread over a workgroup of 256 (4 waves); s_w: 4 words of LDS, *total: the
+// workgroup's sum.  (binning.hip's 1024-thread scans are shaped for the front end's critical path and stay their own.)
+template <typename T>
+__device__ __forceinline__ T gs2m_wg_exclusive_scan(T v, T* s_w, T* total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const T inc = gs2m_wave_inclusive_scan(v, lane);
+    if (lane == 63) s_w[w] = inc;
+    __syncthreads();
+    T off = 0, tot = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const T x = s_w[k];
+        off += k < w ? x : T(0);
+        tot += x;
+    }
+    __syncthreads();  // s_w may be written again by the caller's next scan
+    *total = tot;
+    return off + inc - v;
 }
 
 // alpha evaluation shared bit-for-bit by the forward and backward blend kernels:
@@ -389,34 +377,17 @@ __device__ __forceinline__ float gs2m_power(float dx, float dy, float A, float B
     const float t3 = (B * dx) * dy;
     return (-0.5f * (t1 + t2)) - t3;
 }
-// Does the region {q(dx, dy) = A dx^2 + 2B dx dy + C dy^2 <= t2} around (gx, gy) reach the pixel rectangle
-// [x0, x1] x [y0, y1]?  Exact up to the margins t2 carries (preprocess.hip): the centre lies inside, or the
-// minimum of q over the four edges is within t2.  Instances that fail cannot contribute to any pixel of the
-// rectangle; t2 >= 3e38 marks Gaussians whose culling is disabled (indefinite / ill-conditioned conic).
-// The blend loops are issue bound and this test runs once per (instance, quadrant), so it is written for
-// instruction count: v_rcp_f32 (1 ulp, second-order effect on q at the clamped minimiser), v_med3 clamps.
-//
-// Minimum of q over the two edges dx = l, dx = u with the free coordinate clamped to [fl, fu]
-// (a, c = the conic entries of the fixed and the free coordinate, b2 = 2B).
-__device__ __forceinline__ float gs2m_edge_pair_qmin(float a, float b2, float c, float l, float u, float fl, float fu) {
-    const float nhr = -0.5f * __builtin_amdgcn_rcpf(c);
-    const float bl = b2 * l, bu = b2 * u;
-    const float fml = __builtin_amdgcn_fmed3f(bl * nhr, fl, fu), fmu = __builtin_amdgcn_fmed3f(bu * nhr, fl, fu);
-    const float ql = __builtin_fmaf(__builtin_fmaf(c, fml, bl), fml, (a * l) * l);
-    const float qu = __builtin_fmaf(__builtin_fmaf(c, fmu, bu), fmu, (a * u) * u);
-    return fminf(ql, qu);
-}
-__device__ __forceinline__ bool gs2m_reaches_rect(float gx, float gy, float A, float B, float C, float t2, float x0,
-                                                  float x1, float y0, float y1) {
-    const float lx = x0 - gx, ux = x1 - gx, ly = y0 - gy, uy = y1 - gy;  // rectangle relative to the centre
-    const bool inside = lx <= 0.f && ux >= 0.f && ly <= 0.f && uy >= 0.f;
-    const float b2 = B + B;
-    const float qmin = fminf(gs2m_edge_pair_qmin(A, b2, C, lx, ux, ly, uy), gs2m_edge_pair_qmin(C, b2, A, ly, uy, lx, ux));
-    return !(t2 < 3.0e38f) || inside || qmin <= __builtin_fmaf(1.0e-3f, fabsf(qmin), t2);
-}
-// gs2m_reaches_rect for the four 8x8 quadrants of the 16x16 tile whose first pixel is (x0, y0), sharing what the four
-// tests have in common (two reciprocals instead of eight, the per-line products): bit q of the result is EXACTLY
-// gs2m_reaches_rect(..., x0 + 8 (q & 1), + 7, y0 + 8 (q >> 1), + 7) -- same operations on the same values per edge.
+// Which of the four 8x8 quadrants of the 16x16 tile whose first pixel is (x0, y0) does the region
+// {q(dx, dy) = A dx^2 + 2B dx dy + C dy^2 <= t2} around (gx, gy) reach?  Bit q of the result: the quadrant's pixel rectangle
+// [x0 + 8 (q & 1), + 7] x [y0 + 8 (q >> 1), + 7].  t2 is the upper bound of q where alpha can reach 1/255, with the margins
+// preprocess.hip gives it.  Exact up to those margins: a rectangle is reached when the centre lies inside it, or the minimum of
+// q over its four edges -- on the edge dx = l the minimiser in dy is -B l / C clamped to the edge, likewise with the roles of
+// x and y exchanged -- is within t2, with a relative margin of 1e-3 for the rounding of that minimum.  Instances that fail
+// cannot contribute to any pixel of the quadrant; t2 >= 3e38 marks Gaussians whose culling is disabled (indefinite /
+// ill-conditioned conic): every quadrant is reported.
+// The blend loops are issue bound and this test runs once per (instance, quadrant), so it is written for instruction count:
+// v_rcp_f32 (1 ulp, second-order effect on q at the clamped minimiser), v_med3 clamps, and the four quadrants share what
+// their tests have in common (two reciprocals instead of eight, the per-line products).
 __device__ __forceinline__ uint32_t gs2m_reaches_quads(float gx, float gy, float A, float B, float C, float t2, float x0, float y0) {
     const float b2 = B + B;
     const float nhrC = -0.5f * __builtin_amdgcn_rcpf(C), nhrA = -0.5f * __builtin_amdgcn_rcpf(A);
@@ -455,18 +426,6 @@ __device__ __forceinline__ uint32_t gs2m_reaches_quads(float gx, float gy, float
         mask |= hit ? (1u << q) : 0u;
     }
     return mask;
-}
-// The same test with the work of one instance split over two lanes (lane and lane ^ 32): `swap` lanes take
-// the horizontal edges by exchanging the roles of x and y, then the halves are combined.
-__device__ __forceinline__ bool gs2m_reaches_rect_split(bool swap, float gx, float gy, float A, float B, float C,
-                                                        float t2, float x0, float x1, float y0, float y1) {
-    const float lx = x0 - gx, ux = x1 - gx, ly = y0 - gy, uy = y1 - gy;
-    const bool inside = lx <= 0.f && ux >= 0.f && ly <= 0.f && uy >= 0.f;
-    const float q = gs2m_edge_pair_qmin(swap ? C : A, B + B, swap ? A : C, swap ? ly : lx, swap ? uy : ux,
-                                        swap ? lx : ly, swap ? ux : uy);
-    const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(q), __float_as_uint(q), false, false);
-    const float qmin = fminf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));  // own half and the partner's
-    return !(t2 < 3.0e38f) || inside || qmin <= __builtin_fmaf(1.0e-3f, fabsf(qmin), t2);
 }
 
 // exp(x) for x <= 0 through v_exp_f32

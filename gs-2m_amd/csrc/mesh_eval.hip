@@ -14,11 +14,8 @@
 // Nearest: shells of cells walked outward from the query's cell until the shell's lower bound passes the best distance or
 // max_dist; the first occupied coarse shell sets where the walk starts, or proves that nothing lies within max_dist.
 // Every sum is an integer sum or a fixed-order fp64 reduction: two runs are bitwise identical.  Compiled with -ffp-contract=off.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
 #include <math.h>
 #include "common.h"
-#include "../../include/gs2m_raster.h"
 #include "../../include/gs2m_eval.h"
 
 namespace {
@@ -30,32 +27,7 @@ constexpr int COARSE_SHIFT = 3;      // coarse cell = 8^3 fine cells
 constexpr int COARSE_SHELLS_MAX = 24;
 constexpr int CELL_LIMIT = 1 << 30;
 
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-int status(hipError_t e) { return e == hipSuccess ? GS2M_OK : GS2M_ERR_HIP; }
-
 // ---- device-wide exclusive scan of u64 counts (in place; a[n] = total) ----
-
-__device__ __forceinline__ u64 wg_exclusive_scan_u64(u64 v, u64* s_w, u64* total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    u64 inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const u64 t = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += t;
-    }
-    if (lane == 63) s_w[w] = inc;
-    __syncthreads();
-    u64 off = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const u64 x = s_w[k];
-        off += k < w ? x : 0ull;
-        tot += x;
-    }
-    __syncthreads();
-    *total = tot;
-    return off + inc - v;
-}
 
 __global__ void __launch_bounds__(256) scan_reduce_kernel(long long n, const u64* __restrict__ a, u64* __restrict__ bsum) {
     __shared__ u64 s_w[4];
@@ -64,7 +36,7 @@ __global__ void __launch_bounds__(256) scan_reduce_kernel(long long n, const u64
 #pragma unroll
     for (int k = 0; k < 4; k++) v += i0 + k < n ? a[i0 + k] : 0ull;
     u64 tot;
-    wg_exclusive_scan_u64(v, s_w, &tot);
+    gs2m_wg_exclusive_scan(v, s_w, &tot);
     if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
 }
 
@@ -75,7 +47,7 @@ __global__ void __launch_bounds__(256) scan_blocks_kernel(long long nb, u64* __r
         const long long i = b + threadIdx.x;
         const u64 v = i < nb ? bsum[i] : 0ull;
         u64 t;
-        const u64 e = wg_exclusive_scan_u64(v, s_w, &t);
+        const u64 e = gs2m_wg_exclusive_scan(v, s_w, &t);
         if (i < nb) bsum[i] = carry + e;
         carry += t;
     }
@@ -92,7 +64,7 @@ __global__ void __launch_bounds__(256) scan_down_kernel(long long n, u64* a, con
         s += v[k];
     }
     u64 tot;
-    u64 e = wg_exclusive_scan_u64(s, s_w, &tot) + bsum[blockIdx.x];
+    u64 e = gs2m_wg_exclusive_scan(s, s_w, &tot) + bsum[blockIdx.x];
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         if (i0 + k < n) a[i0 + k] = e;
@@ -221,10 +193,10 @@ struct TriWs {
 TriWs carve_tri(char* base, long long nt) {
     TriWs w;
     size_t o = 0;
-    w.n12 = (double2*)(base + o); o = align_up(o + 16 * (size_t)nt);
-    w.rows = (u64*)(base + o); o = align_up(o + 8 * (size_t)(nt + 1));
-    w.bsum = (u64*)(base + o); o = align_up(o + 8 * (size_t)(scan_blocks(nt) + 1));
-    w.err = (int*)(base + o); o = align_up(o + 8);
+    w.n12 = (double2*)(base + o); o = gs2m_align_up(o + 16 * (size_t)nt);
+    w.rows = (u64*)(base + o); o = gs2m_align_up(o + 8 * (size_t)(nt + 1));
+    w.bsum = (u64*)(base + o); o = gs2m_align_up(o + 8 * (size_t)(scan_blocks(nt) + 1));
+    w.err = (int*)(base + o); o = gs2m_align_up(o + 8);
     w.bytes = o;
     return w;
 }
@@ -236,8 +208,8 @@ struct RowWs {
 RowWs carve_row(char* base, long long nr) {
     RowWs w;
     size_t o = 0;
-    w.cnt = (u64*)(base + o); o = align_up(o + 8 * (size_t)(nr + 1));
-    w.bsum = (u64*)(base + o); o = align_up(o + 8 * (size_t)(scan_blocks(nr) + 1));
+    w.cnt = (u64*)(base + o); o = gs2m_align_up(o + 8 * (size_t)(nr + 1));
+    w.bsum = (u64*)(base + o); o = gs2m_align_up(o + 8 * (size_t)(scan_blocks(nr) + 1));
     w.bytes = o;
     return w;
 }
@@ -278,10 +250,10 @@ Grid carve_grid(char* base, long long n) {
     g.bits = grid_bits(n);
     const size_t nb = (size_t)1 << g.bits;
     size_t o = 0;
-    g.spts = (double*)(base + o); o = align_up(o + 24 * (size_t)n);
-    g.sidx = (uint32_t*)(base + o); o = align_up(o + 4 * (size_t)n);
-    g.start = (uint32_t*)(base + o); o = align_up(o + 4 * (nb + 1));
-    g.occ = (uint8_t*)(base + o); o = align_up(o + nb);
+    g.spts = (double*)(base + o); o = gs2m_align_up(o + 24 * (size_t)n);
+    g.sidx = (uint32_t*)(base + o); o = gs2m_align_up(o + 4 * (size_t)n);
+    g.start = (uint32_t*)(base + o); o = gs2m_align_up(o + 4 * (nb + 1));
+    g.occ = (uint8_t*)(base + o); o = gs2m_align_up(o + nb);
     g.bytes = o;
     return g;
 }
@@ -296,11 +268,11 @@ BuildWs carve_build(char* base, long long n, int bits) {
     uint32_t** arrs[5] = {&w.keys, &w.kA, &w.vA, &w.kB, &w.vB};
     for (auto a : arrs) {
         *a = (uint32_t*)(base + o);
-        o = align_up(o + 4 * (size_t)(n > 0 ? n : 1));
+        o = gs2m_align_up(o + 4 * (size_t)(n > 0 ? n : 1));
     }
     w.temp = base + o;
     w.temp_bytes = gs2m_radix_temp_bytes((size_t)(n > 0 ? n : 1), bits);
-    o = align_up(o + w.temp_bytes);
+    o = gs2m_align_up(o + w.temp_bytes);
     w.bytes = o;
     return w;
 }
@@ -585,10 +557,10 @@ struct ScanWs {
 ScanWs carve_scan(char* base, long long n) {
     ScanWs w;
     size_t o = 0;
-    w.psum = (double*)(base + o); o = align_up(o + 8 * (MEAN_BLOCKS + 1));
-    w.pcnt = (u64*)(base + o); o = align_up(o + 8 * (MEAN_BLOCKS + 1));
-    w.a = (u64*)(base + o); o = align_up(o + 8 * (size_t)(n + 1));
-    w.bsum = (u64*)(base + o); o = align_up(o + 8 * (size_t)(scan_blocks(n) + 1));
+    w.psum = (double*)(base + o); o = gs2m_align_up(o + 8 * (MEAN_BLOCKS + 1));
+    w.pcnt = (u64*)(base + o); o = gs2m_align_up(o + 8 * (MEAN_BLOCKS + 1));
+    w.a = (u64*)(base + o); o = gs2m_align_up(o + 8 * (size_t)(n + 1));
+    w.bsum = (u64*)(base + o); o = gs2m_align_up(o + 8 * (size_t)(scan_blocks(n) + 1));
     w.bytes = o;
     return w;
 }
@@ -607,9 +579,9 @@ ThinWs carve_thin(char* base, long long n) {
     size_t o = w.g.bytes;
     w.b = carve_build(base + o, n, w.g.bits);
     o += w.b.bytes;
-    w.rank_s = (uint32_t*)(base + o); o = align_up(o + 4 * (size_t)n);
-    w.st = (uint8_t*)(base + o); o = align_up(o + (size_t)n);
-    w.counter = (unsigned*)(base + o); o = align_up(o + 4);
+    w.rank_s = (uint32_t*)(base + o); o = gs2m_align_up(o + 4 * (size_t)n);
+    w.st = (uint8_t*)(base + o); o = gs2m_align_up(o + (size_t)n);
+    w.counter = (unsigned*)(base + o); o = gs2m_align_up(o + 4);
     w.bytes = o;
     return w;
 }
@@ -627,7 +599,7 @@ int gs2m_eval_transform(long long n, const double* in, double scale, const doubl
     if (n == 0) return GS2M_OK;
     if (n > MAX_LAUNCH) return GS2M_ERR_UNSUPPORTED;
     transform_kernel<<<blocks_of(n), 256, 0, (hipStream_t)stream>>>(n, in, scale, V3{{t[0], t[1], t[2]}}, out);
-    return status(hipGetLastError());
+    return gs2m_status(hipGetLastError());
 }
 
 int gs2m_eval_sample_workspace_bytes(long long n_tris, long long n_rows, long long* tri_bytes, long long* row_bytes) {
@@ -688,7 +660,7 @@ int gs2m_eval_sample_emit(long long n_verts, const double* verts, long long n_tr
     const RowWs rw = carve_row((char*)row_ws, n_rows);
     if (n_samples > 0)
         emit_kernel<<<blocks_of(n_samples), 256, 0, s>>>(n_verts, verts, n_tris, tris, tw.n12, tw.rows, n_rows, rw.cnt, n_samples, cloud);
-    return status(hipGetLastError());
+    return gs2m_status(hipGetLastError());
 }
 
 int gs2m_eval_gather(long long n, const double* pts, const long long* order, double* out, void* stream) {
@@ -696,7 +668,7 @@ int gs2m_eval_gather(long long n, const double* pts, const long long* order, dou
     if (n == 0) return GS2M_OK;
     if (n > MAX_LAUNCH) return GS2M_ERR_UNSUPPORTED;
     gather_kernel<<<blocks_of(n), 256, 0, (hipStream_t)stream>>>(n, pts, order, out);
-    return status(hipGetLastError());
+    return gs2m_status(hipGetLastError());
 }
 
 int gs2m_eval_grid_bytes(long long n, long long* grid_bytes, long long* build_bytes) {
@@ -712,7 +684,7 @@ int gs2m_eval_grid_build(long long n, const double* pts, double cell, void* grid
     if (n < 0 || !(cell > 0.0) || !grid || !build_ws || (n > 0 && !pts)) return GS2M_ERR_INVALID_ARG;
     if (n > MAX_POINTS) return GS2M_ERR_UNSUPPORTED;
     const Grid g = carve_grid((char*)grid, n);
-    return status(build_grid(n, pts, cell, g, carve_build((char*)build_ws, n, g.bits), (hipStream_t)stream));
+    return gs2m_status(build_grid(n, pts, cell, g, carve_build((char*)build_ws, n, g.bits), (hipStream_t)stream));
 }
 
 int gs2m_eval_thin_workspace_bytes(long long n, long long* bytes) {
@@ -756,7 +728,7 @@ int gs2m_eval_thin(long long n, const double* pts, const unsigned* rank, double 
     }
     if (host_rounds) *host_rounds = (int)(rounds < 0x7FFFFFFF ? rounds : 0x7FFFFFFF);
     thin_keep_kernel<<<blocks_of(n), 256, 0, s>>>(n, w.g.sidx, w.st, keep);
-    return status(hipGetLastError());
+    return gs2m_status(hipGetLastError());
 }
 
 int gs2m_eval_filter(long long n, const double* pts, const double* lo, const double* hi, const double* bb0, double res,
@@ -769,7 +741,7 @@ int gs2m_eval_filter(long long n, const double* pts, const double* lo, const dou
     filter_kernel<<<blocks_of(n), 256, 0, (hipStream_t)stream>>>(n, pts, V3{{lo[0], lo[1], lo[2]}}, V3{{hi[0], hi[1], hi[2]}},
                                                                  V3{{bb0[0], bb0[1], bb0[2]}}, res, mask, dims[0], dims[1], dims[2],
                                                                  flags);
-    return status(hipGetLastError());
+    return gs2m_status(hipGetLastError());
 }
 
 int gs2m_eval_above_plane(long long n, const double* pts, const double* plane, unsigned char* flags, void* stream) {
@@ -777,7 +749,7 @@ int gs2m_eval_above_plane(long long n, const double* pts, const double* plane, u
     if (n == 0) return GS2M_OK;
     if (n > MAX_LAUNCH) return GS2M_ERR_UNSUPPORTED;
     plane_kernel<<<blocks_of(n), 256, 0, (hipStream_t)stream>>>(n, pts, plane[0], plane[1], plane[2], plane[3], flags);
-    return status(hipGetLastError());
+    return gs2m_status(hipGetLastError());
 }
 
 int gs2m_eval_scan_workspace_bytes(long long n, long long* bytes) {
@@ -817,7 +789,7 @@ int gs2m_eval_nearest(long long n_queries, const double* queries, long long n_ta
     nearest_kernel<<<blocks_of(n_queries), 256, 0, (hipStream_t)stream>>>(n_queries, queries, n_targets, cell, 1.0 / cell,
                                                                          (uint32_t)((1ll << g.bits) - 1), g.spts, g.start, g.occ,
                                                                          max_dist, (int)fs, coarse, dist);
-    return status(hipGetLastError());
+    return gs2m_status(hipGetLastError());
 }
 
 int gs2m_eval_masked_mean(long long n, const double* dist, double max_dist, void* ws, double* host_sum, long long* host_count,

@@ -19,10 +19,8 @@
 //   emit_triangles_kernel  per block: triangles in (voxel, table order), vertex ids looked up at the edges' owner voxels
 // No float atomics anywhere: every value is written by one thread in an order fixed by the scans, so two runs are bitwise
 // identical.  Compiled with -ffp-contract=off: every expression is evaluated as written, which tests/mesh_ref.py restates.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
 #include <limits.h>
-#include "../../include/gs2m_raster.h"
+#include "common.h"
 #include "../../include/gs2m_mesh.h"
 #define GS2M_MC_CONST __constant__
 #include "tsdf_tables.h"
@@ -45,8 +43,6 @@ __constant__ int c_corner[8][3] = {{0, 0, 0}, {1, 0, 0}, {1, 1, 0}, {0, 1, 0}, {
 __constant__ int c_edge_owner[12][4] = {{0, 0, 0, 0}, {1, 0, 0, 1}, {0, 1, 0, 0}, {0, 0, 0, 1}, {0, 0, 1, 0}, {1, 0, 1, 1},
                                         {0, 1, 1, 0}, {0, 0, 1, 1}, {0, 0, 0, 2}, {1, 0, 0, 2}, {1, 1, 0, 2}, {0, 1, 0, 2}};
 
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct TouchWs {
     uint8_t* flags;     // N: 1 = touched by this view
     uint32_t* chunk;    // nchunks: touched | new << 16, then their exclusive prefixes (touched_pref, new_pref in two arrays)
@@ -59,11 +55,11 @@ TouchWs carve_touch(char* base, long long N) {
     const size_t nch = (size_t)((N + CHUNK - 1) / CHUNK);
     TouchWs w;
     size_t o = 0;
-    w.flags = (uint8_t*)(base + o); o = align_up(o + (size_t)N);
-    w.chunk = (uint32_t*)(base + o); o = align_up(o + 4 * nch);
-    w.pref_t = (uint32_t*)(base + o); o = align_up(o + 4 * nch);
-    w.pref_n = (uint32_t*)(base + o); o = align_up(o + 4 * nch);
-    w.counters = (int*)(base + o); o = align_up(o + 4 * 8);
+    w.flags = (uint8_t*)(base + o); o = gs2m_align_up(o + (size_t)N);
+    w.chunk = (uint32_t*)(base + o); o = gs2m_align_up(o + 4 * nch);
+    w.pref_t = (uint32_t*)(base + o); o = gs2m_align_up(o + 4 * nch);
+    w.pref_n = (uint32_t*)(base + o); o = gs2m_align_up(o + 4 * nch);
+    w.counters = (int*)(base + o); o = gs2m_align_up(o + 4 * 8);
     w.bytes = o;
     return w;
 }
@@ -80,12 +76,12 @@ MeshWs carve_mesh(char* base, long long n) {
     MeshWs w;
     size_t o = 0;
     const size_t nv = (size_t)n * BV;
-    w.cube = (uint16_t*)(base + o); o = align_up(o + 2 * nv);
-    w.vinfo = (uint32_t*)(base + o); o = align_up(o + 4 * nv);
-    w.slot_cnt = (uint32_t*)(base + o); o = align_up(o + 4 * (size_t)n);
-    w.pref_v = (uint32_t*)(base + o); o = align_up(o + 4 * (size_t)n);
-    w.pref_t = (uint32_t*)(base + o); o = align_up(o + 4 * (size_t)n);
-    w.totals = (unsigned long long*)(base + o); o = align_up(o + 16);
+    w.cube = (uint16_t*)(base + o); o = gs2m_align_up(o + 2 * nv);
+    w.vinfo = (uint32_t*)(base + o); o = gs2m_align_up(o + 4 * nv);
+    w.slot_cnt = (uint32_t*)(base + o); o = gs2m_align_up(o + 4 * (size_t)n);
+    w.pref_v = (uint32_t*)(base + o); o = gs2m_align_up(o + 4 * (size_t)n);
+    w.pref_t = (uint32_t*)(base + o); o = gs2m_align_up(o + 4 * (size_t)n);
+    w.totals = (unsigned long long*)(base + o); o = gs2m_align_up(o + 16);
     w.bytes = o;
     return w;
 }
@@ -93,29 +89,6 @@ MeshWs carve_mesh(char* base, long long n) {
 __device__ __forceinline__ int float_key(float f) {
     const int b = __float_as_int(f);
     return b >= 0 ? b : b ^ 0x7FFFFFFF;
-}
-
-// exclusive scan of one u32 per thread over a workgroup of 256 (4 waves); *total: the workgroup's sum
-__device__ __forceinline__ uint32_t wg_exclusive_scan(uint32_t v, uint32_t* s_w, uint32_t* total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += t;
-    }
-    if (lane == 63) s_w[w] = inc;
-    __syncthreads();
-    uint32_t off = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const uint32_t x = s_w[k];
-        off += k < w ? x : 0u;
-        tot += x;
-    }
-    __syncthreads();  // s_w may be written again by the caller's next scan
-    *total = tot;
-    return off + inc - v;
 }
 
 // the camera-space point of pixel (u, v) at depth d, in world space
@@ -210,7 +183,7 @@ __global__ void __launch_bounds__(256) chunk_count_kernel(long long N, const uin
         if (b < N && flags[b]) c += 1u | (index[b] < 0 ? 1u << 16 : 0u);
     }
     uint32_t tot;
-    wg_exclusive_scan(c, s_w, &tot);
+    gs2m_wg_exclusive_scan(c, s_w, &tot);
     if (threadIdx.x == 0) chunk[blockIdx.x] = tot;
 }
 
@@ -223,8 +196,8 @@ __global__ void __launch_bounds__(256) chunk_scan_kernel(int nchunks, const uint
         const int i = b + (int)threadIdx.x;
         const uint32_t c = i < nchunks ? chunk[i] : 0u;
         uint32_t tt, tn;
-        const uint32_t et = wg_exclusive_scan(c & 0xFFFFu, s_w, &tt);
-        const uint32_t en = wg_exclusive_scan(c >> 16, s_w, &tn);
+        const uint32_t et = gs2m_wg_exclusive_scan(c & 0xFFFFu, s_w, &tt);
+        const uint32_t en = gs2m_wg_exclusive_scan(c >> 16, s_w, &tn);
         if (i < nchunks) {
             pref_t[i] = (uint32_t)(carry_t + et);
             pref_n[i] = (uint32_t)(carry_n + en);
@@ -262,7 +235,7 @@ __global__ void __launch_bounds__(256) chunk_assign_kernel(Dom dom, long long N,
         if (f[k]) c += 1u | (idx[k] < 0 ? 1u << 16 : 0u);
     }
     uint32_t tot;
-    const uint32_t e = wg_exclusive_scan(c, s_w, &tot);
+    const uint32_t e = gs2m_wg_exclusive_scan(c, s_w, &tot);
     const bool fits = counters[3] != 0;
     uint32_t et = pref_t[blockIdx.x] + (e & 0xFFFFu), en = pref_n[blockIdx.x] + (e >> 16);
     const int base = counters[2];
@@ -414,7 +387,7 @@ __global__ void __launch_bounds__(256) mesh_count_kernel(Dom dom, const int* __r
         nt += c != 0xFFFF ? (uint32_t)ntri_of((int)c) : 0u;
     }
     uint32_t tot;
-    wg_exclusive_scan(nv | nt << 16, s_w, &tot);
+    gs2m_wg_exclusive_scan(nv | nt << 16, s_w, &tot);
     if (threadIdx.x == 0) slot_cnt[slot] = tot;
 }
 
@@ -426,8 +399,8 @@ __global__ void __launch_bounds__(256) slot_scan_kernel(int n, const uint32_t* _
         const int i = b + (int)threadIdx.x;
         const uint32_t c = i < n ? slot_cnt[i] : 0u;
         uint32_t tv, tt;
-        const uint32_t ev = wg_exclusive_scan(c & 0xFFFFu, s_w, &tv);
-        const uint32_t et = wg_exclusive_scan(c >> 16, s_w, &tt);
+        const uint32_t ev = gs2m_wg_exclusive_scan(c & 0xFFFFu, s_w, &tv);
+        const uint32_t et = gs2m_wg_exclusive_scan(c >> 16, s_w, &tt);
         if (i < n) {
             pref_v[i] = (uint32_t)(cv + ev);  // meaningful while the totals stay below 2^32 (checked on the host)
             pref_t[i] = (uint32_t)(ct + et);
@@ -454,7 +427,7 @@ __global__ void __launch_bounds__(256) emit_vertices_kernel(Dom dom, float voxel
     uint32_t nv = 0;
     for (int i = 0; i < 16; i++) nv += popc(vinfo[row + i] >> VINFO_BITS);  // the masks mesh_count_kernel stored
     uint32_t tot;
-    uint32_t id = pref_v[slot] + wg_exclusive_scan(nv, s_w, &tot);
+    uint32_t id = pref_v[slot] + gs2m_wg_exclusive_scan(nv, s_w, &tot);
     const float cyz[2] = {voxel_centre(by, j, L, voxel), voxel_centre(bz, k, L, voxel)};
     for (int i = 0; i < 16; i++) {
         const long long g0 = (long long)(row + i);
@@ -497,7 +470,7 @@ __global__ void __launch_bounds__(256) emit_triangles_kernel(Dom dom, const int*
         nt += c != 0xFFFF ? (uint32_t)ntri_of((int)c) : 0u;
     }
     uint32_t tot;
-    uint32_t t = pref_t[slot] + wg_exclusive_scan(nt, s_w, &tot);
+    uint32_t t = pref_t[slot] + gs2m_wg_exclusive_scan(nt, s_w, &tot);
     for (int i = 0; i < 16; i++) {
         const uint32_t c = cube[row + i];
         if (c == 0xFFFF) continue;
@@ -524,7 +497,6 @@ Mat34 mat34(const float* m) {
     return r;
 }
 long long dom_blocks(const Dom& d) { return (long long)d.nx * d.ny * d.nz; }
-int status(hipError_t e) { return e == hipSuccess ? GS2M_OK : GS2M_ERR_HIP; }
 
 }  // namespace
 
@@ -543,7 +515,7 @@ int gs2m_tsdf_points_aabb(int W, int H, const float* depth, float depth_trunc, f
     if (W <= 0 || H <= 0 || !depth || !c2w || !aabb) return GS2M_ERR_INVALID_ARG;
     const int n = ((W + 3) / 4) * ((H + 3) / 4);
     points_aabb_kernel<<<(n + 255) / 256, 256, 0, (hipStream_t)stream>>>(W, H, depth, depth_trunc, fx, fy, cx, cy, mat34(c2w), aabb);
-    return status(hipGetLastError());
+    return gs2m_status(hipGetLastError());
 }
 
 int gs2m_tsdf_touch(const int* dom, float voxel, float trunc, int W, int H, const float* depth, float depth_trunc, float fx,
@@ -590,7 +562,7 @@ int gs2m_tsdf_integrate(float voxel, float trunc, int W, int H, const float* dep
     integrate_kernel<<<n_touched * 16, 256, 0, (hipStream_t)stream>>>(voxel, 16.0f * voxel, trunc, W, H, depth, color, depth_trunc, fx,
                                                                       fy, cx, cy, mat34(w2c), touched_slots, block_coords, tsdf,
                                                                       weight, color_acc);
-    return status(hipGetLastError());
+    return gs2m_status(hipGetLastError());
 }
 
 int gs2m_tsdf_mesh_count(const int* dom, int n_blocks, const int* index, const int* block_coords, const float* tsdf,
@@ -630,7 +602,7 @@ int gs2m_tsdf_mesh_emit(const int* dom, float voxel, int n_blocks, const int* in
     emit_vertices_kernel<<<n_blocks, 256, 0, s>>>(d, voxel, 16.0f * voxel, index, block_coords, tsdf, color_acc, w.pref_v, w.vinfo,
                                                   vertices, vertex_colors);
     emit_triangles_kernel<<<n_blocks, 256, 0, s>>>(d, index, block_coords, w.cube, w.pref_t, w.vinfo, triangles);
-    return status(hipGetLastError());
+    return gs2m_status(hipGetLastError());
 }
 
 int gs2m_tsdf_block_coords(int n_blocks, const int* block_coords, int* host_coords, void* stream) {
@@ -639,7 +611,7 @@ int gs2m_tsdf_block_coords(int n_blocks, const int* block_coords, int* host_coor
     hipStream_t s = (hipStream_t)stream;
     if (hipMemcpyAsync(host_coords, block_coords, 3 * sizeof(int) * (size_t)n_blocks, hipMemcpyDeviceToHost, s) != hipSuccess)
         return GS2M_ERR_HIP;
-    return status(hipStreamSynchronize(s));
+    return gs2m_status(hipStreamSynchronize(s));
 }
 
 }  // extern "C"

@@ -15,9 +15,9 @@ There is no fallback: tensors must live on a HIP device and the HIP library must
 from typing import NamedTuple
 
 import ctypes as C
-import threading
-
+import functools
 import os
+import threading
 
 import torch
 import torch.nn as nn
@@ -29,21 +29,8 @@ NUM_CHANNELS = 3
 NUM_FEATURES = 10
 
 
-def _ptr(t):
-    """Device pointer or NULL for the reference's 'missing optional' encoding (an empty tensor)."""
-    if t is None or t.numel() == 0:
-        return None
-    return t.data_ptr()
-
-
-def _f32c(t, name):
-    if t is None or t.numel() == 0:
-        return t
-    if not t.is_cuda:
-        raise RuntimeError(f"gs2m rasterizer: `{name}` must be on a HIP (cuda) device; there is no CPU path")
-    if t.dtype != torch.float32:
-        raise RuntimeError(f"gs2m rasterizer: `{name}` must be float32, got {t.dtype}")
-    return t.contiguous()
+_ptr = _native.ptr
+_f32c = functools.partial(_native.f32, who="gs2m rasterizer", optional=True)  # absent optionals arrive as empty tensors
 
 
 class _Alloc:
@@ -79,10 +66,6 @@ class _Alloc:
             return self.tensor.data_ptr()
         except Exception:  # out of memory -> NULL, reported as GS2M_ERR_ALLOC
             return 0
-
-
-def _stream():
-    return _native.stream_ptr()
 
 
 class _ScratchCache(_Alloc):
@@ -233,7 +216,6 @@ class _CModule:
         coefficients (P,M-1,3), as the reference model stores them -- no concatenation needed (M = 16 only)."""
         if means3D.dim() != 2 or means3D.size(1) != 3:
             raise RuntimeError("means3D must have dimensions (num_points, 3)")  # rasterize_points.cu:52-54
-        L = _native.lib()
         means3D = _f32c(means3D, "means3D")
         device = means3D.device
         background = _f32c(background, "bg"); colors = _f32c(colors, "colors_precomp")
@@ -256,25 +238,23 @@ class _CModule:
         observe = torch.empty((P,), dtype=torch.int32, device=device)
         geom, binning, img = _Alloc.three(device)
         # the autograd path only (`_C` callers own what they get): the cached buffer of this (device, stream), if free
-        cache, lease = _BinningCache.acquire(device, _stream()) if _cached_binning else (None, None)
+        cache, lease = _BinningCache.acquire(device, _native.stream_ptr(device)) if _cached_binning else (None, None)
         pre = None
         if lease is not None and cache.tensor is not None:
             pre = _native.Prealloc(cache.tensor.data_ptr(), cache.tensor.numel(), binning.cb, None, 0, 0)
             if _CModule._prealloc_cb is None:
-                _CModule._prealloc_cb = C.cast(L.gs2m_prealloc_alloc, _native.ALLOC_FN)
+                _CModule._prealloc_cb = C.cast(_native.lib().gs2m_prealloc_alloc, _native.ALLOC_FN)
             bin_cb, bin_user = _CModule._prealloc_cb, C.byref(pre)
         else:
             bin_cb, bin_user = binning.cb, None
-        with _native.device_guard(device):
-            fwd = L.gs2m_raster_forward_split_sh if split else L.gs2m_raster_forward
-            sh_args = (_ptr(sh), _ptr(sh_rest)) if split else (_ptr(sh),)
-            rendered = fwd(
-                geom.cb, None, bin_cb, bin_user, img.cb, None, P, int(degree), int(M), _ptr(background), W, H,
-                _ptr(means3D), *sh_args, _ptr(colors), _ptr(opacities), _ptr(scales), float(scale_modifier),
-                _ptr(rotations), _ptr(cov3D_precomp), _ptr(features), _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos),
-                float(tan_fovx), float(tan_fovy), int(bool(prefiltered)), int(featureCount), _ptr(out_color),
-                _ptr(radii), _ptr(observe), _ptr(out_buffer), _stream())
-        _native.check(rendered, "gs2m_raster_forward")
+        sh_args = (_ptr(sh), _ptr(sh_rest)) if split else (_ptr(sh),)
+        rendered = _native.launch(
+            "gs2m_raster_forward_split_sh" if split else "gs2m_raster_forward", device,
+            geom.cb, None, bin_cb, bin_user, img.cb, None, P, int(degree), int(M), _ptr(background), W, H,
+            _ptr(means3D), *sh_args, _ptr(colors), _ptr(opacities), _ptr(scales), float(scale_modifier),
+            _ptr(rotations), _ptr(cov3D_precomp), _ptr(features), _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos),
+            float(tan_fovx), float(tan_fovy), int(bool(prefiltered)), int(featureCount), _ptr(out_color),
+            _ptr(radii), _ptr(observe), _ptr(out_buffer))
         if _cached_binning:
             BINNING_CACHE_STATS["calls"] += 1
             if lease is None:
@@ -305,7 +285,6 @@ class _CModule:
         those inputs were not given -- the reference's extension writes them regardless and its autograd Function drops
         them (diff_gaussian_rasterization/__init__.py:127-139); the Function below asks for this form.  `want_sh_grad=False`:
         dL/dSH is not computed either (None in the result): the caller knows the colour gradient to be identically zero."""
-        L = _native.lib()
         device = means3D.device
         means3D = _f32c(means3D, "means3D")
         P = means3D.size(0)
@@ -350,20 +329,18 @@ class _CModule:
         dL_dshs = arena.get("shs"); dL_dscales = arena["scales"]; dL_drotations = arena["rotations"]
         dL_dshs_rest = arena.get("shs_rest")
         dL_dconics = arena.get("conics")
-        scratch = _ScratchCache.get(device, _stream())
-        with _native.device_guard(device):
-            bwd = L.gs2m_raster_backward_split_sh if split else L.gs2m_raster_backward
-            sh_args = (_ptr(sh), _ptr(sh_rest)) if split else (_ptr(sh),)
-            dsh_args = (_ptr(dL_dshs), _ptr(dL_dshs_rest)) if split else (_ptr(dL_dshs),)
-            rc = bwd(
-                P, int(degree), int(M), int(R), _ptr(background), W, H, _ptr(means3D), *sh_args, _ptr(colors),
-                _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp), _ptr(features),
-                _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos), float(tan_fovx), float(tan_fovy), _ptr(radii),
-                _ptr(buffer), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), int(featureCount),
-                _ptr(grad_colors), _ptr(grad_buffer), _ptr(dL_dmeans2D), _ptr(dL_dconics), _ptr(dL_dopacities),
-                _ptr(dL_dcolors), _ptr(dL_dmeans3D), _ptr(dL_dcov3D), *dsh_args, _ptr(dL_dscales),
-                _ptr(dL_drotations), _ptr(dL_dfeatures), scratch.cb, None, _stream())
-        _native.check(rc, "gs2m_raster_backward")
+        scratch = _ScratchCache.get(device, _native.stream_ptr(device))
+        sh_args = (_ptr(sh), _ptr(sh_rest)) if split else (_ptr(sh),)
+        dsh_args = (_ptr(dL_dshs), _ptr(dL_dshs_rest)) if split else (_ptr(dL_dshs),)
+        _native.launch(
+            "gs2m_raster_backward_split_sh" if split else "gs2m_raster_backward", device,
+            P, int(degree), int(M), int(R), _ptr(background), W, H, _ptr(means3D), *sh_args, _ptr(colors),
+            _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp), _ptr(features),
+            _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos), float(tan_fovx), float(tan_fovy), _ptr(radii),
+            _ptr(buffer), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), int(featureCount),
+            _ptr(grad_colors), _ptr(grad_buffer), _ptr(dL_dmeans2D), _ptr(dL_dconics), _ptr(dL_dopacities),
+            _ptr(dL_dcolors), _ptr(dL_dmeans3D), _ptr(dL_dcov3D), *dsh_args, _ptr(dL_dscales),
+            _ptr(dL_drotations), _ptr(dL_dfeatures), scratch.cb, None)
         out = (dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dmeans3D, dL_dcov3D, dL_dshs, dL_dscales, dL_drotations,
                dL_dfeatures)
         if split:
@@ -372,15 +349,12 @@ class _CModule:
 
     @staticmethod
     def mark_visible(means3D, viewmatrix, projmatrix):
-        L = _native.lib()
         means3D = _f32c(means3D, "means3D")
         P = means3D.size(0)
         present = torch.zeros((P,), dtype=torch.bool, device=means3D.device)
         if P != 0:
-            with _native.device_guard(means3D.device):
-                rc = L.gs2m_raster_mark_visible(P, _ptr(means3D), _ptr(_f32c(viewmatrix, "viewmatrix")),
-                                                _ptr(_f32c(projmatrix, "projmatrix")), present.data_ptr(), _stream())
-            _native.check(rc, "gs2m_raster_mark_visible")
+            _native.launch("gs2m_raster_mark_visible", means3D.device, P, _ptr(means3D), _ptr(_f32c(viewmatrix, "viewmatrix")),
+                           _ptr(_f32c(projmatrix, "projmatrix")), present.data_ptr())
         return present
 
 

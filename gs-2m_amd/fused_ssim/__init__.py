@@ -6,8 +6,6 @@ gradient for `img1` only; `FusedSSIMMap` is the autograd Function; `fusedssim` /
 extension entry points (`fused_ssim_cuda` in the reference).  The kernels are hand-written HIP behind the C ABI of
 include/gs2m_ssim.h (csrc/ssim.hip).  There is no CPU path.
 """
-import ctypes as C
-
 import torch
 
 import gs2m_native as _native
@@ -15,25 +13,24 @@ import gs2m_native as _native
 allowed_padding = ["same", "valid"]
 
 
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
+_ptr = _native.ptr
 
 
-def _check(t, name, like=None):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"fused_ssim: {name} must be a CUDA tensor (the op is a HIP kernel; there is no CPU path)")
-    if t.dtype != torch.float32 or t.dim() != 4:
+def _image(t, name, like=None):
+    """`t` as a contiguous float32 (B, CH, H, W) tensor on a HIP device -- of img1's shape and device when `like` is given"""
+    t = _native.f32(t, name, None if like is None else like.shape, who="fused_ssim")
+    if t.dim() != 4:
         raise RuntimeError(f"fused_ssim: {name} must be a float32 (B, CH, H, W) tensor")
-    if like is not None and (t.shape != like.shape or t.device != like.device):
-        raise RuntimeError(f"fused_ssim: {name} must have the shape and device of img1")
-    return t.contiguous()
+    if like is not None and t.device != like.device:
+        raise RuntimeError(f"fused_ssim: {name} must be on the device of img1")
+    return t
 
 
 def fusedssim(C1, C2, img1, img2, train):
     """-> (ssim_map, dm_dmu1, dm_dsigma1_sq, dm_dsigma12); the last three are empty tensors when train is False
     (submodules/fused-ssim/ssim.h:7-14)."""
-    img1 = _check(img1, "img1")
-    img2 = _check(img2, "img2", img1)
+    img1 = _image(img1, "img1")
+    img2 = _image(img2, "img2", img1)
     B, CH, H, W = img1.shape
     ssim_map = torch.empty_like(img1)
     if train:
@@ -41,26 +38,21 @@ def fusedssim(C1, C2, img1, img2, train):
         dm = (d[0], d[1], d[2])
     else:
         dm = tuple(torch.empty(0, dtype=torch.float32, device=img1.device) for _ in range(3))
-    with _native.device_guard(img1.device):
-        _native.check(_native.lib().gs2m_ssim_forward(
-            B, CH, H, W, float(C1), float(C2), _ptr(img1), _ptr(img2), _ptr(ssim_map),
-            *( [_ptr(t) for t in dm] if train else [None, None, None]),
-            C.c_void_p(_native.stream_ptr(img1.device))), "gs2m_ssim_forward")
+    _native.launch("gs2m_ssim_forward", img1.device, B, CH, H, W, float(C1), float(C2), _ptr(img1), _ptr(img2), _ptr(ssim_map),
+                   *[_ptr(t) for t in dm])  # not train: empty tensors, NULL
     return (ssim_map,) + dm
 
 
 def fusedssim_backward(C1, C2, img1, img2, dL_dmap, dm_dmu1, dm_dsigma1_sq, dm_dsigma12):
     """-> dL/dimg1 (submodules/fused-ssim/ssim.h:16-26)."""
-    img1 = _check(img1, "img1")
-    img2 = _check(img2, "img2", img1)
-    dL_dmap = _check(dL_dmap, "dL_dmap", img1)
-    maps = [_check(t, n, img1) for t, n in ((dm_dmu1, "dm_dmu1"), (dm_dsigma1_sq, "dm_dsigma1_sq"), (dm_dsigma12, "dm_dsigma12"))]
+    img1 = _image(img1, "img1")
+    img2 = _image(img2, "img2", img1)
+    dL_dmap = _image(dL_dmap, "dL_dmap", img1)
+    maps = [_image(t, n, img1) for t, n in ((dm_dmu1, "dm_dmu1"), (dm_dsigma1_sq, "dm_dsigma1_sq"), (dm_dsigma12, "dm_dsigma12"))]
     B, CH, H, W = img1.shape
     grad = torch.empty_like(img1)
-    with _native.device_guard(img1.device):
-        _native.check(_native.lib().gs2m_ssim_backward(
-            B, CH, H, W, _ptr(img1), _ptr(img2), _ptr(dL_dmap), _ptr(maps[0]), _ptr(maps[1]), _ptr(maps[2]), _ptr(grad),
-            C.c_void_p(_native.stream_ptr(img1.device))), "gs2m_ssim_backward")
+    _native.launch("gs2m_ssim_backward", img1.device, B, CH, H, W, _ptr(img1), _ptr(img2), _ptr(dL_dmap), _ptr(maps[0]), _ptr(maps[1]), _ptr(maps[2]),
+                   _ptr(grad))
     return grad
 
 
@@ -97,10 +89,8 @@ class _FusedSSIMAffineMean(torch.autograd.Function):
         import gs2m_losses
         ssim_map, dm_dmu1, dm_dsigma1_sq, dm_dsigma12 = fusedssim(C1, C2, img1, img2, True)
         out = torch.empty(1, dtype=torch.float32, device=img1.device)
-        with _native.device_guard(img1.device):
-            _native.check(_native.lib().gs2m_affine_mean(ssim_map.numel(), _ptr(ssim_map), float(a), float(b), _ptr(out),
-                                                         _ptr(gs2m_losses._workspace(img1.device)),
-                                                         C.c_void_p(_native.stream_ptr(img1.device))), "gs2m_affine_mean")
+        _native.launch("gs2m_affine_mean", img1.device, ssim_map.numel(), _ptr(ssim_map), float(a), float(b), _ptr(out),
+                       _ptr(gs2m_losses._workspace(img1.device)))
         ctx.save_for_backward(img1.detach().contiguous(), img2.contiguous(), dm_dmu1, dm_dsigma1_sq, dm_dsigma12)
         ctx.b = float(b)
         return out[0]
@@ -110,10 +100,8 @@ class _FusedSSIMAffineMean(torch.autograd.Function):
         img1, img2, dm_dmu1, dm_dsigma1_sq, dm_dsigma12 = ctx.saved_tensors
         B, CH, H, W = img1.shape
         grad = torch.empty_like(img1)
-        with _native.device_guard(img1.device):
-            _native.check(_native.lib().gs2m_ssim_backward_uniform(
-                B, CH, H, W, _ptr(img1), _ptr(img2), _ptr(g.contiguous()), ctx.b, float(img1.numel()), _ptr(dm_dmu1), _ptr(dm_dsigma1_sq),
-                _ptr(dm_dsigma12), _ptr(grad), C.c_void_p(_native.stream_ptr(img1.device))), "gs2m_ssim_backward_uniform")
+        _native.launch("gs2m_ssim_backward_uniform", img1.device, B, CH, H, W, _ptr(img1), _ptr(img2), _ptr(g.contiguous()), ctx.b,
+                       float(img1.numel()), _ptr(dm_dmu1), _ptr(dm_dsigma1_sq), _ptr(dm_dsigma12), _ptr(grad))
         return None, None, grad, None, None, None
 
 
@@ -122,11 +110,11 @@ def fused_ssim(img1, img2, padding="same", train=True):
     C2 = 0.03 ** 2
     assert padding in allowed_padding
     if padding == "same" and train and torch.is_grad_enabled() and isinstance(img1, torch.Tensor) and img1.requires_grad:
-        return _FusedSSIMAffineMean.apply(C1, C2, _check(img1, "img1"), _check(img2, "img2", img1), 0.0, 1.0)
+        return _FusedSSIMAffineMean.apply(C1, C2, _image(img1, "img1"), _image(img2, "img2", img1), 0.0, 1.0)
     return FusedSSIMMap.apply(C1, C2, img1, img2, padding, train).mean()
 
 
 def dssim_loss(img1, img2, weight=1.0):
     """The D-SSIM term of train.py:103 / :136, weight * (1 - fused_ssim(img1, img2)), as one autograd node (no scalar
     arithmetic kernels around the mean, no materialised map gradient)."""
-    return _FusedSSIMAffineMean.apply(0.01 ** 2, 0.03 ** 2, _check(img1, "img1"), _check(img2, "img2", img1), float(weight), -float(weight))
+    return _FusedSSIMAffineMean.apply(0.01 ** 2, 0.03 ** 2, _image(img1, "img1"), _image(img2, "img2", img1), float(weight), -float(weight))

@@ -27,8 +27,7 @@ import torch
 import gs2m_native as N
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr() if t is not None else 0)
+_ptr = N.ptr
 
 
 def _dev(device):
@@ -45,10 +44,6 @@ def _ws(nbytes, device):
     return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
 
 
-def _stream(device):
-    return C.c_void_p(N.stream_ptr(device))
-
-
 # ---- the steps, on device tensors ----------------------------------------------------------------------------------------
 
 def world_transform(vertices, scale_mat, device=None):
@@ -58,8 +53,7 @@ def world_transform(vertices, scale_mat, device=None):
     v = _points(vertices, dev)
     out = torch.empty_like(v)
     t = (C.c_double * 3)(*[float(x) for x in S[:3, 3]])
-    with N.device_guard(dev):
-        N.check(N.lib().gs2m_eval_transform(len(v), _ptr(v), float(S[0, 0]), t, _ptr(out), _stream(dev)), "gs2m_eval_transform")
+    N.launch("gs2m_eval_transform", dev, len(v), _ptr(v), float(S[0, 0]), t, _ptr(out))
     return out
 
 
@@ -73,19 +67,16 @@ def sample_mesh_points(vertices, triangles, thresh=0.2, device=None):
     L, nv, nt = N.lib(), len(v), len(f)
     tb = C.c_longlong()
     N.check(L.gs2m_eval_sample_workspace_bytes(nt, 0, C.byref(tb), None), "gs2m_eval_sample_workspace_bytes")
-    with N.device_guard(dev):
-        s = _stream(dev)
-        tri_ws = _ws(tb.value, dev)
-        rows = C.c_longlong()
-        N.check(L.gs2m_eval_sample_rows(nv, _ptr(v), nt, _ptr(f), float(thresh), _ptr(tri_ws), C.byref(rows), s), "gs2m_eval_sample_rows")
-        rb = C.c_longlong()
-        N.check(L.gs2m_eval_sample_workspace_bytes(nt, rows.value, None, C.byref(rb)), "gs2m_eval_sample_workspace_bytes")
-        row_ws = _ws(rb.value, dev)
-        ns = C.c_longlong()
-        N.check(L.gs2m_eval_sample_count(nt, rows.value, _ptr(tri_ws), _ptr(row_ws), C.byref(ns), s), "gs2m_eval_sample_count")
-        cloud = torch.empty((nv + ns.value, 3), dtype=torch.float64, device=dev)
-        N.check(L.gs2m_eval_sample_emit(nv, _ptr(v), nt, _ptr(f), rows.value, _ptr(tri_ws), _ptr(row_ws), ns.value, _ptr(cloud), s),
-                "gs2m_eval_sample_emit")
+    tri_ws = _ws(tb.value, dev)
+    rows = C.c_longlong()
+    N.launch("gs2m_eval_sample_rows", dev, nv, _ptr(v), nt, _ptr(f), float(thresh), _ptr(tri_ws), C.byref(rows))
+    rb = C.c_longlong()
+    N.check(L.gs2m_eval_sample_workspace_bytes(nt, rows.value, None, C.byref(rb)), "gs2m_eval_sample_workspace_bytes")
+    row_ws = _ws(rb.value, dev)
+    ns = C.c_longlong()
+    N.launch("gs2m_eval_sample_count", dev, nt, rows.value, _ptr(tri_ws), _ptr(row_ws), C.byref(ns))
+    cloud = torch.empty((nv + ns.value, 3), dtype=torch.float64, device=dev)
+    N.launch("gs2m_eval_sample_emit", dev, nv, _ptr(v), nt, _ptr(f), rows.value, _ptr(tri_ws), _ptr(row_ws), ns.value, _ptr(cloud))
     return cloud
 
 
@@ -102,21 +93,17 @@ def gather(points, order, device=None):
     if len(o) != len(p):
         raise ValueError(f"gs2m_dtu_eval: order has {len(o)} entries for {len(p)} points")
     out = torch.empty_like(p)
-    with N.device_guard(dev):
-        N.check(N.lib().gs2m_eval_gather(len(p), _ptr(p), _ptr(o), _ptr(out), _stream(dev)), "gs2m_eval_gather")
+    N.launch("gs2m_eval_gather", dev, len(p), _ptr(p), _ptr(o), _ptr(out))
     return out
 
 
 def _thin(p, radius, rank, dev):
-    L = N.lib()
     wb = C.c_longlong()
-    N.check(L.gs2m_eval_thin_workspace_bytes(len(p), C.byref(wb)), "gs2m_eval_thin_workspace_bytes")
+    N.check(N.lib().gs2m_eval_thin_workspace_bytes(len(p), C.byref(wb)), "gs2m_eval_thin_workspace_bytes")
     keep = torch.empty(len(p), dtype=torch.uint8, device=dev)
     rounds = C.c_int()
-    with N.device_guard(dev):
-        ws = _ws(wb.value, dev)
-        N.check(L.gs2m_eval_thin(len(p), _ptr(p), _ptr(rank), float(radius), _ptr(ws), _ptr(keep), C.byref(rounds), _stream(dev)),
-                "gs2m_eval_thin")
+    ws = _ws(wb.value, dev)
+    N.launch("gs2m_eval_thin", dev, len(p), _ptr(p), _ptr(rank), float(radius), _ptr(ws), _ptr(keep), C.byref(rounds))
     return keep, rounds.value
 
 
@@ -138,15 +125,12 @@ def radius_downsample(points, radius, order=None, device=None):
 
 
 def _compact(p, flags, bit, dev):
-    L = N.lib()
     wb = C.c_longlong()
-    N.check(L.gs2m_eval_scan_workspace_bytes(len(p), C.byref(wb)), "gs2m_eval_scan_workspace_bytes")
+    N.check(N.lib().gs2m_eval_scan_workspace_bytes(len(p), C.byref(wb)), "gs2m_eval_scan_workspace_bytes")
     out = torch.empty_like(p)
     cnt = C.c_longlong()
-    with N.device_guard(dev):
-        ws = _ws(wb.value, dev)
-        N.check(L.gs2m_eval_compact(len(p), _ptr(p), _ptr(flags), int(bit), _ptr(ws), _ptr(out), C.byref(cnt), _stream(dev)),
-                "gs2m_eval_compact")
+    ws = _ws(wb.value, dev)
+    N.launch("gs2m_eval_compact", dev, len(p), _ptr(p), _ptr(flags), int(bit), _ptr(ws), _ptr(out), C.byref(cnt))
     return out[:cnt.value]
 
 
@@ -167,9 +151,8 @@ def mask_flags(points, obs_mask, bb, res, patch=60.0, device=None):
     dims = (C.c_int * 3)(*[int(x) for x in np.asarray(obs_mask).shape])
     flags = torch.empty(len(p), dtype=torch.uint8, device=dev)
     dd = lambda a: (C.c_double * 3)(*[float(x) for x in a])  # noqa: E731
-    with N.device_guard(dev):
-        N.check(N.lib().gs2m_eval_filter(len(p), _ptr(p), dd(lo), dd(hi), dd(bb0), float(np.asarray(res, np.float64).reshape(-1)[0]),
-                                         _ptr(m), dims, _ptr(flags), _stream(dev)), "gs2m_eval_filter")
+    N.launch("gs2m_eval_filter", dev, len(p), _ptr(p), dd(lo), dd(hi), dd(bb0), float(np.asarray(res, np.float64).reshape(-1)[0]), _ptr(m),
+             dims, _ptr(flags))
     return flags
 
 
@@ -178,8 +161,7 @@ def above_plane(points, plane, device=None):
     p = _points(points, dev)
     P = (C.c_double * 4)(*[float(x) for x in np.asarray(plane, np.float64).reshape(-1)[:4]])
     flags = torch.empty(len(p), dtype=torch.uint8, device=dev)
-    with N.device_guard(dev):
-        N.check(N.lib().gs2m_eval_above_plane(len(p), _ptr(p), P, _ptr(flags), _stream(dev)), "gs2m_eval_above_plane")
+    N.launch("gs2m_eval_above_plane", dev, len(p), _ptr(p), P, _ptr(flags))
     return flags
 
 
@@ -197,17 +179,13 @@ def grid_cell(targets, max_dist):
 
 
 def _nearest(q, t, max_dist, cell, dev):
-    L = N.lib()
     gb, bb = C.c_longlong(), C.c_longlong()
-    N.check(L.gs2m_eval_grid_bytes(len(t), C.byref(gb), C.byref(bb)), "gs2m_eval_grid_bytes")
+    N.check(N.lib().gs2m_eval_grid_bytes(len(t), C.byref(gb), C.byref(bb)), "gs2m_eval_grid_bytes")
     dist = torch.empty(len(q), dtype=torch.float64, device=dev)
-    with N.device_guard(dev):
-        s = _stream(dev)
-        grid, bws = _ws(gb.value, dev), _ws(bb.value, dev)
-        N.check(L.gs2m_eval_grid_build(len(t), _ptr(t), float(cell), _ptr(grid), _ptr(bws), s), "gs2m_eval_grid_build")
-        del bws
-        N.check(L.gs2m_eval_nearest(len(q), _ptr(q), len(t), float(cell), _ptr(grid), float(max_dist), _ptr(dist), s),
-                "gs2m_eval_nearest")
+    grid, bws = _ws(gb.value, dev), _ws(bb.value, dev)
+    N.launch("gs2m_eval_grid_build", dev, len(t), _ptr(t), float(cell), _ptr(grid), _ptr(bws))
+    del bws
+    N.launch("gs2m_eval_nearest", dev, len(q), _ptr(q), len(t), float(cell), _ptr(grid), float(max_dist), _ptr(dist))
     return dist
 
 
@@ -222,14 +200,11 @@ def masked_mean(dist, max_dist, device=None):
     """mean of the entries < max_dist (NaN when there is none), summed in a fixed order on the device.  -> (mean, count)."""
     dev = _dev(device)
     d = torch.as_tensor(dist).to(dev, torch.float64).contiguous()
-    L = N.lib()
     wb = C.c_longlong()
-    N.check(L.gs2m_eval_scan_workspace_bytes(0, C.byref(wb)), "gs2m_eval_scan_workspace_bytes")
+    N.check(N.lib().gs2m_eval_scan_workspace_bytes(0, C.byref(wb)), "gs2m_eval_scan_workspace_bytes")
     tot, cnt = C.c_double(), C.c_longlong()
-    with N.device_guard(dev):
-        ws = _ws(wb.value, dev)
-        N.check(L.gs2m_eval_masked_mean(len(d), _ptr(d), float(max_dist), _ptr(ws), C.byref(tot), C.byref(cnt), _stream(dev)),
-                "gs2m_eval_masked_mean")
+    ws = _ws(wb.value, dev)
+    N.launch("gs2m_eval_masked_mean", dev, len(d), _ptr(d), float(max_dist), _ptr(ws), C.byref(tot), C.byref(cnt))
     return (tot.value / cnt.value if cnt.value else float("nan")), cnt.value
 
 

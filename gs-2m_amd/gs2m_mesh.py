@@ -41,8 +41,7 @@ class TriangleMesh:
                               else np.ascontiguousarray(vertex_colors, dtype=np.float32))
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
+_ptr = N.ptr
 
 
 def _host_mat(m):
@@ -121,54 +120,45 @@ class TSDFVolume:
         w2c = np.asarray(w2c.detach().cpu() if torch.is_tensor(w2c) else w2c, dtype=np.float32).reshape(4, 4)
         c2w = _host_mat(c2w_of(w2c))
         w2c_h = _host_mat(w2c)
-        L = N.lib()
         fx, fy, cx, cy = (float(np.float32(x)) for x in (fx, fy, cx, cy))
-        with N.device_guard(self.device):
-            s = N.stream_ptr(self.device)
-            info = (C.c_int * 4)()
-            while True:
-                rc = N.check(L.gs2m_tsdf_touch(self._dom, self.voxel, self.trunc, W, H, _ptr(d), self.depth_trunc, fx, fy, cx, cy,
-                                               c2w, self.capacity, _ptr(self.state), _ptr(self.index), _ptr(self.block_coords),
-                                               _ptr(self.touched), _ptr(self.touch_ws), info, C.c_void_p(s)), "gs2m_tsdf_touch")
-                if rc != POOL_FULL:
-                    break
-                self._grow(max(int(info[0]), 2 * self.capacity))  # nothing but the ignored count was written: repeat
-            self.ignored_points += int(info[3])
-            self.n_blocks = int(info[0])
-            N.check(L.gs2m_tsdf_integrate(self.voxel, self.trunc, W, H, _ptr(d), _ptr(c), self.depth_trunc, fx, fy, cx, cy, w2c_h,
-                                          int(info[1]), _ptr(self.touched), _ptr(self.block_coords), _ptr(self.tsdf),
-                                          _ptr(self.weight), _ptr(self.color), C.c_void_p(s)), "gs2m_tsdf_integrate")
+        info = (C.c_int * 4)()
+        while True:
+            rc = N.launch("gs2m_tsdf_touch", self.device, self._dom, self.voxel, self.trunc, W, H, _ptr(d), self.depth_trunc, fx, fy, cx, cy,
+                          c2w, self.capacity, _ptr(self.state), _ptr(self.index), _ptr(self.block_coords), _ptr(self.touched),
+                          _ptr(self.touch_ws), info)
+            if rc != POOL_FULL:
+                break
+            self._grow(max(int(info[0]), 2 * self.capacity))  # nothing but the ignored count was written: repeat
+        self.ignored_points += int(info[3])
+        self.n_blocks = int(info[0])
+        N.launch("gs2m_tsdf_integrate", self.device, self.voxel, self.trunc, W, H, _ptr(d), _ptr(c), self.depth_trunc, fx, fy, cx, cy, w2c_h,
+                 int(info[1]), _ptr(self.touched), _ptr(self.block_coords), _ptr(self.tsdf), _ptr(self.weight), _ptr(self.color))
         return int(info[1])
 
     def extract_triangle_mesh(self):
-        L, n = N.lib(), self.n_blocks
+        n = self.n_blocks
         if n == 0:
             return TriangleMesh()
         mb = C.c_longlong()
-        N.check(L.gs2m_tsdf_workspace_bytes(self._dom, n, None, C.byref(mb)), "gs2m_tsdf_workspace_bytes")
-        with N.device_guard(self.device):
-            s = C.c_void_p(N.stream_ptr(self.device))
-            ws = torch.empty(mb.value, dtype=torch.uint8, device=self.device)
-            tot = (C.c_longlong * 2)()
-            N.check(L.gs2m_tsdf_mesh_count(self._dom, n, _ptr(self.index), _ptr(self.block_coords), _ptr(self.tsdf),
-                                           _ptr(self.weight), _ptr(ws), tot, s), "gs2m_tsdf_mesh_count")
-            V, F = int(tot[0]), int(tot[1])
-            verts = torch.empty((max(V, 1), 3), dtype=torch.float32, device=self.device)
-            cols = torch.empty_like(verts)
-            tris = torch.empty((max(F, 1), 3), dtype=torch.int32, device=self.device)
-            N.check(L.gs2m_tsdf_mesh_emit(self._dom, self.voxel, n, _ptr(self.index), _ptr(self.block_coords), _ptr(self.tsdf),
-                                          _ptr(self.color), _ptr(ws), V, F, _ptr(verts), _ptr(cols), _ptr(tris), s),
-                    "gs2m_tsdf_mesh_emit")
-            return TriangleMesh(verts[:V].cpu().numpy(), tris[:F].cpu().numpy(), cols[:V].cpu().numpy())
+        N.check(N.lib().gs2m_tsdf_workspace_bytes(self._dom, n, None, C.byref(mb)), "gs2m_tsdf_workspace_bytes")
+        ws = torch.empty(mb.value, dtype=torch.uint8, device=self.device)
+        tot = (C.c_longlong * 2)()
+        N.launch("gs2m_tsdf_mesh_count", self.device, self._dom, n, _ptr(self.index), _ptr(self.block_coords), _ptr(self.tsdf),
+                 _ptr(self.weight), _ptr(ws), tot)
+        V, F = int(tot[0]), int(tot[1])
+        verts = torch.empty((max(V, 1), 3), dtype=torch.float32, device=self.device)
+        cols = torch.empty_like(verts)
+        tris = torch.empty((max(F, 1), 3), dtype=torch.int32, device=self.device)
+        N.launch("gs2m_tsdf_mesh_emit", self.device, self._dom, self.voxel, n, _ptr(self.index), _ptr(self.block_coords), _ptr(self.tsdf),
+                 _ptr(self.color), _ptr(ws), V, F, _ptr(verts), _ptr(cols), _ptr(tris))
+        return TriangleMesh(verts[:V].cpu().numpy(), tris[:F].cpu().numpy(), cols[:V].cpu().numpy())
 
     def state_arrays(self):
         """Tests: (block coords (n, 3) int32 -- read back through gs2m_tsdf_block_coords --, tsdf (n, 4096), weight (n, 4096),
         color (n, 3, 4096) on 0..255), slot order, numpy."""
         n = self.n_blocks
         coords = np.zeros((n, 3), np.int32)
-        with N.device_guard(self.device):
-            N.check(N.lib().gs2m_tsdf_block_coords(n, _ptr(self.block_coords), coords.ctypes.data_as(C.c_void_p),
-                                                   C.c_void_p(N.stream_ptr(self.device))), "gs2m_tsdf_block_coords")
+        N.launch("gs2m_tsdf_block_coords", self.device, n, _ptr(self.block_coords), coords.ctypes.data_as(C.c_void_p))
         return coords, self.tsdf[:n].cpu().numpy(), self.weight[:n].cpu().numpy(), self.color[:n].cpu().numpy()
 
 
@@ -244,14 +234,11 @@ def fuse_depths(tsdf_depths, views, render_dir, max_depth, voxel_size, sdf_trunc
 def _depth_aabb(depths, views, depth_trunc, dev):
     """The AABB of every view's stride-4 back-projected points (gs2m_tsdf_points_aabb), or (None, None) when there is none."""
     key = torch.tensor([2 ** 31 - 1] * 3 + [-2 ** 31] * 3, dtype=torch.int32, device=dev)
-    with N.device_guard(dev):
-        s = C.c_void_p(N.stream_ptr(dev))
-        for d, view in zip(depths, views):
-            H, W = d.shape
-            N.check(N.lib().gs2m_tsdf_points_aabb(W, H, _ptr(d), depth_trunc, float(view.Fx), float(view.Fy), float(view.Cx),
-                                                  float(view.Cy), _host_mat(c2w_of(_view_w2c(view))), _ptr(key), s),
-                    "gs2m_tsdf_points_aabb")
-        k = key.cpu().numpy().astype(np.int32)
+    for d, view in zip(depths, views):
+        H, W = d.shape
+        N.launch("gs2m_tsdf_points_aabb", dev, W, H, _ptr(d), depth_trunc, float(view.Fx), float(view.Fy), float(view.Cx), float(view.Cy),
+                 _host_mat(c2w_of(_view_w2c(view))), _ptr(key))
+    k = key.cpu().numpy().astype(np.int32)
     if k[0] > k[3]:
         return None, None
     bits = np.where(k >= 0, k, k ^ np.int32(0x7FFFFFFF)).astype(np.int32)

@@ -57,10 +57,8 @@ class _PatchNCC(torch.autograd.Function):
         ncc = torch.empty((N, 1), dtype=torch.float32, device=pixels.device)
         consts = tuple((C.c_float * len(v))(*[float(x) for x in v]) for v in (M.reshape(-1).tolist(), b.reshape(-1).tolist(), Kinv.reshape(-1).tolist()))
         ctx.args = (N, w, h, consts, float(ncc_scale), int(patch))
-        with _native.device_guard(pixels.device):
-            _native.check(_native.lib().gs2m_patch_ncc_forward(
-                N, pixels.data_ptr(), normals.data_ptr(), dists.data_ptr(), ref_gray.data_ptr(), near_gray.data_ptr(), w, h, *consts,
-                float(ncc_scale), int(patch), ncc.data_ptr(), C.c_void_p(_native.stream_ptr(pixels.device))), "gs2m_patch_ncc_forward")
+        _native.launch("gs2m_patch_ncc_forward", pixels.device, N, pixels.data_ptr(), normals.data_ptr(), dists.data_ptr(), ref_gray.data_ptr(),
+                       near_gray.data_ptr(), w, h, *consts, float(ncc_scale), int(patch), ncc.data_ptr())
         ctx.save_for_backward(pixels, normals, dists, ref_gray, near_gray)
         return ncc
 
@@ -70,11 +68,8 @@ class _PatchNCC(torch.autograd.Function):
         N, w, h, consts, ncc_scale, patch = ctx.args
         d_ncc = d_ncc.contiguous().float()
         dn, dd = torch.empty_like(normals), torch.empty_like(dists)
-        with _native.device_guard(pixels.device):
-            _native.check(_native.lib().gs2m_patch_ncc_backward(
-                N, pixels.data_ptr(), normals.data_ptr(), dists.data_ptr(), ref_gray.data_ptr(), near_gray.data_ptr(), w, h, *consts,
-                ncc_scale, patch, d_ncc.data_ptr(), dn.data_ptr(), dd.data_ptr(),
-                C.c_void_p(_native.stream_ptr(pixels.device))), "gs2m_patch_ncc_backward")
+        _native.launch("gs2m_patch_ncc_backward", pixels.device, N, pixels.data_ptr(), normals.data_ptr(), dists.data_ptr(), ref_gray.data_ptr(),
+                       near_gray.data_ptr(), w, h, *consts, ncc_scale, patch, d_ncc.data_ptr(), dn.data_ptr(), dd.data_ptr())
         return None, dn, dd, None, None, None, None, None, None, None
 
 
@@ -87,10 +82,7 @@ class _GridSampleBorder(torch.autograd.Function):
         Cc, H, W = image.shape
         N = grid.shape[0]
         out = torch.empty((N, Cc), dtype=torch.float32, device=image.device)
-        with _native.device_guard(image.device):
-            _native.check(_native.lib().gs2m_grid_sample_border_forward(N, Cc, H, W, image.data_ptr(), grid.data_ptr(), out.data_ptr(),
-                                                                        C.c_void_p(_native.stream_ptr(image.device))),
-                          "gs2m_grid_sample_border_forward")
+        _native.launch("gs2m_grid_sample_border_forward", image.device, N, Cc, H, W, image.data_ptr(), grid.data_ptr(), out.data_ptr())
         ctx.save_for_backward(image, grid)
         return out
 
@@ -101,11 +93,8 @@ class _GridSampleBorder(torch.autograd.Function):
         d_img = torch.zeros_like(image) if ctx.needs_input_grad[0] else None
         d_grid = torch.empty_like(grid) if ctx.needs_input_grad[1] else None
         d_out = d_out.contiguous().float()
-        with _native.device_guard(image.device):
-            _native.check(_native.lib().gs2m_grid_sample_border_backward(
-                grid.shape[0], Cc, H, W, image.data_ptr(), grid.data_ptr(), d_out.data_ptr(), None if d_img is None else d_img.data_ptr(),
-                None if d_grid is None else d_grid.data_ptr(), C.c_void_p(_native.stream_ptr(image.device))),
-                "gs2m_grid_sample_border_backward")
+        _native.launch("gs2m_grid_sample_border_backward", image.device, grid.shape[0], Cc, H, W, image.data_ptr(), grid.data_ptr(), d_out.data_ptr(),
+                       _native.ptr(d_img), _native.ptr(d_grid))
         return d_img, d_grid
 
 
@@ -154,11 +143,8 @@ class _MVGeo(torch.autograd.Function):
         noise = torch.empty(H * W, dtype=torch.float32, device=depth.device)
         angle = torch.empty_like(noise)
         valid = torch.empty(H * W, dtype=torch.uint8, device=depth.device)
-        with _native.device_guard(depth.device):
-            _native.check(_native.lib().gs2m_mv_geo_forward(
-                W, H, Wn, Hn, depth.data_ptr(), normal.data_ptr(), depth_n.data_ptr(), normal_n.data_ptr(), *consts, float(occlusion),
-                noise.data_ptr(), angle.data_ptr(), valid.data_ptr(), C.c_void_p(_native.stream_ptr(depth.device))),
-                "gs2m_mv_geo_forward")
+        _native.launch("gs2m_mv_geo_forward", depth.device, W, H, Wn, Hn, depth.data_ptr(), normal.data_ptr(), depth_n.data_ptr(),
+                       normal_n.data_ptr(), *consts, float(occlusion), noise.data_ptr(), angle.data_ptr(), valid.data_ptr())
         ctx.save_for_backward(depth, normal, depth_n, normal_n)
         ctx.args = (W, H, Wn, Hn, consts, float(occlusion))
         valid = valid.bool()
@@ -173,11 +159,9 @@ class _MVGeo(torch.autograd.Function):
         d_noise, d_angle = z(d_noise), z(d_angle)
         dd, dn = torch.empty_like(depth), torch.empty_like(normal)
         ddn, dnn = torch.zeros_like(depth_n), torch.zeros_like(normal_n)
-        with _native.device_guard(depth.device):
-            _native.check(_native.lib().gs2m_mv_geo_backward(
-                W, H, Wn, Hn, depth.data_ptr(), normal.data_ptr(), depth_n.data_ptr(), normal_n.data_ptr(), *consts, occlusion,
-                d_noise.data_ptr(), d_angle.data_ptr(), dd.data_ptr(), dn.data_ptr(), ddn.data_ptr(), dnn.data_ptr(),
-                C.c_void_p(_native.stream_ptr(depth.device))), "gs2m_mv_geo_backward")
+        _native.launch("gs2m_mv_geo_backward", depth.device, W, H, Wn, Hn, depth.data_ptr(), normal.data_ptr(), depth_n.data_ptr(),
+                       normal_n.data_ptr(), *consts, occlusion, d_noise.data_ptr(), d_angle.data_ptr(), dd.data_ptr(), dn.data_ptr(), ddn.data_ptr(),
+                       dnn.data_ptr())
         return dd, dn, ddn, dnn, None, None, None
 
 
@@ -200,10 +184,8 @@ class _MVGeoLoss(torch.autograd.Function):
         pixel_valid = torch.empty(noise.shape, dtype=torch.bool, device=dev)
         w_ncc = torch.empty_like(noise)
         args = (float(angle_threshold), float(decay), float(factor), float(weight))
-        with _native.device_guard(dev):
-            _native.check(_native.lib().gs2m_mv_geo_loss_forward(
-                n, noise.data_ptr(), angle.data_ptr(), valid.data_ptr(), *args, out.data_ptr(), pixel_valid.data_ptr(), w_ncc.data_ptr(),
-                gs2m_losses._workspace(dev).data_ptr(), C.c_void_p(_native.stream_ptr(dev))), "gs2m_mv_geo_loss_forward")
+        _native.launch("gs2m_mv_geo_loss_forward", dev, n, noise.data_ptr(), angle.data_ptr(), valid.data_ptr(), *args, out.data_ptr(),
+                       pixel_valid.data_ptr(), w_ncc.data_ptr(), gs2m_losses._workspace(dev).data_ptr())
         ctx.save_for_backward(noise, angle, valid, out)
         ctx.args = args
         ctx.mark_non_differentiable(pixel_valid, w_ncc)
@@ -213,10 +195,8 @@ class _MVGeoLoss(torch.autograd.Function):
     def backward(ctx, g, _gv, _gw):
         noise, angle, valid, out = ctx.saved_tensors
         d_noise, d_angle = torch.empty_like(noise), torch.empty_like(angle)
-        with _native.device_guard(noise.device):
-            _native.check(_native.lib().gs2m_mv_geo_loss_backward(
-                noise.numel(), noise.data_ptr(), angle.data_ptr(), valid.data_ptr(), *ctx.args, out.data_ptr(), g.contiguous().data_ptr(),
-                d_noise.data_ptr(), d_angle.data_ptr(), C.c_void_p(_native.stream_ptr(noise.device))), "gs2m_mv_geo_loss_backward")
+        _native.launch("gs2m_mv_geo_loss_backward", noise.device, noise.numel(), noise.data_ptr(), angle.data_ptr(), valid.data_ptr(), *ctx.args,
+                       out.data_ptr(), g.contiguous().data_ptr(), d_noise.data_ptr(), d_angle.data_ptr())
         return d_noise, d_angle, None, None, None, None, None
 
 
@@ -279,11 +259,8 @@ def patch_ncc_roughness(pixels, normals, dists, ref_cam, near_cam, ncc_scale, pa
     N = pixels.shape[0]
     out = torch.empty((3, N, 1), dtype=torch.float32, device=pixels.device)
     consts = tuple((C.c_float * len(v))(*[float(x) for x in v]) for v in (M.reshape(-1).tolist(), b.reshape(-1).tolist(), Kinv.reshape(-1).tolist()))
-    with _native.device_guard(pixels.device):
-        _native.check(_native.lib().gs2m_patch_ncc_roughness(
-            N, pixels.data_ptr(), normals.data_ptr(), dists.data_ptr(), rg.data_ptr(), ng.data_ptr(), w, h, *consts, float(ncc_scale), int(patch),
-            out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), C.c_void_p(_native.stream_ptr(pixels.device))),
-            "gs2m_patch_ncc_roughness")
+    _native.launch("gs2m_patch_ncc_roughness", pixels.device, N, pixels.data_ptr(), normals.data_ptr(), dists.data_ptr(), rg.data_ptr(),
+                   ng.data_ptr(), w, h, *consts, float(ncc_scale), int(patch), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr())
     return out[0], out[1], torch.sqrt(out[2]) < 0.01
 
 
@@ -454,10 +431,7 @@ class _MVTake(torch.autograd.Function):
         dists = torch.empty((n,), dtype=torch.float32, device=dev)
         w = torch.empty((n,), dtype=torch.float32, device=dev)
         wm = None if w_map is None else w_map.contiguous().float()
-        with _native.device_guard(dev):
-            _native.check(_native.lib().gs2m_mv_take_forward(n, idx.data_ptr(), W, H, normal_map.data_ptr(), dist_map.data_ptr(),
-                                                             None if wm is None else wm.data_ptr(), pixels.data_ptr(), normals.data_ptr(),
-                                                             dists.data_ptr(), w.data_ptr(), C.c_void_p(_native.stream_ptr(dev))), "gs2m_mv_take_forward")
+        _native.launch("gs2m_mv_take_forward", dev, n, idx.data_ptr(), W, H, normal_map.data_ptr(), dist_map.data_ptr(), _native.ptr(wm), pixels.data_ptr(), normals.data_ptr(), dists.data_ptr(), w.data_ptr())
         ctx.save_for_backward(idx)
         ctx.shapes = (normal_map.shape, dist_map.shape, W, H)
         ctx.mark_non_differentiable(pixels, w)
@@ -469,10 +443,8 @@ class _MVTake(torch.autograd.Function):
         nshape, dshape, W, H = ctx.shapes
         dev = g_normals.device
         maps = torch.zeros((4, H, W), dtype=torch.float32, device=dev)  # one fill for both maps
-        with _native.device_guard(dev):
-            _native.check(_native.lib().gs2m_mv_take_backward(idx.numel(), idx.data_ptr(), W, H, g_normals.contiguous().float().data_ptr(),
-                                                              g_dists.contiguous().float().data_ptr(), maps[:3].data_ptr(), maps[3].data_ptr(),
-                                                              C.c_void_p(_native.stream_ptr(dev))), "gs2m_mv_take_backward")
+        _native.launch("gs2m_mv_take_backward", dev, idx.numel(), idx.data_ptr(), W, H, g_normals.contiguous().float().data_ptr(),
+                       g_dists.contiguous().float().data_ptr(), maps[:3].data_ptr(), maps[3].data_ptr())
         return None, maps[:3].reshape(nshape), maps[3].reshape(dshape), None
 
 
@@ -485,9 +457,8 @@ class _NCCTail(torch.autograd.Function):
         ncc, w = ncc.contiguous().float().reshape(-1), w.contiguous().float().reshape(-1)
         dev = ncc.device
         out = torch.empty(2, dtype=torch.float32, device=dev)
-        with _native.device_guard(dev):
-            _native.check(_native.lib().gs2m_ncc_tail_forward(ncc.numel(), ncc.data_ptr(), w.data_ptr(), out.data_ptr(),
-                                                              gs2m_losses._workspace(dev).data_ptr(), C.c_void_p(_native.stream_ptr(dev))), "gs2m_ncc_tail_forward")
+        _native.launch("gs2m_ncc_tail_forward", dev, ncc.numel(), ncc.data_ptr(), w.data_ptr(), out.data_ptr(),
+                       gs2m_losses._workspace(dev).data_ptr())
         ctx.save_for_backward(ncc, w, out)
         return out[0]
 
@@ -495,9 +466,8 @@ class _NCCTail(torch.autograd.Function):
     def backward(ctx, g):
         ncc, w, out = ctx.saved_tensors
         d = torch.empty_like(ncc)
-        with _native.device_guard(ncc.device):
-            _native.check(_native.lib().gs2m_ncc_tail_backward(ncc.numel(), ncc.data_ptr(), w.data_ptr(), out.data_ptr(), g.contiguous().float().data_ptr(),
-                                                               d.data_ptr(), C.c_void_p(_native.stream_ptr(ncc.device))), "gs2m_ncc_tail_backward")
+        _native.launch("gs2m_ncc_tail_backward", ncc.device, ncc.numel(), ncc.data_ptr(), w.data_ptr(), out.data_ptr(),
+                       g.contiguous().float().data_ptr(), d.data_ptr())
         return d.reshape(-1, 1), None
 
 
@@ -542,21 +512,18 @@ def _subset_device(flat, k, rng):
         _subset_scratch[key] = sc
     idx, counts, blocks, host = sc
     s1, s2 = rng.getrandbits(63), rng.getrandbits(63)
-    with _native.device_guard(dev):
-        _native.check(_native.lib().gs2m_subset_thin(n, flat.data_ptr(), int(k), s1, idx.data_ptr(), cap, counts.data_ptr(), blocks.data_ptr(),
-                                                     C.c_void_p(_native.stream_ptr(dev))), "gs2m_subset_thin")
-        host.copy_(counts, non_blocking=True)
-        torch.cuda.current_stream(dev).synchronize()  # (the one host wait `nonzero` always had)
-        total, m = int(host[0]), int(host[1])
-        if m > cap or (m < k and total > m):
-            return None
-        if m <= k:
-            return idx[:m].clone()
-        if 4 * (m - k) > m:
-            return None
-        out = torch.empty(int(k), dtype=torch.int64, device=dev)
-        _native.check(_native.lib().gs2m_subset_remove(m, int(k), s2, idx.data_ptr(), out.data_ptr(), C.c_void_p(_native.stream_ptr(dev))),
-                      "gs2m_subset_remove")
+    _native.launch("gs2m_subset_thin", dev, n, flat.data_ptr(), int(k), s1, idx.data_ptr(), cap, counts.data_ptr(), blocks.data_ptr())
+    host.copy_(counts, non_blocking=True)
+    torch.cuda.current_stream(dev).synchronize()  # (the one host wait `nonzero` always had)
+    total, m = int(host[0]), int(host[1])
+    if m > cap or (m < k and total > m):
+        return None
+    if m <= k:
+        return idx[:m].clone()
+    if 4 * (m - k) > m:
+        return None
+    out = torch.empty(int(k), dtype=torch.int64, device=dev)
+    _native.launch("gs2m_subset_remove", dev, m, int(k), s2, idx.data_ptr(), out.data_ptr())
     return out
 
 

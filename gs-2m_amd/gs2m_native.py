@@ -14,25 +14,6 @@ LIB_PATH = os.environ.get("GS2M_LIB", os.path.join(CSRC, "libgs2m_raster.so"))  
 
 ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_size_t, C.c_void_p)
 
-EXPORTS = ("gs2m_raster_forward", "gs2m_raster_backward", "gs2m_raster_mark_visible", "gs2m_raster_forward_split_sh", "gs2m_raster_backward_split_sh", "gs2m_knn_dist2",
-           "gs2m_debug_layout", "gs2m_debug_tile_sort", "gs2m_raster_forward_token", "gs2m_raster_dense_rows", "gs2m_raster_backward_rows_hint", "gs2m_prealloc_alloc", "gs2m_set_debug", "gs2m_set_markers", "gs2m_stage_name", "gs2m_set_reference_binning", "gs2m_set_spin_wait", "gs2m_set_sort_tickets", "gs2m_set_tile_sort_policy", "gs2m_pack_features_forward", "gs2m_pack_features_backward", "gs2m_gbuffer_post_forward",
-           "gs2m_gbuffer_post_backward", "gs2m_gbuffer_maps_backward", "gs2m_sobel_normal_forward", "gs2m_sobel_normal_backward", "gs2m_activate_forward", "gs2m_activate_backward", "gs2m_texture_cube_forward", "gs2m_texture_cube_backward", "gs2m_texture_2d_clamp_forward", "gs2m_texture_2d_clamp_backward", "gs2m_diffuse_cubemap_forward", "gs2m_diffuse_cubemap_backward", "gs2m_cubemap_texel_table", "gs2m_specular_cubemap_forward", "gs2m_specular_cubemap_backward", "gs2m_specular_cubemap_normalized_forward", "gs2m_specular_cubemap_normalized_backward", "gs2m_pbr_shade_forward", "gs2m_pbr_shade_backward", "gs2m_patch_ncc_forward", "gs2m_patch_ncc_backward", "gs2m_patch_ncc_roughness", "gs2m_grid_sample_border_forward", "gs2m_grid_sample_border_backward", "gs2m_mv_geo_forward", "gs2m_mv_geo_backward", "gs2m_mvs_set_deterministic", "gs2m_mvs_get_deterministic", "gs2m_adam_step", "gs2m_ssim_forward", "gs2m_ssim_backward", "gs2m_profile_mode", "gs2m_profile_sampling", "gs2m_profile_collect", "gs2m_version",
-           # include/gs2m_loss.h (round 3: the loss tail of the training iteration)
-           "gs2m_affine_mean", "gs2m_densification_stats", "gs2m_edge_gradient", "gs2m_image_loss_backward", "gs2m_image_loss_forward", "gs2m_loss_workspace_bytes", "gs2m_mv_geo_loss_backward", "gs2m_mv_geo_loss_forward", "gs2m_mv_take_backward", "gs2m_mv_take_forward", "gs2m_ncc_tail_backward", "gs2m_ncc_tail_forward", "gs2m_subset_thin", "gs2m_subset_remove", "gs2m_pbr_inputs_backward", "gs2m_pbr_inputs_forward", "gs2m_plane_loss_backward", "gs2m_plane_loss_forward", "gs2m_ssim_backward_uniform", "gs2m_tv_loss_backward", "gs2m_tv_loss_forward",
-           # include/gs2m_mesh.h (TSDF fusion and marching cubes)
-           "gs2m_tsdf_workspace_bytes", "gs2m_tsdf_points_aabb", "gs2m_tsdf_touch", "gs2m_tsdf_integrate", "gs2m_tsdf_mesh_count",
-           "gs2m_tsdf_mesh_emit", "gs2m_tsdf_block_coords",
-           # include/gs2m_eval.h (DTU mesh evaluation)
-           "gs2m_eval_transform", "gs2m_eval_sample_workspace_bytes", "gs2m_eval_sample_rows", "gs2m_eval_sample_count",
-           "gs2m_eval_sample_emit", "gs2m_eval_gather", "gs2m_eval_grid_bytes", "gs2m_eval_grid_build", "gs2m_eval_thin_workspace_bytes",
-           "gs2m_eval_thin", "gs2m_eval_filter", "gs2m_eval_above_plane", "gs2m_eval_scan_workspace_bytes", "gs2m_eval_compact",
-           "gs2m_eval_nearest", "gs2m_eval_masked_mean")
-
-STAGES = ("preprocess", "unused1", "scan", "emit", "tile_sort", "lists", "blend_fwd", "unused7", "blend_bwd",
-          "gaussian_bwd")
-
-_lib = None
-
 
 class Prealloc(C.Structure):
     """include/gs2m_raster.h: gs2m_prealloc (user block of gs2m_prealloc_alloc)"""
@@ -45,6 +26,139 @@ class Layout(C.Structure):
         "geom_bytes", "rec", "tiles_touched", "depth_key", "rect", "gauss_rows", "clamped", "wave_rowbase", "counters",
         "binning_bytes", "point_list", "tile_keys", "qlist", "qrow",
         "image_bytes", "final_T", "n_contrib", "ranges", "qcount")]
+
+
+class STREAM(C.c_void_p):
+    """`void* stream` as an entry point's LAST parameter: the function enqueues GPU work (call it through `launch`)."""
+
+
+# Every exported function: name -> (restype, argtypes), header by header in the headers' order of declaration.
+# tests/test_cabi.py compares each entry with the prototype in include/.
+p, i, f, d, ll, ull, A, s = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_longlong, C.c_ulonglong, ALLOC_FN, STREAM
+SIGNATURES = {
+    # include/gs2m_raster.h
+    "gs2m_raster_forward": (i, [A, p, A, p, A, p, i, i, i, p, i, i, p, p, p, p, p, f, p, p, p, p, p, p, f, f, i, i, p,
+                                p, p, p, s]),
+    "gs2m_raster_backward": (i, [i, i, i, i, p, i, i, p, p, p, p, f, p, p, p, p, p, p, f, f, p, p, p, p, p, i, p, p, p,
+                                 p, p, p, p, p, p, p, p, p, A, p, s]),
+    "gs2m_raster_mark_visible": (i, [i, p, p, p, p, s]),
+    "gs2m_knn_dist2": (i, [i, p, p, A, p, s]),
+    "gs2m_debug_layout": (i, [i, i, i, i, C.POINTER(Layout)]),
+    "gs2m_set_reference_binning": (i, [i]),
+    "gs2m_raster_forward_split_sh": (i, [A, p, A, p, A, p, i, i, i, p, i, i, p, p, p, p, p, p, f, p, p, p, p, p, p, f,
+                                         f, i, i, p, p, p, p, s]),
+    "gs2m_raster_backward_split_sh": (i, [i, i, i, i, p, i, i, p, p, p, p, p, f, p, p, p, p, p, p, f, f, p, p, p, p, p,
+                                          i, p, p, p, p, p, p, p, p, p, p, p, p, p, A, p, s]),
+    "gs2m_pack_features_forward": (i, [i, p, p, p, p, p, p, p, p, i, i, p, s]),
+    "gs2m_pack_features_backward": (i, [i, p, p, p, p, p, i, i, p, p, p, p, p, p, s]),
+    "gs2m_gbuffer_post_forward": (i, [i, i, p, p, p, i, p, p, p, s]),
+    "gs2m_gbuffer_post_backward": (i, [i, i, p, p, p, i, p, p, p, s]),
+    "gs2m_gbuffer_maps_backward": (i, [i, i, p, p, p, i, p, p, p, p, p, p, p, p, p, s]),
+    "gs2m_sobel_normal_forward": (i, [i, i, p, p, p, p, f, f, f, f, p, s]),
+    "gs2m_sobel_normal_backward": (i, [i, i, p, p, p, p, f, f, f, f, p, p, p, s]),
+    "gs2m_activate_forward": (i, [i, p, p, p, p, p, p, p, p, p, p, p, p, s]),
+    "gs2m_activate_backward": (i, [i, p, p, p, p, p, p, p, p, p, p, p, p, p, p, p, p, p, p, s]),
+    "gs2m_set_spin_wait": (i, [i]),
+    "gs2m_set_sort_tickets": (i, [i]),
+    "gs2m_set_tile_sort_policy": (i, [i]),
+    "gs2m_prealloc_alloc": (p, [C.c_size_t, p]),  # a ready-made ALLOC_FN: only ever cast to that type
+    "gs2m_set_debug": (i, [i]),
+    "gs2m_set_markers": (i, [i]),
+    "gs2m_stage_name": (C.c_char_p, [i]),
+    "gs2m_raster_forward_token": (ull, []),
+    "gs2m_raster_dense_rows": (ll, [ull]),
+    "gs2m_raster_backward_rows_hint": (i, [ll]),
+    "gs2m_debug_tile_sort": (i, [i, p, p, p, p, p, p, p, p, p, p, s]),
+    "gs2m_profile_mode": (i, [i]),
+    "gs2m_profile_sampling": (i, [i]),
+    "gs2m_profile_collect": (i, [C.POINTER(C.c_float), C.POINTER(C.c_int), i]),
+    "gs2m_version": (C.c_char_p, []),
+    # include/gs2m_texture.h
+    "gs2m_texture_cube_forward": (i, [i, i, i, p, p, p, p, p, s]),
+    "gs2m_texture_cube_backward": (i, [i, i, i, p, p, p, p, p, i, s]),
+    "gs2m_texture_2d_clamp_forward": (i, [i, i, i, i, p, p, p, s]),
+    "gs2m_texture_2d_clamp_backward": (i, [i, i, i, i, p, p, p, s]),
+    # include/gs2m_cubemap.h
+    "gs2m_diffuse_cubemap_forward": (i, [i, p, p, s]),
+    "gs2m_diffuse_cubemap_backward": (i, [i, p, p, s]),
+    "gs2m_cubemap_texel_table": (i, [i, p, s]),
+    "gs2m_specular_cubemap_forward": (i, [i, f, f, p, p, p, s]),
+    "gs2m_specular_cubemap_backward": (i, [i, f, f, p, p, p, s]),
+    "gs2m_specular_cubemap_normalized_forward": (i, [i, f, f, p, p, p, p, s]),
+    "gs2m_specular_cubemap_normalized_backward": (i, [i, f, f, p, p, p, p, p, s]),
+    # include/gs2m_pbr.h
+    "gs2m_pbr_shade_forward": (i, [i, p, p, p, p, p, p, i, i, p, i, i, p, p, f, f, p, p, p, p, s]),
+    "gs2m_pbr_shade_backward": (i, [i, p, p, p, p, p, p, i, i, p, i, i, p, p, f, f, p, p, p, p, p, i, s]),
+    "gs2m_pbr_inputs_forward": (i, [i, i, p, p, p, p, p, f, f, p, p, p, p, s]),
+    "gs2m_pbr_inputs_backward": (i, [i, i, p, p, p, s]),
+    # include/gs2m_mvs.h
+    "gs2m_patch_ncc_forward": (i, [i, p, p, p, p, p, i, i, p, p, p, f, i, p, s]),
+    "gs2m_patch_ncc_backward": (i, [i, p, p, p, p, p, i, i, p, p, p, f, i, p, p, p, s]),
+    "gs2m_patch_ncc_roughness": (i, [i, p, p, p, p, p, i, i, p, p, p, f, i, p, p, p, s]),
+    "gs2m_mvs_set_deterministic": (None, [i]),
+    "gs2m_mvs_get_deterministic": (i, []),
+    "gs2m_grid_sample_border_forward": (i, [i, i, i, i, p, p, p, s]),
+    "gs2m_grid_sample_border_backward": (i, [i, i, i, i, p, p, p, p, p, s]),
+    "gs2m_mv_geo_forward": (i, [i, i, i, i, p, p, p, p, p, p, p, p, p, p, f, p, p, p, s]),
+    "gs2m_mv_geo_backward": (i, [i, i, i, i, p, p, p, p, p, p, p, p, p, p, f, p, p, p, p, p, p, s]),
+    # include/gs2m_optim.h
+    "gs2m_adam_step": (i, [i, p, d, d, d, s]),
+    # include/gs2m_ssim.h
+    "gs2m_ssim_forward": (i, [i, i, i, i, f, f, p, p, p, p, p, p, s]),
+    "gs2m_ssim_backward": (i, [i, i, i, i, p, p, p, p, p, p, p, s]),
+    "gs2m_ssim_backward_uniform": (i, [i, i, i, i, p, p, p, f, f, p, p, p, p, s]),
+    # include/gs2m_loss.h
+    "gs2m_loss_workspace_bytes": (i, []),
+    "gs2m_edge_gradient": (i, [i, i, p, p, p, p, s]),
+    "gs2m_image_loss_forward": (i, [i, i, p, i, p, p, p, p, p, p, p, p, f, f, p, p, p, s]),
+    "gs2m_image_loss_backward": (i, [i, i, p, i, p, p, p, p, p, p, p, f, f, p, p, p, p, p, s]),
+    "gs2m_tv_loss_forward": (i, [i, i, i, p, p, p, i, f, p, p, s]),
+    "gs2m_tv_loss_backward": (i, [i, i, i, p, p, p, i, f, p, p, s]),
+    "gs2m_mv_geo_loss_forward": (i, [i, p, p, p, f, f, f, f, p, p, p, p, s]),
+    "gs2m_mv_geo_loss_backward": (i, [i, p, p, p, f, f, f, f, p, p, p, p, s]),
+    "gs2m_mv_take_forward": (i, [i, p, i, i, p, p, p, p, p, p, p, s]),
+    "gs2m_mv_take_backward": (i, [i, p, i, i, p, p, p, p, s]),
+    "gs2m_ncc_tail_forward": (i, [i, p, p, p, p, s]),
+    "gs2m_ncc_tail_backward": (i, [i, p, p, p, p, p, s]),
+    "gs2m_subset_thin": (i, [i, p, i, ull, p, i, p, p, s]),
+    "gs2m_subset_remove": (i, [i, i, ull, p, p, s]),
+    "gs2m_affine_mean": (i, [ll, p, f, f, p, p, s]),
+    "gs2m_plane_loss_forward": (i, [i, p, i, p, f, p, p, s]),
+    "gs2m_plane_loss_backward": (i, [i, p, i, p, f, p, p, p, s]),
+    "gs2m_densification_stats": (i, [i, p, p, p, p, p, p, p, p, s]),
+    # include/gs2m_mesh.h
+    "gs2m_tsdf_workspace_bytes": (i, [p, i, p, p]),
+    "gs2m_tsdf_points_aabb": (i, [i, i, p, f, f, f, f, f, p, p, s]),
+    "gs2m_tsdf_touch": (i, [p, f, f, i, i, p, f, f, f, f, f, p, i, p, p, p, p, p, p, s]),
+    "gs2m_tsdf_integrate": (i, [f, f, i, i, p, p, f, f, f, f, f, p, i, p, p, p, p, p, s]),
+    "gs2m_tsdf_mesh_count": (i, [p, i, p, p, p, p, p, p, s]),
+    "gs2m_tsdf_mesh_emit": (i, [p, f, i, p, p, p, p, p, ll, ll, p, p, p, s]),
+    "gs2m_tsdf_block_coords": (i, [i, p, p, s]),
+    # include/gs2m_eval.h
+    "gs2m_eval_transform": (i, [ll, p, d, p, p, s]),
+    "gs2m_eval_sample_workspace_bytes": (i, [ll, ll, p, p]),
+    "gs2m_eval_sample_rows": (i, [ll, p, ll, p, d, p, p, s]),
+    "gs2m_eval_sample_count": (i, [ll, ll, p, p, p, s]),
+    "gs2m_eval_sample_emit": (i, [ll, p, ll, p, ll, p, p, ll, p, s]),
+    "gs2m_eval_gather": (i, [ll, p, p, p, s]),
+    "gs2m_eval_grid_bytes": (i, [ll, p, p]),
+    "gs2m_eval_grid_build": (i, [ll, p, d, p, p, s]),
+    "gs2m_eval_thin_workspace_bytes": (i, [ll, p]),
+    "gs2m_eval_thin": (i, [ll, p, p, d, p, p, p, s]),
+    "gs2m_eval_filter": (i, [ll, p, p, p, p, d, p, p, p, s]),
+    "gs2m_eval_above_plane": (i, [ll, p, p, p, s]),
+    "gs2m_eval_scan_workspace_bytes": (i, [ll, p]),
+    "gs2m_eval_compact": (i, [ll, p, p, i, p, p, p, s]),
+    "gs2m_eval_nearest": (i, [ll, p, ll, d, p, d, p, s]),
+    "gs2m_eval_masked_mean": (i, [ll, p, d, p, p, p, s]),
+}
+del p, i, f, d, ll, ull, A, s
+EXPORTS = tuple(SIGNATURES)
+
+STAGES = ("preprocess", "unused1", "scan", "emit", "tile_sort", "lists", "blend_fwd", "unused7", "blend_bwd",
+          "gaussian_bwd")
+
+_lib = None
 
 
 def build(jobs=8, force=False):
@@ -65,198 +179,9 @@ def lib():
             f"gs2m: HIP extension not built: {LIB_PATH} is missing. Run `python -c 'import __graft_entry__ as g; "
             f"g.build()'` (needs hipcc, --offload-arch=gfx950). There is no CPU fallback.")
     L = C.CDLL(LIB_PATH)
-    p, i, f = C.c_void_p, C.c_int, C.c_float
-    L.gs2m_raster_forward.restype = i
-    L.gs2m_raster_forward.argtypes = [ALLOC_FN, p, ALLOC_FN, p, ALLOC_FN, p, i, i, i, p, i, i, p, p, p, p, p, f, p, p,
-                                      p, p, p, p, f, f, i, i, p, p, p, p, p]
-    L.gs2m_raster_backward.restype = i
-    L.gs2m_raster_backward.argtypes = [i, i, i, i, p, i, i, p, p, p, p, f, p, p, p, p, p, p, f, f, p, p, p, p, p, i,
-                                       p, p, p, p, p, p, p, p, p, p, p, p, ALLOC_FN, p, p]
-    L.gs2m_raster_forward_split_sh.restype = i
-    L.gs2m_raster_forward_split_sh.argtypes = [ALLOC_FN, p, ALLOC_FN, p, ALLOC_FN, p, i, i, i, p, i, i, p, p, p, p, p, p, f, p, p,
-                                               p, p, p, p, f, f, i, i, p, p, p, p, p]
-    L.gs2m_raster_backward_split_sh.restype = i
-    L.gs2m_raster_backward_split_sh.argtypes = [i, i, i, i, p, i, i, p, p, p, p, p, f, p, p, p, p, p, p, f, f, p, p, p, p, p, i,
-                                                p, p, p, p, p, p, p, p, p, p, p, p, p, ALLOC_FN, p, p]
-    L.gs2m_raster_mark_visible.restype = i
-    L.gs2m_raster_mark_visible.argtypes = [i, p, p, p, p, p]
-    L.gs2m_knn_dist2.restype = i
-    L.gs2m_knn_dist2.argtypes = [i, p, p, ALLOC_FN, p, p]
-    L.gs2m_debug_layout.restype = i
-    L.gs2m_debug_layout.argtypes = [i, i, i, i, C.POINTER(Layout)]
-    L.gs2m_raster_forward_token.restype = C.c_ulonglong
-    L.gs2m_raster_forward_token.argtypes = []
-    L.gs2m_raster_dense_rows.restype = C.c_longlong
-    L.gs2m_raster_dense_rows.argtypes = [C.c_ulonglong]
-    L.gs2m_raster_backward_rows_hint.restype = i
-    L.gs2m_raster_backward_rows_hint.argtypes = [C.c_longlong]
-    L.gs2m_debug_tile_sort.restype = i
-    L.gs2m_debug_tile_sort.argtypes = [i] + [p] * 11
-    L.gs2m_set_debug.restype = i
-    L.gs2m_set_debug.argtypes = [i]
-    L.gs2m_set_markers.restype = i
-    L.gs2m_set_markers.argtypes = [i]
-    L.gs2m_stage_name.restype = C.c_char_p
-    L.gs2m_stage_name.argtypes = [i]
-    L.gs2m_set_reference_binning.restype = i
-    L.gs2m_set_reference_binning.argtypes = [i]
-    L.gs2m_set_spin_wait.restype = i
-    L.gs2m_set_spin_wait.argtypes = [i]
-    L.gs2m_set_sort_tickets.restype = i
-    L.gs2m_set_sort_tickets.argtypes = [i]
-    L.gs2m_set_tile_sort_policy.restype = i
-    L.gs2m_set_tile_sort_policy.argtypes = [i]
-    L.gs2m_pack_features_forward.restype = i
-    L.gs2m_pack_features_forward.argtypes = [i, p, p, p, p, p, p, p, p, i, i, p, p]
-    L.gs2m_pack_features_backward.restype = i
-    L.gs2m_pack_features_backward.argtypes = [i, p, p, p, p, p, i, i, p, p, p, p, p, p, p]
-    L.gs2m_gbuffer_post_forward.restype = i
-    L.gs2m_gbuffer_post_forward.argtypes = [i, i, p, p, p, i, p, p, p, p]
-    L.gs2m_gbuffer_post_backward.restype = i
-    L.gs2m_gbuffer_post_backward.argtypes = [i, i, p, p, p, i, p, p, p, p]
-    L.gs2m_gbuffer_maps_backward.restype = i
-    L.gs2m_gbuffer_maps_backward.argtypes = [i, i, p, p, p, i, p, p, p, p, p, p, p, p, p, p]
-    L.gs2m_sobel_normal_forward.restype = i
-    L.gs2m_sobel_normal_forward.argtypes = [i, i, p, p, p, p, f, f, f, f, p, p]
-    L.gs2m_sobel_normal_backward.restype = i
-    L.gs2m_sobel_normal_backward.argtypes = [i, i, p, p, p, p, f, f, f, f, p, p, p, p]
-    L.gs2m_activate_forward.restype = i
-    L.gs2m_activate_forward.argtypes = [i] + [p] * 13
-    L.gs2m_activate_backward.restype = i
-    L.gs2m_activate_backward.argtypes = [i] + [p] * 19
-    L.gs2m_texture_cube_forward.restype = i
-    L.gs2m_texture_cube_forward.argtypes = [i, i, i, p, p, p, p, p, p]
-    L.gs2m_texture_cube_backward.restype = i
-    L.gs2m_texture_cube_backward.argtypes = [i, i, i, p, p, p, p, p, i, p]
-    L.gs2m_texture_2d_clamp_forward.restype = i
-    L.gs2m_texture_2d_clamp_forward.argtypes = [i, i, i, i, p, p, p, p]
-    L.gs2m_texture_2d_clamp_backward.restype = i
-    L.gs2m_texture_2d_clamp_backward.argtypes = [i, i, i, i, p, p, p, p]
-    L.gs2m_diffuse_cubemap_forward.restype = i
-    L.gs2m_diffuse_cubemap_forward.argtypes = [i, p, p, p]
-    L.gs2m_diffuse_cubemap_backward.restype = i
-    L.gs2m_diffuse_cubemap_backward.argtypes = [i, p, p, p]
-    L.gs2m_specular_cubemap_forward.restype = i
-    L.gs2m_cubemap_texel_table.restype = i
-    L.gs2m_cubemap_texel_table.argtypes = [i, p, p]
-    L.gs2m_specular_cubemap_forward.argtypes = [i, f, f, p, p, p, p]
-    L.gs2m_specular_cubemap_backward.restype = i
-    L.gs2m_specular_cubemap_backward.argtypes = [i, f, f, p, p, p, p]
-    L.gs2m_pbr_shade_forward.restype = i
-    L.gs2m_pbr_shade_forward.argtypes = [i, p, p, p, p, p, p, i, i, p, i, i, p, p, f, f, p, p, p, p, p]
-    L.gs2m_pbr_shade_backward.restype = i
-    L.gs2m_pbr_shade_backward.argtypes = [i, p, p, p, p, p, p, i, i, p, i, i, p, p, f, f, p, p, p, p, p, i, p]
-    L.gs2m_patch_ncc_forward.restype = i
-    L.gs2m_patch_ncc_forward.argtypes = [i, p, p, p, p, p, i, i, p, p, p, f, i, p, p]
-    L.gs2m_patch_ncc_backward.restype = i
-    L.gs2m_patch_ncc_backward.argtypes = [i, p, p, p, p, p, i, i, p, p, p, f, i, p, p, p, p]
-    L.gs2m_patch_ncc_roughness.restype = i
-    L.gs2m_patch_ncc_roughness.argtypes = [i, p, p, p, p, p, i, i, p, p, p, f, i, p, p, p, p]
-    L.gs2m_specular_cubemap_normalized_forward.restype = i
-    L.gs2m_specular_cubemap_normalized_forward.argtypes = [i, f, f, p, p, p, p, p]
-    L.gs2m_specular_cubemap_normalized_backward.restype = i
-    L.gs2m_specular_cubemap_normalized_backward.argtypes = [i, f, f, p, p, p, p, p, p]
-    L.gs2m_grid_sample_border_forward.restype = i
-    L.gs2m_grid_sample_border_forward.argtypes = [i, i, i, i, p, p, p, p]
-    L.gs2m_mvs_set_deterministic.restype = None
-    L.gs2m_mvs_set_deterministic.argtypes = [i]
-    L.gs2m_mvs_get_deterministic.restype = i
-    L.gs2m_mvs_get_deterministic.argtypes = []
-    L.gs2m_grid_sample_border_backward.restype = i
-    L.gs2m_grid_sample_border_backward.argtypes = [i, i, i, i, p, p, p, p, p, p]
-    L.gs2m_mv_geo_forward.restype = i
-    L.gs2m_mv_geo_forward.argtypes = [i, i, i, i, p, p, p, p, p, p, p, p, p, p, f, p, p, p, p]
-    L.gs2m_mv_geo_backward.restype = i
-    L.gs2m_mv_geo_backward.argtypes = [i, i, i, i, p, p, p, p, p, p, p, p, p, p, f, p, p, p, p, p, p, p]
-    L.gs2m_adam_step.restype = i
-    L.gs2m_adam_step.argtypes = [i, p, C.c_double, C.c_double, C.c_double, p]
-    L.gs2m_ssim_forward.restype = i
-    L.gs2m_ssim_forward.argtypes = [i, i, i, i, f, f, p, p, p, p, p, p, p]
-    L.gs2m_ssim_backward.restype = i
-    L.gs2m_ssim_backward.argtypes = [i, i, i, i, p, p, p, p, p, p, p, p]
-    L.gs2m_profile_mode.restype = i
-    L.gs2m_loss_workspace_bytes.argtypes = []
-    L.gs2m_loss_workspace_bytes.restype = i
-    L.gs2m_edge_gradient.argtypes = [i, i, p, p, p, p, p]
-    L.gs2m_edge_gradient.restype = i
-    L.gs2m_image_loss_forward.argtypes = [i, i, p, i, p, p, p, p, p, p, p, p, f, f, p, p, p, p]
-    L.gs2m_image_loss_forward.restype = i
-    L.gs2m_image_loss_backward.argtypes = [i, i, p, i, p, p, p, p, p, p, p, f, f, p, p, p, p, p, p]
-    L.gs2m_image_loss_backward.restype = i
-    L.gs2m_pbr_inputs_forward.argtypes = [i, i, p, p, p, p, p, f, f, p, p, p, p, p]
-    L.gs2m_pbr_inputs_forward.restype = i
-    L.gs2m_pbr_inputs_backward.argtypes = [i, i, p, p, p, p]
-    L.gs2m_pbr_inputs_backward.restype = i
-    L.gs2m_tv_loss_forward.argtypes = [i, i, i, p, p, p, i, f, p, p, p]
-    L.gs2m_tv_loss_forward.restype = i
-    L.gs2m_tv_loss_backward.argtypes = [i, i, i, p, p, p, i, f, p, p, p]
-    L.gs2m_tv_loss_backward.restype = i
-    L.gs2m_mv_geo_loss_forward.argtypes = [i, p, p, p, f, f, f, f, p, p, p, p, p]
-    L.gs2m_mv_geo_loss_forward.restype = i
-    L.gs2m_mv_geo_loss_backward.argtypes = [i, p, p, p, f, f, f, f, p, p, p, p, p]
-    L.gs2m_mv_geo_loss_backward.restype = i
-    L.gs2m_mv_take_forward.argtypes = [i, p, i, i, p, p, p, p, p, p, p, p]
-    L.gs2m_mv_take_forward.restype = i
-    L.gs2m_mv_take_backward.argtypes = [i, p, i, i, p, p, p, p, p]
-    L.gs2m_mv_take_backward.restype = i
-    L.gs2m_ncc_tail_forward.argtypes = [i, p, p, p, p, p]
-    L.gs2m_ncc_tail_forward.restype = i
-    L.gs2m_ncc_tail_backward.argtypes = [i, p, p, p, p, p, p]
-    L.gs2m_ncc_tail_backward.restype = i
-    L.gs2m_subset_thin.argtypes = [i, p, i, C.c_ulonglong, p, i, p, p, p]
-    L.gs2m_subset_thin.restype = i
-    L.gs2m_subset_remove.argtypes = [i, i, C.c_ulonglong, p, p, p]
-    L.gs2m_subset_remove.restype = i
-    L.gs2m_affine_mean.argtypes = [C.c_longlong, p, f, f, p, p, p]
-    L.gs2m_affine_mean.restype = i
-    L.gs2m_ssim_backward_uniform.argtypes = [i, i, i, i, p, p, p, f, f, p, p, p, p, p]
-    L.gs2m_ssim_backward_uniform.restype = i
-    L.gs2m_plane_loss_forward.argtypes = [i, p, i, p, f, p, p, p]
-    L.gs2m_plane_loss_forward.restype = i
-    L.gs2m_plane_loss_backward.argtypes = [i, p, i, p, f, p, p, p, p]
-    L.gs2m_plane_loss_backward.restype = i
-    L.gs2m_densification_stats.argtypes = [i, p, p, p, p, p, p, p, p, p]
-    L.gs2m_densification_stats.restype = i
-    L.gs2m_profile_mode.argtypes = [i]
-    L.gs2m_profile_sampling.restype = i
-    L.gs2m_profile_sampling.argtypes = [i]
-    L.gs2m_profile_collect.restype = i
-    L.gs2m_profile_collect.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_int), i]
-    L.gs2m_version.restype = C.c_char_p
-    ll = C.c_longlong
-    L.gs2m_tsdf_workspace_bytes.argtypes = [p, i, p, p]
-    L.gs2m_tsdf_workspace_bytes.restype = i
-    L.gs2m_tsdf_points_aabb.argtypes = [i, i, p, f, f, f, f, f, p, p, p]
-    L.gs2m_tsdf_points_aabb.restype = i
-    L.gs2m_tsdf_touch.argtypes = [p, f, f, i, i, p, f, f, f, f, f, p, i, p, p, p, p, p, p, p]
-    L.gs2m_tsdf_touch.restype = i
-    L.gs2m_tsdf_integrate.argtypes = [f, f, i, i, p, p, f, f, f, f, f, p, i, p, p, p, p, p, p]
-    L.gs2m_tsdf_integrate.restype = i
-    L.gs2m_tsdf_mesh_count.argtypes = [p, i, p, p, p, p, p, p, p]
-    L.gs2m_tsdf_mesh_count.restype = i
-    L.gs2m_tsdf_mesh_emit.argtypes = [p, f, i, p, p, p, p, p, ll, ll, p, p, p, p]
-    L.gs2m_tsdf_mesh_emit.restype = i
-    L.gs2m_tsdf_block_coords.argtypes = [i, p, p, p]
-    L.gs2m_tsdf_block_coords.restype = i
-    d = C.c_double
-    for name, args in (("gs2m_eval_transform", [ll, p, d, p, p, p]),
-                       ("gs2m_eval_sample_workspace_bytes", [ll, ll, p, p]),
-                       ("gs2m_eval_sample_rows", [ll, p, ll, p, d, p, p, p]),
-                       ("gs2m_eval_sample_count", [ll, ll, p, p, p, p]),
-                       ("gs2m_eval_sample_emit", [ll, p, ll, p, ll, p, p, ll, p, p]),
-                       ("gs2m_eval_gather", [ll, p, p, p, p]),
-                       ("gs2m_eval_grid_bytes", [ll, p, p]),
-                       ("gs2m_eval_grid_build", [ll, p, d, p, p, p]),
-                       ("gs2m_eval_thin_workspace_bytes", [ll, p]),
-                       ("gs2m_eval_thin", [ll, p, p, d, p, p, p, p]),
-                       ("gs2m_eval_filter", [ll, p, p, p, p, d, p, p, p, p]),
-                       ("gs2m_eval_above_plane", [ll, p, p, p, p]),
-                       ("gs2m_eval_scan_workspace_bytes", [ll, p]),
-                       ("gs2m_eval_compact", [ll, p, p, i, p, p, p, p]),
-                       ("gs2m_eval_nearest", [ll, p, ll, d, p, d, p, p]),
-                       ("gs2m_eval_masked_mean", [ll, p, d, p, p, p, p])):
-        getattr(L, name).argtypes = args
-        getattr(L, name).restype = i
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -302,6 +227,36 @@ def check(rc, what):
     if rc < 0:
         raise RuntimeError(f"gs2m: {what} failed: {ERRORS.get(rc, rc)}")
     return rc
+
+
+def launch(name, device, *args):
+    """Call the entry point `name` -- one whose last parameter is the stream, i.e. one that enqueues GPU work -- with `args`
+    and torch's current stream on `device`, under `device_guard(device)`; a failure is raised under that name."""
+    fn = getattr(lib(), name)
+    if fn.argtypes[-1] is not STREAM:
+        raise TypeError(f"gs2m: {name} takes no stream: call it as check(lib().{name}(...), ...)")
+    with device_guard(device):
+        return check(fn(*args, stream_ptr(device)), name)
+
+
+def ptr(t):
+    """Device address of tensor `t`; None (NULL) for None and for an empty tensor, the reference's 'missing optional'."""
+    return None if t is None or t.numel() == 0 else t.data_ptr()
+
+
+def f32(t, name, shape=None, *, who, optional=False):
+    """`t` made contiguous, after checking that it is a float32 tensor on a HIP device (of `shape`, when given); the
+    RuntimeError starts with the wrapper's name `who`.  `optional`: None and empty tensors pass through as they are."""
+    import torch
+    if optional and (t is None or t.numel() == 0):
+        return t
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"{who}: `{name}` must be a CUDA tensor on a HIP device; there is no CPU path")
+    if t.dtype != torch.float32:
+        raise RuntimeError(f"{who}: `{name}` must be float32, got {t.dtype}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise RuntimeError(f"{who}: `{name}` must have shape {tuple(shape)}, got {tuple(t.shape)}")
+    return t.contiguous()
 
 
 def set_debug(on):

@@ -11,22 +11,13 @@ Gradients flow to `tex` and to every tensor in `mip`; `uv` and `mip_level_bias` 
 detaches what feeds them, pbr/__init__.py:25-43).  HIP kernels behind include/gs2m_texture.h; no CPU path.
 """
 import ctypes as C
+import functools
 
 import torch
 
 import gs2m_native as _native
 
-
-def _f32(t, name):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"nvdiffrast(texture): `{name}` must be a CUDA tensor (HIP kernel; there is no CPU path)")
-    if t.dtype != torch.float32:
-        raise RuntimeError(f"nvdiffrast(texture): `{name}` must be float32")
-    return t.contiguous()
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+_f32 = functools.partial(_native.f32, who="nvdiffrast(texture)")
 
 
 def _arr(ptrs):
@@ -40,10 +31,9 @@ class _CubeTexture(torch.autograd.Function):
         ch = levels[0].shape[-1]
         widths = [int(l.shape[2]) for l in levels]
         out = torch.empty(uv.shape[:-1] + (ch,), dtype=torch.float32, device=uv.device)
-        with torch.cuda.device(uv.device):
-            _native.check(_native.lib().gs2m_texture_cube_forward(
-                n, ch, len(levels), _arr([l.data_ptr() for l in levels]), (C.c_int * len(levels))(*widths), uv.data_ptr(),
-                None if bias is None else bias.data_ptr(), out.data_ptr(), _stream(uv.device)), "gs2m_texture_cube_forward")
+        _native.launch("gs2m_texture_cube_forward", uv.device,
+                       n, ch, len(levels), _arr([l.data_ptr() for l in levels]), (C.c_int * len(levels))(*widths), uv.data_ptr(),
+                       _native.ptr(bias), out.data_ptr())
         ctx.save_for_backward(uv, bias)
         ctx.shapes, ctx.widths = [l.shape for l in levels], widths
         return out
@@ -53,11 +43,9 @@ class _CubeTexture(torch.autograd.Function):
         uv, bias = ctx.saved_tensors
         dy = _f32(dy, "grad")
         grads = [torch.zeros(s, dtype=torch.float32, device=uv.device) for s in ctx.shapes]
-        with torch.cuda.device(uv.device):
-            _native.check(_native.lib().gs2m_texture_cube_backward(
-                uv.numel() // 3, ctx.shapes[0][-1], len(grads), _arr([g.data_ptr() for g in grads]),
-                (C.c_int * len(grads))(*ctx.widths), uv.data_ptr(), None if bias is None else bias.data_ptr(), dy.data_ptr(),
-                int(uv.shape[-2]), _stream(uv.device)), "gs2m_texture_cube_backward")
+        _native.launch("gs2m_texture_cube_backward", uv.device,
+                       uv.numel() // 3, ctx.shapes[0][-1], len(grads), _arr([g.data_ptr() for g in grads]),
+                       (C.c_int * len(grads))(*ctx.widths), uv.data_ptr(), _native.ptr(bias), dy.data_ptr(), int(uv.shape[-2]))
         return (None, None) + tuple(grads)
 
 
@@ -66,9 +54,7 @@ class _Texture2DClamp(torch.autograd.Function):
     def forward(ctx, uv, tex):
         _, H, W, ch = tex.shape
         out = torch.empty(uv.shape[:-1] + (ch,), dtype=torch.float32, device=uv.device)
-        with torch.cuda.device(uv.device):
-            _native.check(_native.lib().gs2m_texture_2d_clamp_forward(uv.numel() // 2, ch, W, H, tex.data_ptr(), uv.data_ptr(),
-                                                                      out.data_ptr(), _stream(uv.device)), "gs2m_texture_2d_clamp_forward")
+        _native.launch("gs2m_texture_2d_clamp_forward", uv.device, uv.numel() // 2, ch, W, H, tex.data_ptr(), uv.data_ptr(), out.data_ptr())
         ctx.save_for_backward(uv)
         ctx.shape = tex.shape
         return out
@@ -79,9 +65,7 @@ class _Texture2DClamp(torch.autograd.Function):
         dy = _f32(dy, "grad")
         _, H, W, ch = ctx.shape
         g = torch.zeros(ctx.shape, dtype=torch.float32, device=uv.device)
-        with torch.cuda.device(uv.device):
-            _native.check(_native.lib().gs2m_texture_2d_clamp_backward(uv.numel() // 2, ch, W, H, g.data_ptr(), uv.data_ptr(),
-                                                                       dy.data_ptr(), _stream(uv.device)), "gs2m_texture_2d_clamp_backward")
+        _native.launch("gs2m_texture_2d_clamp_backward", uv.device, uv.numel() // 2, ch, W, H, g.data_ptr(), uv.data_ptr(), dy.data_ptr())
         return None, g
 
 

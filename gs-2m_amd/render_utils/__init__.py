@@ -3,43 +3,32 @@
 MI355X.  Same names and argument meaning; hand-written HIP behind include/gs2m_cubemap.h (csrc/cubemap.hip).  The
 backward passes are deterministic gathers; no bounds table is built (the boxes are an acceleration structure in the
 reference and do not change the result).  There is no CPU path."""
-import ctypes as C
-
 import numpy as np
 import torch
 
 import gs2m_native as _native
 
 
-def _check(t, name, ch):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"render_utils: `{name}` must be a CUDA tensor (HIP kernel; there is no CPU path)")
-    if t.dtype != torch.float32 or t.dim() != 4 or t.shape[0] != 6 or t.shape[1] != t.shape[2] or t.shape[3] != ch:
-        raise RuntimeError(f"render_utils: `{name}` must be a float32 (6, res, res, {ch}) tensor, got {tuple(t.shape)} {t.dtype}")
-    return t.contiguous()
-
-
-def _stream(dev):
-    return C.c_void_p(_native.stream_ptr(dev))
+def _cubemap(t, name, ch):
+    t = _native.f32(t, name, who="render_utils")
+    if t.dim() != 4 or t.shape[0] != 6 or t.shape[1] != t.shape[2] or t.shape[3] != ch:
+        raise RuntimeError(f"render_utils: `{name}` must be a float32 (6, res, res, {ch}) tensor, got {tuple(t.shape)}")
+    return t
 
 
 class _diffuse_cubemap_func(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cubemap):
-        cubemap = _check(cubemap, "cubemap", 3)
+        cubemap = _cubemap(cubemap, "cubemap", 3)
         out = torch.empty_like(cubemap)
-        with _native.device_guard(cubemap.device):
-            _native.check(_native.lib().gs2m_diffuse_cubemap_forward(cubemap.shape[1], cubemap.data_ptr(), out.data_ptr(),
-                                                                     _stream(cubemap.device)), "gs2m_diffuse_cubemap_forward")
+        _native.launch("gs2m_diffuse_cubemap_forward", cubemap.device, cubemap.shape[1], cubemap.data_ptr(), out.data_ptr())
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        dout = _check(dout, "grad", 3)
+        dout = _cubemap(dout, "grad", 3)
         g = torch.empty_like(dout)
-        with _native.device_guard(dout.device):
-            _native.check(_native.lib().gs2m_diffuse_cubemap_backward(dout.shape[1], dout.data_ptr(), g.data_ptr(),
-                                                                      _stream(dout.device)), "gs2m_diffuse_cubemap_backward")
+        _native.launch("gs2m_diffuse_cubemap_backward", dout.device, dout.shape[1], dout.data_ptr(), g.data_ptr())
         return g
 
 
@@ -56,8 +45,7 @@ def _texel_table(res, device):
     key = (str(device), int(res))
     if key not in _tables:
         t = torch.empty((res,), dtype=torch.float32, device=device)
-        with _native.device_guard(device):
-            _native.check(_native.lib().gs2m_cubemap_texel_table(res, t.data_ptr(), _stream(device)), "gs2m_cubemap_texel_table")
+        _native.launch("gs2m_cubemap_texel_table", device, res, t.data_ptr())
         _tables[key] = t
     return _tables[key]
 
@@ -65,23 +53,21 @@ def _texel_table(res, device):
 class _specular_cubemap(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cubemap, roughness, costheta_cutoff):
-        cubemap = _check(cubemap, "cubemap", 3)
+        cubemap = _cubemap(cubemap, "cubemap", 3)
         res = cubemap.shape[1]
         out = torch.empty((6, res, res, 4), dtype=torch.float32, device=cubemap.device)
-        with _native.device_guard(cubemap.device):
-            _native.check(_native.lib().gs2m_specular_cubemap_forward(res, float(roughness), float(costheta_cutoff), _texel_table(res, cubemap.device).data_ptr(),
-                                                                      cubemap.data_ptr(), out.data_ptr(), _stream(cubemap.device)), "gs2m_specular_cubemap_forward")
+        _native.launch("gs2m_specular_cubemap_forward", cubemap.device, res, float(roughness), float(costheta_cutoff),
+                       _texel_table(res, cubemap.device).data_ptr(), cubemap.data_ptr(), out.data_ptr())
         ctx.args = (float(roughness), float(costheta_cutoff))
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        dout = _check(dout, "grad", 4)
+        dout = _cubemap(dout, "grad", 4)
         res = dout.shape[1]
         g = torch.empty((6, res, res, 3), dtype=torch.float32, device=dout.device)
-        with _native.device_guard(dout.device):
-            _native.check(_native.lib().gs2m_specular_cubemap_backward(res, ctx.args[0], ctx.args[1], _texel_table(res, dout.device).data_ptr(), dout.data_ptr(), g.data_ptr(),
-                                                                       _stream(dout.device)), "gs2m_specular_cubemap_backward")
+        _native.launch("gs2m_specular_cubemap_backward", dout.device, res, ctx.args[0], ctx.args[1], _texel_table(res, dout.device).data_ptr(),
+                       dout.data_ptr(), g.data_ptr())
         return g, None, None
 
 
@@ -91,14 +77,12 @@ class _specular_cubemap_normalized(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, cubemap, roughness, costheta_cutoff):
-        cubemap = _check(cubemap, "cubemap", 3)
+        cubemap = _cubemap(cubemap, "cubemap", 3)
         res = cubemap.shape[1]
         raw = torch.empty((6, res, res, 4), dtype=torch.float32, device=cubemap.device)
         out = torch.empty_like(cubemap)
-        with _native.device_guard(cubemap.device):
-            _native.check(_native.lib().gs2m_specular_cubemap_normalized_forward(
-                res, float(roughness), float(costheta_cutoff), _texel_table(res, cubemap.device).data_ptr(), cubemap.data_ptr(), raw.data_ptr(),
-                out.data_ptr(), _stream(cubemap.device)), "gs2m_specular_cubemap_normalized_forward")
+        _native.launch("gs2m_specular_cubemap_normalized_forward", cubemap.device, res, float(roughness), float(costheta_cutoff),
+                       _texel_table(res, cubemap.device).data_ptr(), cubemap.data_ptr(), raw.data_ptr(), out.data_ptr())
         ctx.save_for_backward(raw)
         ctx.args = (float(roughness), float(costheta_cutoff))
         return out
@@ -106,14 +90,12 @@ class _specular_cubemap_normalized(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         (raw,) = ctx.saved_tensors
-        dout = _check(dout, "grad", 3)
+        dout = _cubemap(dout, "grad", 3)
         res = dout.shape[1]
         scratch = torch.empty_like(raw)
         g = torch.empty_like(dout)
-        with _native.device_guard(dout.device):
-            _native.check(_native.lib().gs2m_specular_cubemap_normalized_backward(
-                res, ctx.args[0], ctx.args[1], _texel_table(res, dout.device).data_ptr(), raw.data_ptr(), dout.data_ptr(), scratch.data_ptr(),
-                g.data_ptr(), _stream(dout.device)), "gs2m_specular_cubemap_normalized_backward")
+        _native.launch("gs2m_specular_cubemap_normalized_backward", dout.device, res, ctx.args[0], ctx.args[1],
+                       _texel_table(res, dout.device).data_ptr(), raw.data_ptr(), dout.data_ptr(), scratch.data_ptr(), g.data_ptr())
         return g, None, None
 
 

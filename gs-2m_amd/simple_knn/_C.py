@@ -26,8 +26,5 @@ def distCUDA2(points):
             return 0
 
     cb = _native.ALLOC_FN(_alloc)
-    with torch.cuda.device(pts.device):
-        rc = _native.lib().gs2m_knn_dist2(P, pts.data_ptr(), means.data_ptr(), cb, None,
-                                          torch.cuda.current_stream().cuda_stream)
-    _native.check(rc, "gs2m_knn_dist2")
+    _native.launch("gs2m_knn_dist2", pts.device, P, pts.data_ptr(), means.data_ptr(), cb, None)
     return means

@@ -9,15 +9,63 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _declared_functions():
-    names = []
+def _declared_prototypes():
+    """{name: (return type, [parameter, ...])} of every function include/*.h declares, comments stripped"""
+    protos = {}
     for fn in os.listdir(os.path.join(ROOT, "include")):
         if not fn.endswith(".h"):
             continue
         src = open(os.path.join(ROOT, "include", fn)).read()
         src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-        names += re.findall(r"^\s*(?:const\s+)?(?:unsigned\s+long\s+long|long\s+long|int|char\s*\*|void)\s*\*?\s*(gs2m_\w+)\s*\(", src, flags=re.M)
-    return sorted(set(names))
+        src = re.sub(r"//.*", "", src)
+        for ret, name, params in re.findall(r"^\s*((?:const\s+)?(?:unsigned\s+long\s+long|long\s+long|int|char\s*\*|void)\s*\*?)\s*(gs2m_\w+)\s*\(([^;{]*?)\)\s*;",
+                                            src, flags=re.M):
+            params = [" ".join(a.split()) for a in params.split(",")]
+            protos[name] = (" ".join(ret.split()), [] if params in (["void"], [""]) else params)
+    return protos
+
+
+def _declared_functions():
+    return sorted(_declared_prototypes())
+
+
+def _c_class(decl):
+    """A C parameter or return type as the class ctypes has to pass it as."""
+    if "*" in decl or re.search(r"\bgs2m_alloc_fn\b", decl):
+        return "pointer"
+    for c_type, cls in (("double", "double"), ("float", "float"), ("long long", "int64"), ("size_t", "int64"), ("int", "int"), ("void", "void")):
+        if re.search(r"\b" + c_type.replace(" ", r"\s+") + r"\b", decl):
+            return cls
+    raise AssertionError(f"unclassified C type: {decl!r}")
+
+
+def _ctypes_class(t):
+    import gs2m_native
+    if t is None:
+        return "void"
+    if t is gs2m_native.ALLOC_FN or t is ctypes.c_char_p or issubclass(t, (ctypes.c_void_p, ctypes._Pointer)):
+        return "pointer"
+    # ([unsigned] long long and size_t are one class: ctypes aliases the 64-bit integer types of an LP64 platform)
+    return {ctypes.c_int: "int", ctypes.c_float: "float", ctypes.c_double: "double", ctypes.c_longlong: "int64",
+            ctypes.c_ulonglong: "int64", ctypes.c_size_t: "int64"}[t]
+
+
+def test_signature_table_matches_the_headers():
+    """gs2m_native.SIGNATURES against include/*.h, entry by entry: the number of parameters, the class of each (pointer, int,
+    float, double, 64-bit integer) and of the return type; `launch` is for exactly the functions whose last
+    parameter is `void* stream`.  The table is read, the library is not loaded."""
+    import gs2m_native
+    protos = _declared_prototypes()
+    assert set(gs2m_native.SIGNATURES) == set(protos)
+    assert gs2m_native.EXPORTS == tuple(gs2m_native.SIGNATURES)
+    for name, (ret, params) in sorted(protos.items()):
+        restype, argtypes = gs2m_native.SIGNATURES[name]
+        assert _ctypes_class(restype) == _c_class(ret), f"{name}: returns {ret}"
+        assert len(argtypes) == len(params), f"{name}: {len(params)} parameters declared, {len(argtypes)} in the table"
+        for k, (a, decl) in enumerate(zip(argtypes, params)):
+            assert _ctypes_class(a) == _c_class(decl), f"{name}: parameter {k} is `{decl}`"
+            is_stream = k == len(params) - 1 and re.fullmatch(r"void\s*\*\s*stream\w*", decl) is not None
+            assert (a is gs2m_native.STREAM) == is_stream, f"{name}: parameter {k} is `{decl}`"
 
 
 def test_header_declares_the_expected_entry_points():

@@ -234,6 +234,10 @@ size_t gs2m_radix_temp_bytes(size_t n, int total_bits);
 hipError_t gs2m_radix_sort_pairs(void* temp, size_t temp_bytes, const uint32_t* kin, const uint32_t* vin, uint32_t* kA,
                                  uint32_t* vA, uint32_t* kB, uint32_t* vB, size_t n, int total_bits, bool prezeroed, hipStream_t s,
                                  uint32_t* range_raw = nullptr, const uint32_t* ext_hist = nullptr);
+// mesh_eval.hip's device-wide exclusive scan of u64 counts, in place (a: n + 1 entries, a[n] = the total; bsum:
+// gs2m_eval_scan_blocks(n) + 1 entries), shared with tnt_eval.hip
+long long gs2m_eval_scan_blocks(long long n);
+hipError_t gs2m_eval_scan_u64(unsigned long long* a, long long n, unsigned long long* bsum, hipStream_t s);
 #define GS2M_HIST_COPIES 8
 #define GS2M_HIST_COPY_WORDS 1024
 void gs2m_radix_plan(int total_bits, int* npass, int bits[4], int shift[4]);

@@ -387,14 +387,19 @@ __device__ __forceinline__ bool shell_any(int cx, int cy, int cz, int s, uint32_
     return false;
 }
 
+// IDX: also the nearest point's index in the targets' given order (sidx), ties to the lowest index; -1 where dist is +inf.
+// The distances are the same with and without: the minimum over the same candidates.
+template <bool IDX>
 __global__ void __launch_bounds__(256) nearest_kernel(long long nq, const double* __restrict__ queries, long long n, double cell,
                                                       double inv, uint32_t mask, const double* __restrict__ spts,
-                                                      const uint32_t* __restrict__ start, const uint8_t* __restrict__ occ,
-                                                      double max_dist, int fine_shells, int coarse_shells, double* __restrict__ dist) {
+                                                      const uint32_t* __restrict__ sidx, const uint32_t* __restrict__ start,
+                                                      const uint8_t* __restrict__ occ, double max_dist, int fine_shells,
+                                                      int coarse_shells, long long* __restrict__ index, double* __restrict__ dist) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= nq) return;
     const double q[3] = {queries[3 * i], queries[3 * i + 1], queries[3 * i + 2]};
     const double INF = __builtin_huge_val();
+    if (IDX) index[i] = -1;
     if (n == 0) {
         dist[i] = INF;
         return;
@@ -419,10 +424,22 @@ __global__ void __launch_bounds__(256) nearest_kernel(long long nq, const double
         if (s0 < 0) s0 = 0;
     }
     double best = INF;
+    uint32_t best_i = 0xFFFFFFFFu;
     for (int s = s0; s <= fine_shells; s++) {
         shell_any(cx, cy, cz, s, mask, [&](uint32_t b) {
             const uint32_t e = start[b + 1];
-            for (uint32_t k = start[b]; k < e; k++) best = fmin(best, dist2(spts + 3 * (size_t)k, q));
+            for (uint32_t k = start[b]; k < e; k++) {
+                const double d2 = dist2(spts + 3 * (size_t)k, q);
+                if (IDX) {
+                    // a tie lies at the same distance, so inside the shells walked before the walk may stop
+                    if (d2 < best || (d2 == best && sidx[k] < best_i)) {
+                        best = d2;
+                        best_i = sidx[k];
+                    }
+                } else {
+                    best = fmin(best, d2);
+                }
+            }
             return false;
         });
         // points beyond shell s are >= s cells away on some axis
@@ -431,6 +448,7 @@ __global__ void __launch_bounds__(256) nearest_kernel(long long nq, const double
     }
     const double d = sqrt(best);
     dist[i] = d < max_dist ? d : INF;
+    if (IDX && d < max_dist) index[i] = (long long)best_i;
 }
 
 // ---- filters, compaction, mean ----
@@ -590,7 +608,35 @@ unsigned blocks_of(long long n) { return (unsigned)((n + 255) / 256); }
 constexpr long long MAX_POINTS = 0xFFFFFFF0ll;  // sorted slots and indices are u32
 constexpr long long MAX_LAUNCH = 256ll * 0x7FFFFFFFll;
 
+int nearest(long long n_queries, const double* queries, long long n_targets, double cell, const void* grid, double max_dist,
+            long long* index, double* dist, bool with_index, void* stream) {
+    if (n_queries < 0 || n_targets < 0 || !(cell > 0.0) || !(max_dist > 0.0) || !grid || (n_queries > 0 && (!queries || !dist)))
+        return GS2M_ERR_INVALID_ARG;
+    if (n_targets > MAX_POINTS || n_queries > MAX_LAUNCH) return GS2M_ERR_UNSUPPORTED;
+    if (n_queries == 0) return GS2M_OK;
+    const Grid g = carve_grid((char*)const_cast<void*>(grid), n_targets);
+    const double fs = ceil(max_dist / cell) + 1.0;
+    if (!(fs < 1e6)) return GS2M_ERR_UNSUPPORTED;  // cell far too small for max_dist
+    const double cs = ceil(max_dist / (cell * (1 << COARSE_SHIFT))) + 1.0;
+    const int coarse = cs <= COARSE_SHELLS_MAX ? (int)cs : 0;  // 0: no coarse bound (the fine walk alone is still exact)
+    const uint32_t mask = (uint32_t)((1ll << g.bits) - 1);
+    hipStream_t s = (hipStream_t)stream;
+    if (with_index)
+        nearest_kernel<true><<<blocks_of(n_queries), 256, 0, s>>>(n_queries, queries, n_targets, cell, 1.0 / cell, mask, g.spts, g.sidx,
+                                                                  g.start, g.occ, max_dist, (int)fs, coarse, index, dist);
+    else
+        nearest_kernel<false><<<blocks_of(n_queries), 256, 0, s>>>(n_queries, queries, n_targets, cell, 1.0 / cell, mask, g.spts, g.sidx,
+                                                                   g.start, g.occ, max_dist, (int)fs, coarse, nullptr, dist);
+    return gs2m_status(hipGetLastError());
+}
+
 }  // namespace
+
+// the device-wide scan for the other evaluation unit (tnt_eval.hip; declared in common.h)
+long long gs2m_eval_scan_blocks(long long n) { return scan_blocks(n); }
+hipError_t gs2m_eval_scan_u64(unsigned long long* a, long long n, unsigned long long* bsum, hipStream_t s) {
+    return scan_u64(a, n, bsum, s);
+}
 
 extern "C" {
 
@@ -777,19 +823,13 @@ int gs2m_eval_compact(long long n, const double* pts, const unsigned char* flags
 
 int gs2m_eval_nearest(long long n_queries, const double* queries, long long n_targets, double cell, const void* grid,
                       double max_dist, double* dist, void* stream) {
-    if (n_queries < 0 || n_targets < 0 || !(cell > 0.0) || !(max_dist > 0.0) || !grid || (n_queries > 0 && (!queries || !dist)))
-        return GS2M_ERR_INVALID_ARG;
-    if (n_targets > MAX_POINTS || n_queries > MAX_LAUNCH) return GS2M_ERR_UNSUPPORTED;
-    if (n_queries == 0) return GS2M_OK;
-    const Grid g = carve_grid((char*)const_cast<void*>(grid), n_targets);
-    const double fs = ceil(max_dist / cell) + 1.0;
-    if (!(fs < 1e6)) return GS2M_ERR_UNSUPPORTED;  // cell far too small for max_dist
-    const double cs = ceil(max_dist / (cell * (1 << COARSE_SHIFT))) + 1.0;
-    const int coarse = cs <= COARSE_SHELLS_MAX ? (int)cs : 0;  // 0: no coarse bound (the fine walk alone is still exact)
-    nearest_kernel<<<blocks_of(n_queries), 256, 0, (hipStream_t)stream>>>(n_queries, queries, n_targets, cell, 1.0 / cell,
-                                                                         (uint32_t)((1ll << g.bits) - 1), g.spts, g.start, g.occ,
-                                                                         max_dist, (int)fs, coarse, dist);
-    return gs2m_status(hipGetLastError());
+    return nearest(n_queries, queries, n_targets, cell, grid, max_dist, nullptr, dist, false, stream);
+}
+
+int gs2m_eval_nearest_index(long long n_queries, const double* queries, long long n_targets, double cell, const void* grid,
+                            double max_dist, long long* index, double* dist, void* stream) {
+    if (n_queries > 0 && !index) return GS2M_ERR_INVALID_ARG;
+    return nearest(n_queries, queries, n_targets, cell, grid, max_dist, index, dist, true, stream);
 }
 
 int gs2m_eval_masked_mean(long long n, const double* dist, double max_dist, void* ws, double* host_sum, long long* host_count,

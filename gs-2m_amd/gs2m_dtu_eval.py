@@ -27,21 +27,7 @@ import torch
 import gs2m_native as N
 
 
-_ptr = N.ptr
-
-
-def _dev(device):
-    return torch.device(device if device is not None else "cuda")
-
-
-def _points(a, device):
-    """(n, 3) fp64 contiguous tensor on `device` (numpy or torch input)."""
-    t = torch.as_tensor(a)
-    return t.to(device=device, dtype=torch.float64).reshape(-1, 3).contiguous()
-
-
-def _ws(nbytes, device):
-    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
+from gs2m_eval_util import compact as _compact, device as _dev, points as _points, ptr as _ptr, workspace as _ws  # noqa: E402
 
 
 # ---- the steps, on device tensors ----------------------------------------------------------------------------------------
@@ -122,16 +108,6 @@ def radius_downsample(points, radius, order=None, device=None):
         rank = torch.as_tensor(r.astype(np.int32)).to(dev).contiguous()
     keep, _ = _thin(p, radius, rank, dev)
     return keep.cpu().numpy().astype(bool)
-
-
-def _compact(p, flags, bit, dev):
-    wb = C.c_longlong()
-    N.check(N.lib().gs2m_eval_scan_workspace_bytes(len(p), C.byref(wb)), "gs2m_eval_scan_workspace_bytes")
-    out = torch.empty_like(p)
-    cnt = C.c_longlong()
-    ws = _ws(wb.value, dev)
-    N.launch("gs2m_eval_compact", dev, len(p), _ptr(p), _ptr(flags), int(bit), _ptr(ws), _ptr(out), C.byref(cnt))
-    return out[:cnt.value]
 
 
 def mask_bounds(bb, patch):

@@ -7,7 +7,7 @@ per-voxel projective TSDF, marching cubes with shared vertices).  Fusion and ext
 memory is torch tensors owned here (the library allocates nothing).  The blocks live in a dense block-index table over a
 box fixed at creation: `fuse_depths` derives it from the depth maps (or `bounds`).
 
-    python gs-2m_amd/gs2m_mesh.py --ply point_cloud.ply -s SCENE -o OUT [--dtu]
+    python gs-2m_amd/gs2m_mesh.py --ply point_cloud.ply -s SCENE -o OUT [--dtu | --tnt [--scene NAME]]
 writes OUT/tsdf_mesh.ply, OUT/tsdf_post.ply and OUT/config.json as render.py --extract_mesh does.
 """
 import argparse
@@ -401,7 +401,11 @@ def extract_mesh(gaussians, views, cameras_extent, out_dir, max_depth=-1.0, voxe
     return mesh, post
 
 
-def main(argv=None):
+TNT_360_SCENES = ("barn", "caterpillar", "ignatius", "truck")
+
+
+def parse_args(argv=None):
+    """The command line with render.py's presets applied.  -> (namespace, bounds): bounds (3, 2) is --tnt's aabb_range, else None."""
     ap = argparse.ArgumentParser(description="TSDF mesh of a trained model (render.py --extract_mesh)")
     ap.add_argument("--ply", required=True, help="the model's point_cloud.ply")
     ap.add_argument("--source-path", "-s", required=True, help="COLMAP-format dataset (or NeRF-synthetic with --blender)")
@@ -415,10 +419,33 @@ def main(argv=None):
     ap.add_argument("--sdf_trunc", type=float, default=-1.0)
     ap.add_argument("--num_clusters", type=int, default=1)
     ap.add_argument("--dtu", action="store_true", help="render.py's DTU preset: 5.0 / 0.002 / 0.008 / 1")
+    ap.add_argument("--tnt", action="store_true",
+                    help="render.py's Tanks and Temples preset: max_depth 3.0 (barn, caterpillar, ignatius, truck) or 4.5; voxel_size "
+                         "max(aabb_range extent) / 2048 and bounds = aabb_range from the dataset's transforms.json, else 0.002; 1 cluster")
+    ap.add_argument("--scene", default="", help="--tnt: the scene's name (default: the output directory's name)")
     ap.add_argument("--sh-degree", type=int, default=3)
     a = ap.parse_args(argv)
+    if a.dtu and a.tnt:
+        ap.error("--dtu and --tnt are two presets: choose one")
+    bounds = None
     if a.dtu:
         a.max_depth, a.voxel_size, a.sdf_trunc, a.num_clusters = 5.0, 0.002, 4.0 * 0.002, 1
+    if a.tnt:
+        scene = (a.scene or os.path.basename(os.path.normpath(a.output))).lower()
+        a.max_depth, a.num_clusters, a.voxel_size = (3.0 if scene in TNT_360_SCENES else 4.5), 1, 0.002
+        tf = os.path.join(a.source_path, "transforms.json")
+        if os.path.exists(tf):
+            with open(tf) as f:
+                aabb = json.load(f).get("aabb_range")
+            if aabb is not None:
+                bounds = np.asarray(aabb, dtype=np.float64).reshape(3, 2)
+                a.voxel_size = float(np.max(bounds[:, 1] - bounds[:, 0])) / 2048
+        a.sdf_trunc = 4.0 * a.voxel_size
+    return a, bounds
+
+
+def main(argv=None):
+    a, bounds = parse_args(argv)
     import gs2m_train as T
     from gs2m_model import GaussianModel
     if a.blender:
@@ -429,7 +456,7 @@ def main(argv=None):
             cams = cams[::8]
     model = GaussianModel(a.sh_degree)
     model.load_ply(a.ply)
-    extract_mesh(model, cams, extent, a.output, a.max_depth, a.voxel_size, a.sdf_trunc, a.num_clusters)
+    extract_mesh(model, cams, extent, a.output, a.max_depth, a.voxel_size, a.sdf_trunc, a.num_clusters, bounds)
 
 
 if __name__ == "__main__":

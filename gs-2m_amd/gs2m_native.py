@@ -150,7 +150,18 @@ SIGNATURES = {
     "gs2m_eval_scan_workspace_bytes": (i, [ll, p]),
     "gs2m_eval_compact": (i, [ll, p, p, i, p, p, p, s]),
     "gs2m_eval_nearest": (i, [ll, p, ll, d, p, d, p, s]),
+    "gs2m_eval_nearest_index": (i, [ll, p, ll, d, p, d, p, p, s]),
     "gs2m_eval_masked_mean": (i, [ll, p, d, p, p, p, s]),
+    # include/gs2m_tnt.h
+    "gs2m_tnt_mesh_points": (i, [ll, p, ll, p, p, p, s]),
+    "gs2m_tnt_transform": (i, [ll, p, p, p, s]),
+    "gs2m_tnt_crop_flags": (i, [ll, p, i, d, d, i, p, p, s]),
+    "gs2m_tnt_voxel_workspace_bytes": (i, [ll, p]),
+    "gs2m_tnt_voxel_downsample": (i, [ll, p, d, p, p, p, s]),
+    "gs2m_tnt_stride_gather": (i, [ll, p, ll, p, s]),
+    "gs2m_tnt_icp_workspace_bytes": (i, [p]),
+    "gs2m_tnt_icp_moments": (i, [ll, p, ll, p, p, p, p, p, s]),
+    "gs2m_tnt_histogram": (i, [ll, p, i, p, p, s]),
 }
 del p, i, f, d, ll, ull, A, s
 EXPORTS = tuple(SIGNATURES)

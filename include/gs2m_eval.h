@@ -80,6 +80,11 @@ int gs2m_eval_compact(long long n, const double* pts, const unsigned char* flags
 int gs2m_eval_nearest(long long n_queries, const double* queries, long long n_targets, double cell, const void* grid,
                       double max_dist, double* dist, void* stream);
 
+/* gs2m_eval_nearest plus index[i]: the nearest point's index in the targets' given order (the lowest index among points at
+ * the same (dx dx + dy dy) + dz dz), -1 where dist[i] is +inf.  dist equals gs2m_eval_nearest's bit for bit. */
+int gs2m_eval_nearest_index(long long n_queries, const double* queries, long long n_targets, double cell, const void* grid,
+                            double max_dist, long long* index, double* dist, void* stream);
+
 /* The sum and count of the entries < max_dist, summed in a fixed order (HOST outputs). */
 int gs2m_eval_masked_mean(long long n, const double* dist, double max_dist, void* ws, double* host_sum, long long* host_count,
                           void* stream);

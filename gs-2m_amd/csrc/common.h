@@ -229,15 +229,12 @@ ImageState gs2m_carve_image(char* base, size_t N, size_t tiles);
 
 // hand-written onesweep radix sort of (u32 key, u32 value) pairs (radix_sort.hip).  Users: the stable sort of the emitted
 // instances by tile (api.hip: digit histogram from emit_kernel through ext_hist, tile ranges out through range_raw), distCUDA2's
-// Morton order (knn.hip) and the grid buckets of the DTU evaluation (mesh_eval.hip).
+// Morton order (knn.hip), the grid buckets of the mesh evaluations (mesh_eval.hip) and the voxel downsample's keys, low word then
+// high word (tnt_eval.hip).
 size_t gs2m_radix_temp_bytes(size_t n, int total_bits);
 hipError_t gs2m_radix_sort_pairs(void* temp, size_t temp_bytes, const uint32_t* kin, const uint32_t* vin, uint32_t* kA,
                                  uint32_t* vA, uint32_t* kB, uint32_t* vB, size_t n, int total_bits, bool prezeroed, hipStream_t s,
                                  uint32_t* range_raw = nullptr, const uint32_t* ext_hist = nullptr);
-// mesh_eval.hip's device-wide exclusive scan of u64 counts, in place (a: n + 1 entries, a[n] = the total; bsum:
-// gs2m_eval_scan_blocks(n) + 1 entries), shared with tnt_eval.hip
-long long gs2m_eval_scan_blocks(long long n);
-hipError_t gs2m_eval_scan_u64(unsigned long long* a, long long n, unsigned long long* bsum, hipStream_t s);
 #define GS2M_HIST_COPIES 8
 #define GS2M_HIST_COPY_WORDS 1024
 void gs2m_radix_plan(int total_bits, int* npass, int bits[4], int shift[4]);

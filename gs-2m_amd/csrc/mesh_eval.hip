@@ -15,19 +15,17 @@
 // max_dist; the first occupied coarse shell sets where the walk starts, or proves that nothing lies within max_dist.
 // Every sum is an integer sum or a fixed-order fp64 reduction: two runs are bitwise identical.  Compiled with -ffp-contract=off.
 #include <math.h>
-#include "common.h"
+#include "eval_common.h"
 #include "../../include/gs2m_eval.h"
 
 namespace {
 
-typedef unsigned long long u64;
 constexpr int TILE = 1024;           // scan: entries per workgroup (256 threads x 4)
-constexpr int MEAN_BLOCKS = 256;     // masked mean: partial sums
 constexpr int COARSE_SHIFT = 3;      // coarse cell = 8^3 fine cells
 constexpr int COARSE_SHELLS_MAX = 24;
 constexpr int CELL_LIMIT = 1 << 30;
 
-// ---- device-wide exclusive scan of u64 counts (in place; a[n] = total) ----
+// ---- device-wide exclusive scan of u64 counts (in place; a[n] = total): gs2m_scan_u64 of eval_common.h ----
 
 __global__ void __launch_bounds__(256) scan_reduce_kernel(long long n, const u64* __restrict__ a, u64* __restrict__ bsum) {
     __shared__ u64 s_w[4];
@@ -72,17 +70,20 @@ __global__ void __launch_bounds__(256) scan_down_kernel(long long n, u64* a, con
     }
 }
 
-long long scan_blocks(long long n) { return (n + TILE - 1) / TILE; }
+}  // namespace
 
-// a: n + 1 entries, counts in [0, n); bsum: scan_blocks(n) + 1 entries.  Exclusive prefixes in place, the total in a[n].
-hipError_t scan_u64(u64* a, long long n, u64* bsum, hipStream_t s) {
-    const long long nb = scan_blocks(n);
+long long gs2m_scan_blocks(long long n) { return (n + TILE - 1) / TILE; }
+
+hipError_t gs2m_scan_u64(u64* a, long long n, u64* bsum, hipStream_t s) {
+    const long long nb = gs2m_scan_blocks(n);
     if (nb == 0) return hipMemsetAsync(a, 0, sizeof(u64), s);
     scan_reduce_kernel<<<(unsigned)nb, 256, 0, s>>>(n, a, bsum);
     scan_blocks_kernel<<<1, 256, 0, s>>>(nb, bsum, a + n);
     scan_down_kernel<<<(unsigned)nb, 256, 0, s>>>(n, a, bsum);
     return hipGetLastError();
 }
+
+namespace {
 
 // the last index k in [0, m) with a[k] <= x (a non-decreasing, a[0] <= x)
 __device__ __forceinline__ long long last_le(const u64* __restrict__ a, long long m, u64 x) {
@@ -118,8 +119,7 @@ __global__ void __launch_bounds__(256) tri_rows_kernel(long long nv, const doubl
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= nt) return;
     const int a = tris[3 * t], b = tris[3 * t + 1], c = tris[3 * t + 2];
-    if (a < 0 || b < 0 || c < 0 || a >= nv || b >= nv || c >= nv) {
-        err[0] = 1;
+    if (!tri_in_range(a, b, c, nv, err)) {
         n12[t] = make_double2(0.0, 0.0);
         rows[t] = 0;
         return;
@@ -191,13 +191,13 @@ struct TriWs {
     size_t bytes;
 };
 TriWs carve_tri(char* base, long long nt) {
+    Carver c{base, 0};
     TriWs w;
-    size_t o = 0;
-    w.n12 = (double2*)(base + o); o = gs2m_align_up(o + 16 * (size_t)nt);
-    w.rows = (u64*)(base + o); o = gs2m_align_up(o + 8 * (size_t)(nt + 1));
-    w.bsum = (u64*)(base + o); o = gs2m_align_up(o + 8 * (size_t)(scan_blocks(nt) + 1));
-    w.err = (int*)(base + o); o = gs2m_align_up(o + 8);
-    w.bytes = o;
+    w.n12 = c.take<double2>(nt);
+    w.rows = c.take<u64>(nt + 1);
+    w.bsum = c.take<u64>(gs2m_scan_blocks(nt) + 1);
+    w.err = c.take<int>(2);
+    w.bytes = c.off;
     return w;
 }
 struct RowWs {
@@ -206,11 +206,11 @@ struct RowWs {
     size_t bytes;
 };
 RowWs carve_row(char* base, long long nr) {
+    Carver c{base, 0};
     RowWs w;
-    size_t o = 0;
-    w.cnt = (u64*)(base + o); o = gs2m_align_up(o + 8 * (size_t)(nr + 1));
-    w.bsum = (u64*)(base + o); o = gs2m_align_up(o + 8 * (size_t)(scan_blocks(nr) + 1));
-    w.bytes = o;
+    w.cnt = c.take<u64>(nr + 1);
+    w.bsum = c.take<u64>(gs2m_scan_blocks(nr) + 1);
+    w.bytes = c.off;
     return w;
 }
 
@@ -246,34 +246,32 @@ struct Grid {
     size_t bytes;
 };
 Grid carve_grid(char* base, long long n) {
+    Carver c{base, 0};
     Grid g;
     g.bits = grid_bits(n);
     const size_t nb = (size_t)1 << g.bits;
-    size_t o = 0;
-    g.spts = (double*)(base + o); o = gs2m_align_up(o + 24 * (size_t)n);
-    g.sidx = (uint32_t*)(base + o); o = gs2m_align_up(o + 4 * (size_t)n);
-    g.start = (uint32_t*)(base + o); o = gs2m_align_up(o + 4 * (nb + 1));
-    g.occ = (uint8_t*)(base + o); o = gs2m_align_up(o + nb);
-    g.bytes = o;
+    g.spts = c.take<double>(3 * (size_t)n);
+    g.sidx = c.take<uint32_t>(n);
+    g.start = c.take<uint32_t>(nb + 1);
+    g.occ = c.take<uint8_t>(nb);
+    g.bytes = c.off;
     return g;
 }
 struct BuildWs {
-    uint32_t *keys, *kA, *vA, *kB, *vB;
+    uint32_t* keys;  // max(n, 1), as the sort's arrays
+    SortBufs sort;
     void* temp;
     size_t temp_bytes, bytes;
 };
 BuildWs carve_build(char* base, long long n, int bits) {
+    Carver c{base, 0};
     BuildWs w;
-    size_t o = 0;
-    uint32_t** arrs[5] = {&w.keys, &w.kA, &w.vA, &w.kB, &w.vB};
-    for (auto a : arrs) {
-        *a = (uint32_t*)(base + o);
-        o = gs2m_align_up(o + 4 * (size_t)(n > 0 ? n : 1));
-    }
-    w.temp = base + o;
-    w.temp_bytes = gs2m_radix_temp_bytes((size_t)(n > 0 ? n : 1), bits);
-    o = gs2m_align_up(o + w.temp_bytes);
-    w.bytes = o;
+    const size_t m = (size_t)(n > 0 ? n : 1);
+    w.keys = c.take<uint32_t>(m);
+    w.sort = take_sort_bufs(c, m);
+    w.temp_bytes = gs2m_radix_temp_bytes(m, bits);
+    w.temp = c.take<char>(w.temp_bytes);
+    w.bytes = c.off;
     return w;
 }
 
@@ -310,10 +308,11 @@ hipError_t build_grid(long long n, const double* pts, double cell, const Grid& g
     if (e != hipSuccess) return e;
     if (n > 0) {
         grid_key_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(n, pts, 1.0 / cell, mask, w.keys, g.occ);
-        e = gs2m_radix_sort_pairs(w.temp, w.temp_bytes, w.keys, nullptr, w.kA, w.vA, w.kB, w.vB, (size_t)n, g.bits, false, s);
+        e = gs2m_radix_sort_pairs(w.temp, w.temp_bytes, w.keys, nullptr, w.sort.kA, w.sort.vA, w.sort.kB, w.sort.vB, (size_t)n, g.bits,
+                                  false, s);
         if (e != hipSuccess) return e;
     }
-    grid_place_kernel<<<(unsigned)((n + 1 + 255) / 256), 256, 0, s>>>(n, pts, w.kB, w.vB, nb, g.spts, g.sidx, g.start);
+    grid_place_kernel<<<(unsigned)((n + 1 + 255) / 256), 256, 0, s>>>(n, pts, w.sort.kB, w.sort.vB, nb, g.spts, g.sidx, g.start);
     return hipGetLastError();
 }
 
@@ -453,10 +452,6 @@ __global__ void __launch_bounds__(256) nearest_kernel(long long nq, const double
 
 // ---- filters, compaction, mean ----
 
-struct V3 {
-    double v[3];
-};
-
 __global__ void __launch_bounds__(256) filter_kernel(long long n, const double* __restrict__ pts, V3 lo, V3 hi, V3 bb0, double res,
                                                      const unsigned char* __restrict__ mask, int X, int Y, int Z,
                                                      unsigned char* __restrict__ flags) {
@@ -520,66 +515,35 @@ __global__ void __launch_bounds__(256) transform_kernel(long long n, const doubl
     for (int k = 0; k < 3; k++) out[3 * i + k] = in[3 * i + k] * scale + t.v[k];
 }
 
-// fixed partition: block b sums i = b * 256 + tid + m * MEAN_BLOCKS * 256 in m order, then a fixed tree over the block
-__global__ void __launch_bounds__(256) mean_partial_kernel(long long n, const double* __restrict__ d, double max_dist,
-                                                           double* __restrict__ psum, u64* __restrict__ pcnt) {
-    __shared__ double s_s[4];
-    __shared__ u64 s_c[4];
-    double acc = 0.0;
-    u64 c = 0;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+// the masked mean's term of the fixed-order reduction (eval_common.h): the distances below max_dist and their count
+struct MeanTerm {
+    const double* d;
+    double max_dist;
+    __device__ void operator()(long long i, double* acc, u64& c) const {
         const double x = d[i];
         if (x < max_dist) {
-            acc += x;
+            acc[0] += x;
             c++;
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        acc += __shfl_down(acc, o, 64);
-        c += __shfl_down(c, o, 64);
-    }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) {
-        s_s[w] = acc;
-        s_c[w] = c;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        psum[blockIdx.x] = (s_s[0] + s_s[1]) + (s_s[2] + s_s[3]);
-        pcnt[blockIdx.x] = (s_c[0] + s_c[1]) + (s_c[2] + s_c[3]);
-    }
-}
-
-__global__ void __launch_bounds__(64) mean_final_kernel(int nb, const double* __restrict__ psum, const u64* __restrict__ pcnt,
-                                                        double* __restrict__ out_sum, u64* __restrict__ out_cnt) {
-    if (threadIdx.x != 0) return;
-    double s = 0.0;
-    u64 c = 0;
-    for (int b = 0; b < nb; b++) {
-        s += psum[b];
-        c += pcnt[b];
-    }
-    *out_sum = s;
-    *out_cnt = c;
-}
+};
 
 // the mean's partials first: their place does not depend on n, so any scan workspace (n >= 0) serves the mean
 struct ScanWs {
-    double* psum;  // MEAN_BLOCKS + 1 (the last: the total)
-    u64* pcnt;     // MEAN_BLOCKS + 1
+    double* psum;  // RED_BLOCKS + 1 (the last: the total)
+    u64* pcnt;     // RED_BLOCKS + 1
     u64* a;        // n + 1
     u64* bsum;     // scan_blocks(n) + 1
     size_t bytes;
 };
 ScanWs carve_scan(char* base, long long n) {
+    Carver c{base, 0};
     ScanWs w;
-    size_t o = 0;
-    w.psum = (double*)(base + o); o = gs2m_align_up(o + 8 * (MEAN_BLOCKS + 1));
-    w.pcnt = (u64*)(base + o); o = gs2m_align_up(o + 8 * (MEAN_BLOCKS + 1));
-    w.a = (u64*)(base + o); o = gs2m_align_up(o + 8 * (size_t)(n + 1));
-    w.bsum = (u64*)(base + o); o = gs2m_align_up(o + 8 * (size_t)(scan_blocks(n) + 1));
-    w.bytes = o;
+    w.psum = c.take<double>(RED_BLOCKS + 1);
+    w.pcnt = c.take<u64>(RED_BLOCKS + 1);
+    w.a = c.take<u64>(n + 1);
+    w.bsum = c.take<u64>(gs2m_scan_blocks(n) + 1);
+    w.bytes = c.off;
     return w;
 }
 
@@ -594,19 +558,14 @@ struct ThinWs {
 ThinWs carve_thin(char* base, long long n) {
     ThinWs w;
     w.g = carve_grid(base, n);
-    size_t o = w.g.bytes;
-    w.b = carve_build(base + o, n, w.g.bits);
-    o += w.b.bytes;
-    w.rank_s = (uint32_t*)(base + o); o = gs2m_align_up(o + 4 * (size_t)n);
-    w.st = (uint8_t*)(base + o); o = gs2m_align_up(o + (size_t)n);
-    w.counter = (unsigned*)(base + o); o = gs2m_align_up(o + 4);
-    w.bytes = o;
+    w.b = carve_build(base + w.g.bytes, n, w.g.bits);
+    Carver c{base, w.g.bytes + w.b.bytes};
+    w.rank_s = c.take<uint32_t>(n);
+    w.st = c.take<uint8_t>(n);
+    w.counter = c.take<unsigned>(1);
+    w.bytes = c.off;
     return w;
 }
-
-unsigned blocks_of(long long n) { return (unsigned)((n + 255) / 256); }
-constexpr long long MAX_POINTS = 0xFFFFFFF0ll;  // sorted slots and indices are u32
-constexpr long long MAX_LAUNCH = 256ll * 0x7FFFFFFFll;
 
 int nearest(long long n_queries, const double* queries, long long n_targets, double cell, const void* grid, double max_dist,
             long long* index, double* dist, bool with_index, void* stream) {
@@ -631,12 +590,6 @@ int nearest(long long n_queries, const double* queries, long long n_targets, dou
 }
 
 }  // namespace
-
-// the device-wide scan for the other evaluation unit (tnt_eval.hip; declared in common.h)
-long long gs2m_eval_scan_blocks(long long n) { return scan_blocks(n); }
-hipError_t gs2m_eval_scan_u64(unsigned long long* a, long long n, unsigned long long* bsum, hipStream_t s) {
-    return scan_u64(a, n, bsum, s);
-}
 
 extern "C" {
 
@@ -665,13 +618,10 @@ int gs2m_eval_sample_rows(long long n_verts, const double* verts, long long n_tr
     if (hipMemsetAsync(w.err, 0, 8, s) != hipSuccess) return GS2M_ERR_HIP;
     if (n_tris > 0)
         tri_rows_kernel<<<blocks_of(n_tris), 256, 0, s>>>(n_verts, verts, n_tris, tris, thresh, w.n12, w.rows, w.err);
-    if (hipGetLastError() != hipSuccess || scan_u64(w.rows, n_tris, w.bsum, s) != hipSuccess) return GS2M_ERR_HIP;
+    if (hipGetLastError() != hipSuccess || gs2m_scan_u64(w.rows, n_tris, w.bsum, s) != hipSuccess) return GS2M_ERR_HIP;
     int err[2];
     u64 total;
-    if (hipMemcpyAsync(err, w.err, sizeof(err), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(&total, w.rows + n_tris, sizeof(total), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess)
-        return GS2M_ERR_HIP;
+    if (gs2m_read_back(s, {{err, w.err, sizeof(err)}, {&total, w.rows + n_tris, sizeof(total)}}) != GS2M_OK) return GS2M_ERR_HIP;
     if (err[0]) return GS2M_ERR_INVALID_ARG;
     if (err[1] || total > (u64)MAX_LAUNCH) return GS2M_ERR_UNSUPPORTED;
     *host_rows = (long long)total;
@@ -685,11 +635,9 @@ int gs2m_eval_sample_count(long long n_tris, long long n_rows, const void* tri_w
     const TriWs tw = carve_tri((char*)tri_ws, n_tris);
     const RowWs rw = carve_row((char*)row_ws, n_rows);
     if (n_rows > 0) row_count_kernel<<<blocks_of(n_rows), 256, 0, s>>>(n_tris, n_rows, tw.rows, tw.n12, rw.cnt);
-    if (hipGetLastError() != hipSuccess || scan_u64(rw.cnt, n_rows, rw.bsum, s) != hipSuccess) return GS2M_ERR_HIP;
+    if (hipGetLastError() != hipSuccess || gs2m_scan_u64(rw.cnt, n_rows, rw.bsum, s) != hipSuccess) return GS2M_ERR_HIP;
     u64 total;
-    if (hipMemcpyAsync(&total, rw.cnt + n_rows, sizeof(total), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess)
-        return GS2M_ERR_HIP;
+    if (gs2m_read_back(s, {{&total, rw.cnt + n_rows, sizeof(total)}}) != GS2M_OK) return GS2M_ERR_HIP;
     if (total > (u64)MAX_LAUNCH) return GS2M_ERR_UNSUPPORTED;
     *host_samples = (long long)total;
     return GS2M_OK;
@@ -766,9 +714,7 @@ int gs2m_eval_thin(long long n, const double* pts, const unsigned* rank, double 
         thin_round_kernel<<<blocks_of(n), 256, 0, s>>>(n, inv, mask, w.g.spts, w.g.start, w.rank_s, r2, w.st, w.counter);
         rounds += BATCH;
         unsigned left = 0;
-        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&left, w.counter, 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess)
-            return GS2M_ERR_HIP;
+        if (gs2m_read_back(s, {{&left, w.counter, 4}}) != GS2M_OK) return GS2M_ERR_HIP;
         if (left == 0) break;
         if (rounds > n + BATCH) return GS2M_ERR_HIP;  // cannot happen: see above
     }
@@ -811,12 +757,10 @@ int gs2m_eval_compact(long long n, const double* pts, const unsigned char* flags
     hipStream_t s = (hipStream_t)stream;
     const ScanWs w = carve_scan((char*)ws, n);
     if (n > 0) flag_count_kernel<<<blocks_of(n), 256, 0, s>>>(n, flags, bit, w.a);
-    if (hipGetLastError() != hipSuccess || scan_u64(w.a, n, w.bsum, s) != hipSuccess) return GS2M_ERR_HIP;
+    if (hipGetLastError() != hipSuccess || gs2m_scan_u64(w.a, n, w.bsum, s) != hipSuccess) return GS2M_ERR_HIP;
     if (n > 0) compact_kernel<<<blocks_of(n), 256, 0, s>>>(n, pts, flags, bit, w.a, out);
     u64 total;
-    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&total, w.a + n, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess)
-        return GS2M_ERR_HIP;
+    if (gs2m_read_back(s, {{&total, w.a + n, 8}}) != GS2M_OK) return GS2M_ERR_HIP;
     *host_count = (long long)total;
     return GS2M_OK;
 }
@@ -837,13 +781,9 @@ int gs2m_eval_masked_mean(long long n, const double* dist, double max_dist, void
     if (n < 0 || !ws || !host_sum || !host_count || (n > 0 && !dist)) return GS2M_ERR_INVALID_ARG;
     hipStream_t s = (hipStream_t)stream;
     const ScanWs w = carve_scan((char*)ws, 0);  // the partials only (at the same place for every n)
-    mean_partial_kernel<<<MEAN_BLOCKS, 256, 0, s>>>(n, dist, max_dist, w.psum, w.pcnt);
-    mean_final_kernel<<<1, 64, 0, s>>>(MEAN_BLOCKS, w.psum, w.pcnt, w.psum + MEAN_BLOCKS, w.pcnt + MEAN_BLOCKS);
+    reduce_fixed_order<1, SumOp>(n, MeanTerm{dist, max_dist}, w.psum, w.pcnt, w.psum + RED_BLOCKS, w.pcnt + RED_BLOCKS, s);
     u64 c;
-    if (hipGetLastError() != hipSuccess ||
-        hipMemcpyAsync(host_sum, w.psum + MEAN_BLOCKS, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(&c, w.pcnt + MEAN_BLOCKS, 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-        return GS2M_ERR_HIP;
+    if (gs2m_read_back(s, {{host_sum, w.psum + RED_BLOCKS, 8}, {&c, w.pcnt + RED_BLOCKS, 8}}) != GS2M_OK) return GS2M_ERR_HIP;
     *host_count = (long long)c;
     return GS2M_OK;
 }

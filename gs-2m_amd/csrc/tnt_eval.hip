@@ -7,30 +7,21 @@
 // Voxel downsample: the cloud's box comes back to the host (it fixes lo and the bits per axis of the key); the keys
 // ix : iy : iz sort with the project's stable 32-bit radix sort, low word first and then the high word (LSD), so that the
 // members of a voxel stay in input order; a thread per voxel then adds its members one after the other.
-// ICP moments: the fixed-order fp64 sums of gs2m_eval_masked_mean (256 x 256 partial sums by stride, a shuffle tree, the four
-// waves, the partials in order), several quantities at once.
+// ICP moments and the cloud's box: the fixed-order reduction of eval_common.h (the one of gs2m_eval_masked_mean), several
+// quantities at once; the box folds with a NaN-keeping min / max in place of +.
 // Every sum is an integer sum or a fixed-order fp64 reduction: two runs are bitwise identical.  Compiled with -ffp-contract=off.
 #include <math.h>
-#include "common.h"
+#include "eval_common.h"
 #include "../../include/gs2m_tnt.h"
 
 namespace {
 
-typedef unsigned long long u64;
-constexpr int RED_BLOCKS = 256;   // reductions: partial sums
 constexpr int CROP_EDGES = 96;    // polygon edges per launch
 constexpr int POLY_MAX = 1024;
 constexpr int HIST_MAX_BINS = 4096;
 constexpr int HIST_BLOCKS = 1024;
-constexpr long long MAX_POINTS = 0xFFFFFFF0ll;  // sorted slots and indices are u32
-constexpr long long MAX_LAUNCH = 256ll * 0x7FFFFFFFll;
 constexpr double VOXEL_LIMIT = 2097152.0;  // 2^21 per axis
 
-unsigned blocks_of(long long n) { return (unsigned)((n + 255) / 256); }
-
-struct V3 {
-    double v[3];
-};
 struct M34 {
     double m[12];
 };
@@ -43,8 +34,7 @@ __global__ void __launch_bounds__(256) centres_kernel(long long nv, const double
     if (t >= nt) return;
     const int a = tris[3 * t], b = tris[3 * t + 1], c = tris[3 * t + 2];
     double* o = cloud + 3 * (size_t)(nv + t);
-    if (a < 0 || b < 0 || c < 0 || a >= nv || b >= nv || c >= nv) {
-        err[0] = 1;
+    if (!tri_in_range(a, b, c, nv, err)) {
         o[0] = o[1] = o[2] = __builtin_nan("");
         return;
     }
@@ -101,11 +91,14 @@ __global__ void __launch_bounds__(256) crop_kernel(long long n, const double* __
 __device__ __forceinline__ double nmin(double a, double b) { return a != a ? a : (b != b ? b : fmin(a, b)); }
 __device__ __forceinline__ double nmax(double a, double b) { return a != a ? a : (b != b ? b : fmax(a, b)); }
 
-__global__ void __launch_bounds__(256) box_partial_kernel(long long n, const double* __restrict__ pts, double* __restrict__ part) {
-    __shared__ double s_m[4][6];
-    const double INF = __builtin_huge_val();
-    double m[6] = {INF, INF, INF, -INF, -INF, -INF};
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+// the cloud's box as a fixed-order reduction of 6 quantities: min x, y, z, then max x, y, z
+struct BoxOp {
+    __device__ static double identity(int q) { return q < 3 ? __builtin_huge_val() : -__builtin_huge_val(); }
+    __device__ static double combine(int q, double a, double b) { return q < 3 ? nmin(a, b) : nmax(a, b); }
+};
+struct BoxTerm {
+    const double* pts;
+    __device__ void operator()(long long i, double* m, u64&) const {
 #pragma unroll
         for (int k = 0; k < 3; k++) {
             const double x = pts[3 * i + k];
@@ -113,34 +106,7 @@ __global__ void __launch_bounds__(256) box_partial_kernel(long long n, const dou
             m[3 + k] = nmax(m[3 + k], x);
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            m[k] = nmin(m[k], __shfl_down(m[k], o, 64));
-            m[3 + k] = nmax(m[3 + k], __shfl_down(m[3 + k], o, 64));
-        }
-    }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < 6; k++) s_m[w][k] = m[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        const int k = threadIdx.x;
-        const double a = s_m[0][k], b = s_m[1][k], c = s_m[2][k], d = s_m[3][k];
-        part[6 * blockIdx.x + k] = k < 3 ? nmin(nmin(a, b), nmin(c, d)) : nmax(nmax(a, b), nmax(c, d));
-    }
-}
-
-__global__ void __launch_bounds__(64) box_final_kernel(int nb, const double* __restrict__ part, double* __restrict__ out) {
-    const int k = threadIdx.x;
-    if (k >= 6) return;
-    double m = part[k];
-    for (int b = 1; b < nb; b++) m = k < 3 ? nmin(m, part[6 * b + k]) : nmax(m, part[6 * b + k]);
-    out[k] = m;
-}
+};
 
 struct VoxelSpec {
     double lo[3], s;
@@ -211,7 +177,8 @@ __global__ void __launch_bounds__(256) voxel_emit_kernel(long long n, const doub
 }
 
 struct VoxelWs {
-    uint32_t *klo, *khi, *v2, *kA, *vA, *kB, *vB;  // n each
+    uint32_t *klo, *khi, *v2;  // n each, as the sort's arrays
+    SortBufs sort;
     uint32_t* start;                               // n + 1
     u64* a;                                        // n + 1
     u64* bsum;                                     // scan blocks + 1
@@ -220,23 +187,21 @@ struct VoxelWs {
     size_t temp_bytes, bytes;
 };
 VoxelWs carve_voxel(char* base, long long n) {
+    Carver c{base, 0};
     VoxelWs w;
     const size_t m = (size_t)(n > 0 ? n : 1);
-    size_t o = 0;
-    uint32_t** arrs[7] = {&w.klo, &w.khi, &w.v2, &w.kA, &w.vA, &w.kB, &w.vB};
-    for (auto a : arrs) {
-        *a = (uint32_t*)(base + o);
-        o = gs2m_align_up(o + 4 * m);
-    }
-    w.start = (uint32_t*)(base + o); o = gs2m_align_up(o + 4 * (m + 1));
-    w.a = (u64*)(base + o); o = gs2m_align_up(o + 8 * (m + 1));
-    w.bsum = (u64*)(base + o); o = gs2m_align_up(o + 8 * (size_t)(gs2m_eval_scan_blocks(n) + 1));
-    w.part = (double*)(base + o); o = gs2m_align_up(o + 8 * (6 * RED_BLOCKS + 6));
-    w.temp = base + o;
+    w.klo = c.take<uint32_t>(m);
+    w.khi = c.take<uint32_t>(m);
+    w.v2 = c.take<uint32_t>(m);
+    w.sort = take_sort_bufs(c, m);
+    w.start = c.take<uint32_t>(m + 1);
+    w.a = c.take<u64>(m + 1);
+    w.bsum = c.take<u64>(gs2m_scan_blocks(n) + 1);
+    w.part = c.take<double>(6 * RED_BLOCKS + 6);
     const size_t t32 = gs2m_radix_temp_bytes(m, 32), t16 = gs2m_radix_temp_bytes(m, 16);
     w.temp_bytes = t32 > t16 ? t32 : t16;
-    o = gs2m_align_up(o + w.temp_bytes + GS2M_ALIGN);
-    w.bytes = o;
+    w.temp = c.take<char>(w.temp_bytes + GS2M_ALIGN);
+    w.bytes = c.off;
     return w;
 }
 
@@ -246,7 +211,7 @@ int bits_for(double imax) {  // bits that hold 0 .. imax
     return b;
 }
 
-// ---- fixed-order sums of Q quantities over the pairs ----
+// ---- ICP moments: the terms of the fixed-order sums over the pairs ----
 
 struct Means {
     double mx[3], my[3];
@@ -254,22 +219,18 @@ struct Means {
 
 // STAGE 0: d^2, x, y (7 sums) and the count; STAGE 1: Sigma (9, row major: rows y, columns x) and sx2, about the means
 template <int STAGE>
-__global__ void __launch_bounds__(256) icp_partial_kernel(long long n, const double* __restrict__ src, long long nt,
-                                                          const double* __restrict__ tgt, const long long* __restrict__ index, Means mu,
-                                                          double* __restrict__ psum, u64* __restrict__ pcnt, unsigned* __restrict__ err) {
-    constexpr int Q = STAGE == 0 ? 7 : 10;
-    __shared__ double s_s[4][Q];
-    __shared__ u64 s_c[4];
-    double acc[Q];
-#pragma unroll
-    for (int q = 0; q < Q; q++) acc[q] = 0.0;
-    u64 c = 0;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+struct IcpTerm {
+    const double *src, *tgt;
+    const long long* index;
+    long long nt;
+    Means mu;
+    unsigned* err;
+    __device__ void operator()(long long i, double* acc, u64& c) const {
         const long long t = index[i];
-        if (t < 0) continue;
+        if (t < 0) return;
         if (t >= nt) {  // not an index into these targets: the host refuses the call
             err[0] = 1u;
-            continue;
+            return;
         }
         const double x[3] = {src[3 * i], src[3 * i + 1], src[3 * i + 2]};
         const double y[3] = {tgt[3 * t], tgt[3 * t + 1], tgt[3 * t + 2]};
@@ -292,40 +253,7 @@ __global__ void __launch_bounds__(256) icp_partial_kernel(long long n, const dou
         }
         c++;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int q = 0; q < Q; q++) acc[q] += __shfl_down(acc[q], o, 64);
-        c += __shfl_down(c, o, 64);
-    }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int q = 0; q < Q; q++) s_s[w][q] = acc[q];
-        s_c[w] = c;
-    }
-    __syncthreads();
-    if (threadIdx.x < Q) {
-        const int q = threadIdx.x;
-        psum[(size_t)blockIdx.x * Q + q] = (s_s[0][q] + s_s[1][q]) + (s_s[2][q] + s_s[3][q]);
-    }
-    if (threadIdx.x == 0) pcnt[blockIdx.x] = (s_c[0] + s_c[1]) + (s_c[2] + s_c[3]);
-}
-
-__global__ void __launch_bounds__(64) icp_final_kernel(int nb, int Q, const double* __restrict__ psum, const u64* __restrict__ pcnt,
-                                                       double* __restrict__ out_sum, u64* __restrict__ out_cnt) {
-    const int q = threadIdx.x;
-    if (q < Q) {
-        double s = 0.0;
-        for (int b = 0; b < nb; b++) s += psum[(size_t)b * Q + q];
-        out_sum[q] = s;
-    }
-    if (q == 0) {
-        u64 c = 0;
-        for (int b = 0; b < nb; b++) c += pcnt[b];
-        *out_cnt = c;
-    }
-}
+};
 
 struct IcpWs {
     double* psum;  // 10 RED_BLOCKS
@@ -336,14 +264,14 @@ struct IcpWs {
     size_t bytes;
 };
 IcpWs carve_icp(char* base) {
+    Carver c{base, 0};
     IcpWs w;
-    size_t o = 0;
-    w.psum = (double*)(base + o); o = gs2m_align_up(o + 8 * 10 * RED_BLOCKS);
-    w.pcnt = (u64*)(base + o); o = gs2m_align_up(o + 8 * RED_BLOCKS);
-    w.tot = (double*)(base + o); o = gs2m_align_up(o + 8 * 10);
-    w.cnt = (u64*)(base + o); o = gs2m_align_up(o + 8);
-    w.err = (unsigned*)(base + o); o = gs2m_align_up(o + 4);
-    w.bytes = o;
+    w.psum = c.take<double>(10 * RED_BLOCKS);
+    w.pcnt = c.take<u64>(RED_BLOCKS);
+    w.tot = c.take<double>(10);
+    w.cnt = c.take<u64>(1);
+    w.err = c.take<unsigned>(1);
+    w.bytes = c.off;
     return w;
 }
 
@@ -387,9 +315,7 @@ int gs2m_tnt_mesh_points(long long n_verts, const double* verts, long long n_tri
     if (n_verts > 0 && hipMemcpyAsync(cloud, verts, 24 * (size_t)n_verts, hipMemcpyDeviceToDevice, s) != hipSuccess) return GS2M_ERR_HIP;
     if (n_tris > 0) centres_kernel<<<blocks_of(n_tris), 256, 0, s>>>(n_verts, verts, n_tris, tris, cloud, err);
     int bad = 0;
-    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&bad, err, 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess)
-        return GS2M_ERR_HIP;
+    if (gs2m_read_back(s, {{&bad, err, 4}}) != GS2M_OK) return GS2M_ERR_HIP;
     return bad ? GS2M_ERR_INVALID_ARG : GS2M_OK;
 }
 
@@ -442,12 +368,9 @@ int gs2m_tnt_voxel_downsample(long long n, const double* pts, double s, void* ws
     if (n == 0) return GS2M_OK;
     hipStream_t st = (hipStream_t)stream;
     const VoxelWs w = carve_voxel((char*)ws, n);
-    box_partial_kernel<<<RED_BLOCKS, 256, 0, st>>>(n, pts, w.part);
-    box_final_kernel<<<1, 64, 0, st>>>(RED_BLOCKS, w.part, w.part + 6 * RED_BLOCKS);
+    reduce_fixed_order<6, BoxOp>(n, BoxTerm{pts}, w.part, nullptr, w.part + 6 * RED_BLOCKS, nullptr, st);
     double box[6];
-    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(box, w.part + 6 * RED_BLOCKS, sizeof(box), hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess)
-        return GS2M_ERR_HIP;
+    if (gs2m_read_back(st, {{box, w.part + 6 * RED_BLOCKS, sizeof(box)}}) != GS2M_OK) return GS2M_ERR_HIP;
     VoxelSpec v;
     v.s = s;
     int bits[3];
@@ -462,24 +385,23 @@ int gs2m_tnt_voxel_downsample(long long n, const double* pts, double s, void* ws
     const int total = bits[0] + bits[1] + bits[2];
     voxel_key_kernel<<<blocks_of(n), 256, 0, st>>>(n, pts, v, w.klo, w.khi);
     if (hipGetLastError() != hipSuccess) return GS2M_ERR_HIP;
-    if (gs2m_radix_sort_pairs(w.temp, w.temp_bytes, w.klo, nullptr, w.kA, w.vA, w.kB, w.vB, (size_t)n, total < 32 ? total : 32, false, st) !=
+    const SortBufs& b = w.sort;
+    if (gs2m_radix_sort_pairs(w.temp, w.temp_bytes, w.klo, nullptr, b.kA, b.vA, b.kB, b.vB, (size_t)n, total < 32 ? total : 32, false, st) !=
         hipSuccess)
         return GS2M_ERR_HIP;
     if (total > 32) {
         // LSD: the order by the low word, then stably by the high word (klo is free again: it takes the gathered high words)
-        voxel_regather_kernel<<<blocks_of(n), 256, 0, st>>>(n, w.vB, w.khi, w.klo, w.v2);
+        voxel_regather_kernel<<<blocks_of(n), 256, 0, st>>>(n, b.vB, w.khi, w.klo, w.v2);
         if (hipGetLastError() != hipSuccess ||
-            gs2m_radix_sort_pairs(w.temp, w.temp_bytes, w.klo, w.v2, w.kA, w.vA, w.kB, w.vB, (size_t)n, total - 32, false, st) != hipSuccess)
+            gs2m_radix_sort_pairs(w.temp, w.temp_bytes, w.klo, w.v2, b.kA, b.vA, b.kB, b.vB, (size_t)n, total - 32, false, st) != hipSuccess)
             return GS2M_ERR_HIP;
     }
-    voxel_head_kernel<<<blocks_of(n), 256, 0, st>>>(n, pts, w.vB, v, w.a);
-    if (hipGetLastError() != hipSuccess || gs2m_eval_scan_u64(w.a, n, w.bsum, st) != hipSuccess) return GS2M_ERR_HIP;
+    voxel_head_kernel<<<blocks_of(n), 256, 0, st>>>(n, pts, b.vB, v, w.a);
+    if (hipGetLastError() != hipSuccess || gs2m_scan_u64(w.a, n, w.bsum, st) != hipSuccess) return GS2M_ERR_HIP;
     voxel_start_kernel<<<blocks_of(n + 1), 256, 0, st>>>(n, w.a, w.start);
-    voxel_emit_kernel<<<blocks_of(n), 256, 0, st>>>(n, pts, w.vB, w.a, w.start, out);
+    voxel_emit_kernel<<<blocks_of(n), 256, 0, st>>>(n, pts, b.vB, w.a, w.start, out);
     u64 total_voxels;
-    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&total_voxels, w.a + n, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess)
-        return GS2M_ERR_HIP;
+    if (gs2m_read_back(st, {{&total_voxels, w.a + n, 8}}) != GS2M_OK) return GS2M_ERR_HIP;
     *host_count = (long long)total_voxels;
     return GS2M_OK;
 }
@@ -509,15 +431,11 @@ int gs2m_tnt_icp_moments(long long n, const double* source, long long n_targets,
     *host_count = 0;
     Means mu = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
     if (hipMemsetAsync(w.err, 0, 4, s) != hipSuccess) return GS2M_ERR_HIP;
-    icp_partial_kernel<0><<<RED_BLOCKS, 256, 0, s>>>(n, source, n_targets, targets, index, mu, w.psum, w.pcnt, w.err);
-    icp_final_kernel<<<1, 64, 0, s>>>(RED_BLOCKS, 7, w.psum, w.pcnt, w.tot, w.cnt);
+    reduce_fixed_order<7, SumOp>(n, IcpTerm<0>{source, targets, index, n_targets, mu, w.err}, w.psum, w.pcnt, w.tot, w.cnt, s);
     double t[10];
     u64 c;
     unsigned bad = 0;
-    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(t, w.tot, 7 * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(&c, w.cnt, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(&bad, w.err, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-        return GS2M_ERR_HIP;
+    if (gs2m_read_back(s, {{t, w.tot, 7 * 8}, {&c, w.cnt, 8}, {&bad, w.err, 4}}) != GS2M_OK) return GS2M_ERR_HIP;
     if (bad) return GS2M_ERR_INVALID_ARG;
     if (c == 0) return GS2M_OK;
     const double cd = (double)c;
@@ -527,11 +445,8 @@ int gs2m_tnt_icp_moments(long long n, const double* source, long long n_targets,
         host_out[1 + k] = mu.mx[k] = t[1 + k] / cd;
         host_out[4 + k] = mu.my[k] = t[4 + k] / cd;
     }
-    icp_partial_kernel<1><<<RED_BLOCKS, 256, 0, s>>>(n, source, n_targets, targets, index, mu, w.psum, w.pcnt, w.err);
-    icp_final_kernel<<<1, 64, 0, s>>>(RED_BLOCKS, 10, w.psum, w.pcnt, w.tot, w.cnt);
-    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(t, w.tot, 10 * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess)
-        return GS2M_ERR_HIP;
+    reduce_fixed_order<10, SumOp>(n, IcpTerm<1>{source, targets, index, n_targets, mu, w.err}, w.psum, w.pcnt, w.tot, w.cnt, s);
+    if (gs2m_read_back(s, {{t, w.tot, 10 * 8}}) != GS2M_OK) return GS2M_ERR_HIP;
     for (int k = 0; k < 10; k++) host_out[7 + k] = t[k] / cd;
     return GS2M_OK;
 }

@@ -20,7 +20,7 @@
 // No float atomics anywhere: every value is written by one thread in an order fixed by the scans, so two runs are bitwise
 // identical.  Compiled with -ffp-contract=off: every expression is evaluated as written, which tests/mesh_ref.py restates.
 #include <limits.h>
-#include "common.h"
+#include "eval_common.h"
 #include "../../include/gs2m_mesh.h"
 #define GS2M_MC_CONST __constant__
 #include "tsdf_tables.h"
@@ -53,14 +53,14 @@ struct TouchWs {
 };
 TouchWs carve_touch(char* base, long long N) {
     const size_t nch = (size_t)((N + CHUNK - 1) / CHUNK);
+    Carver c{base, 0};
     TouchWs w;
-    size_t o = 0;
-    w.flags = (uint8_t*)(base + o); o = gs2m_align_up(o + (size_t)N);
-    w.chunk = (uint32_t*)(base + o); o = gs2m_align_up(o + 4 * nch);
-    w.pref_t = (uint32_t*)(base + o); o = gs2m_align_up(o + 4 * nch);
-    w.pref_n = (uint32_t*)(base + o); o = gs2m_align_up(o + 4 * nch);
-    w.counters = (int*)(base + o); o = gs2m_align_up(o + 4 * 8);
-    w.bytes = o;
+    w.flags = c.take<uint8_t>(N);
+    w.chunk = c.take<uint32_t>(nch);
+    w.pref_t = c.take<uint32_t>(nch);
+    w.pref_n = c.take<uint32_t>(nch);
+    w.counters = c.take<int>(8);
+    w.bytes = c.off;
     return w;
 }
 struct MeshWs {
@@ -69,20 +69,20 @@ struct MeshWs {
     uint32_t* slot_cnt;  // n: vertices | triangles << 16 of the block
     uint32_t* pref_v;    // n
     uint32_t* pref_t;    // n
-    unsigned long long* totals;  // 2
+    u64* totals;         // 2
     size_t bytes;
 };
 MeshWs carve_mesh(char* base, long long n) {
+    Carver c{base, 0};
     MeshWs w;
-    size_t o = 0;
     const size_t nv = (size_t)n * BV;
-    w.cube = (uint16_t*)(base + o); o = gs2m_align_up(o + 2 * nv);
-    w.vinfo = (uint32_t*)(base + o); o = gs2m_align_up(o + 4 * nv);
-    w.slot_cnt = (uint32_t*)(base + o); o = gs2m_align_up(o + 4 * (size_t)n);
-    w.pref_v = (uint32_t*)(base + o); o = gs2m_align_up(o + 4 * (size_t)n);
-    w.pref_t = (uint32_t*)(base + o); o = gs2m_align_up(o + 4 * (size_t)n);
-    w.totals = (unsigned long long*)(base + o); o = gs2m_align_up(o + 16);
-    w.bytes = o;
+    w.cube = c.take<uint16_t>(nv);
+    w.vinfo = c.take<uint32_t>(nv);
+    w.slot_cnt = c.take<uint32_t>(n);
+    w.pref_v = c.take<uint32_t>(n);
+    w.pref_t = c.take<uint32_t>(n);
+    w.totals = c.take<u64>(2);
+    w.bytes = c.off;
     return w;
 }
 
@@ -530,8 +530,7 @@ int gs2m_tsdf_touch(const int* dom, float voxel, float trunc, int W, int H, cons
     const long long nch = (N + CHUNK - 1) / CHUNK;
     if (nch > INT_MAX) return GS2M_ERR_UNSUPPORTED;
     TouchWs w = carve_touch((char*)touch_ws, N);
-    hipError_t e = hipMemsetAsync(w.counters, 0, 8 * sizeof(int), s);
-    if (e != hipSuccess) return GS2M_ERR_HIP;
+    if (hipMemsetAsync(w.counters, 0, 8 * sizeof(int), s) != hipSuccess) return GS2M_ERR_HIP;
     const int n = ((W + 3) / 4) * ((H + 3) / 4);
     touch_kernel<<<(n + 255) / 256, 256, 0, s>>>(d, 16.0f * voxel, trunc, W, H, depth, depth_trunc, fx, fy, cx, cy, mat34(c2w),
                                                  w.flags, w.counters + 4);
@@ -539,11 +538,8 @@ int gs2m_tsdf_touch(const int* dom, float voxel, float trunc, int W, int H, cons
     chunk_scan_kernel<<<1, 256, 0, s>>>((int)nch, w.chunk, w.pref_t, w.pref_n, capacity, state, w.counters);
     chunk_assign_kernel<<<(unsigned)nch, 256, 0, s>>>(d, N, w.flags, index, w.pref_t, w.pref_n, w.counters, block_coords,
                                                       touched_slots);
-    if ((e = hipGetLastError()) != hipSuccess) return GS2M_ERR_HIP;
     int cnt[8], st = 0;
-    if (hipMemcpyAsync(cnt, w.counters, sizeof(cnt), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(&st, state, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-        return GS2M_ERR_HIP;
+    if (gs2m_read_back(s, {{cnt, w.counters, sizeof(cnt)}, {&st, state, sizeof(int)}}) != GS2M_OK) return GS2M_ERR_HIP;
     info[0] = cnt[3] ? st : cnt[5];
     info[1] = cnt[1];
     info[2] = cnt[0];
@@ -578,10 +574,8 @@ int gs2m_tsdf_mesh_count(const int* dom, int n_blocks, const int* index, const i
     cube_case_kernel<<<n_blocks * 16, 256, 0, s>>>(d, index, block_coords, tsdf, weight, w.cube);
     mesh_count_kernel<<<n_blocks, 256, 0, s>>>(d, index, block_coords, tsdf, w.cube, w.vinfo, w.slot_cnt);
     slot_scan_kernel<<<1, 256, 0, s>>>(n_blocks, w.slot_cnt, w.pref_v, w.pref_t, w.totals);
-    if (hipGetLastError() != hipSuccess) return GS2M_ERR_HIP;
-    unsigned long long t[2];
-    if (hipMemcpyAsync(t, w.totals, sizeof(t), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-        return GS2M_ERR_HIP;
+    u64 t[2];
+    if (gs2m_read_back(s, {{t, w.totals, sizeof(t)}}) != GS2M_OK) return GS2M_ERR_HIP;
     totals[0] = (long long)t[0];
     totals[1] = (long long)t[1];
     if (t[0] >= (1ull << VINFO_BITS) || t[1] >= (1ull << 31)) return GS2M_ERR_UNSUPPORTED;

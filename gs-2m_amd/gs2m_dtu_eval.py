@@ -12,7 +12,6 @@ writes OUT/results.json (mean_d2s, mean_s2d, overall, plus counts, seed and stag
 import argparse
 import ctypes as C
 import json
-import math
 import os
 import sys
 import time
@@ -25,9 +24,8 @@ import numpy as np
 import torch
 
 import gs2m_native as N
-
-
-from gs2m_eval_util import compact as _compact, device as _dev, points as _points, ptr as _ptr, workspace as _ws  # noqa: E402
+from gs2m_eval_util import (TargetGrid, compact as _compact, device as _dev, grid_cell, masked_mean, points as _points,  # noqa: E402,F401
+                            ptr as _ptr, read_ply, triangles_i32, workspace_for, write_point_cloud)
 
 
 # ---- the steps, on device tensors ----------------------------------------------------------------------------------------
@@ -48,17 +46,12 @@ def sample_mesh_points(vertices, triangles, thresh=0.2, device=None):
     order.  -> (V + S, 3) fp64 tensor on the device."""
     dev = _dev(device)
     v = _points(vertices, dev)
-    f = torch.as_tensor(np.asarray(triangles, dtype=np.int64).reshape(-1, 3) if not torch.is_tensor(triangles) else triangles)
-    f = f.to(device=dev, dtype=torch.int32).reshape(-1, 3).contiguous()
-    L, nv, nt = N.lib(), len(v), len(f)
-    tb = C.c_longlong()
-    N.check(L.gs2m_eval_sample_workspace_bytes(nt, 0, C.byref(tb), None), "gs2m_eval_sample_workspace_bytes")
-    tri_ws = _ws(tb.value, dev)
+    f = triangles_i32(triangles, dev)
+    nv, nt = len(v), len(f)
+    tri_ws = workspace_for("gs2m_eval_sample_workspace_bytes", dev, nt, 0, only=0)
     rows = C.c_longlong()
     N.launch("gs2m_eval_sample_rows", dev, nv, _ptr(v), nt, _ptr(f), float(thresh), _ptr(tri_ws), C.byref(rows))
-    rb = C.c_longlong()
-    N.check(L.gs2m_eval_sample_workspace_bytes(nt, rows.value, None, C.byref(rb)), "gs2m_eval_sample_workspace_bytes")
-    row_ws = _ws(rb.value, dev)
+    row_ws = workspace_for("gs2m_eval_sample_workspace_bytes", dev, nt, rows.value, only=1)
     ns = C.c_longlong()
     N.launch("gs2m_eval_sample_count", dev, nt, rows.value, _ptr(tri_ws), _ptr(row_ws), C.byref(ns))
     cloud = torch.empty((nv + ns.value, 3), dtype=torch.float64, device=dev)
@@ -84,11 +77,9 @@ def gather(points, order, device=None):
 
 
 def _thin(p, radius, rank, dev):
-    wb = C.c_longlong()
-    N.check(N.lib().gs2m_eval_thin_workspace_bytes(len(p), C.byref(wb)), "gs2m_eval_thin_workspace_bytes")
     keep = torch.empty(len(p), dtype=torch.uint8, device=dev)
     rounds = C.c_int()
-    ws = _ws(wb.value, dev)
+    ws = workspace_for("gs2m_eval_thin_workspace_bytes", dev, len(p))
     N.launch("gs2m_eval_thin", dev, len(p), _ptr(p), _ptr(rank), float(radius), _ptr(ws), _ptr(keep), C.byref(rounds))
     return keep, rounds.value
 
@@ -141,47 +132,10 @@ def above_plane(points, plane, device=None):
     return flags
 
 
-def grid_cell(targets, max_dist):
-    """The grid edge for nearest-neighbour queries against `targets` (a device tensor): about two point spacings of a surface
-    sample (2 extent / sqrt(n)), never below a volume's spacing (extent / cbrt(n)), and within [max_dist / 128, max_dist] so
-    that the walk's shells and the coarse bound stay few."""
-    n = len(targets)
-    if n == 0:
-        return max_dist
-    lo, hi = torch.aminmax(targets, dim=0)
-    ext = float((hi - lo).max())
-    h = max(2.0 * ext / math.sqrt(n), ext / n ** (1.0 / 3.0)) if ext > 0 else max_dist
-    return min(max(h, max_dist / 128.0), max_dist)
-
-
-def _nearest(q, t, max_dist, cell, dev):
-    gb, bb = C.c_longlong(), C.c_longlong()
-    N.check(N.lib().gs2m_eval_grid_bytes(len(t), C.byref(gb), C.byref(bb)), "gs2m_eval_grid_bytes")
-    dist = torch.empty(len(q), dtype=torch.float64, device=dev)
-    grid, bws = _ws(gb.value, dev), _ws(bb.value, dev)
-    N.launch("gs2m_eval_grid_build", dev, len(t), _ptr(t), float(cell), _ptr(grid), _ptr(bws))
-    del bws
-    N.launch("gs2m_eval_nearest", dev, len(q), _ptr(q), len(t), float(cell), _ptr(grid), float(max_dist), _ptr(dist))
-    return dist
-
-
 def nearest_distances(queries, targets, max_dist, cell=None, device=None):
     """The distance of every query to its nearest target point where that is < max_dist, +inf elsewhere.  -> numpy fp64."""
     dev = _dev(device)
-    q, t = _points(queries, dev), _points(targets, dev)
-    return _nearest(q, t, max_dist, cell if cell else grid_cell(t, max_dist), dev).cpu().numpy()
-
-
-def masked_mean(dist, max_dist, device=None):
-    """mean of the entries < max_dist (NaN when there is none), summed in a fixed order on the device.  -> (mean, count)."""
-    dev = _dev(device)
-    d = torch.as_tensor(dist).to(dev, torch.float64).contiguous()
-    wb = C.c_longlong()
-    N.check(N.lib().gs2m_eval_scan_workspace_bytes(0, C.byref(wb)), "gs2m_eval_scan_workspace_bytes")
-    tot, cnt = C.c_double(), C.c_longlong()
-    ws = _ws(wb.value, dev)
-    N.launch("gs2m_eval_masked_mean", dev, len(d), _ptr(d), float(max_dist), _ptr(ws), C.byref(tot), C.byref(cnt))
-    return (tot.value / cnt.value if cnt.value else float("nan")), cnt.value
+    return TargetGrid(targets, max_dist, cell, dev).distances(queries, max_dist).cpu().numpy()
 
 
 # ---- colours of the two visualisation clouds -------------------------------------------------------------------------------
@@ -230,12 +184,12 @@ def evaluate_mesh(vertices, triangles, stl, obs_mask, bb, res, plane, downsample
     data_in_obs = _compact(down, flags, 1, dev)
     t0 = stage("filter", t0)
     stl_t = _points(stl, dev)
-    d2s = _nearest(data_in_obs, stl_t, max_dist, grid_cell(stl_t, max_dist), dev)
+    d2s = TargetGrid(stl_t, max_dist, device=dev).distances(data_in_obs, max_dist)
     mean_d2s, n_d2s = masked_mean(d2s, max_dist, dev)
     t0 = stage("d2s", t0)
     above = above_plane(stl_t, plane, dev)
     stl_above = _compact(stl_t, above, 0, dev)
-    s2d = _nearest(stl_above, data_in, max_dist, grid_cell(data_in, max_dist), dev)
+    s2d = TargetGrid(data_in, max_dist, device=dev).distances(stl_above, max_dist)
     mean_s2d, n_s2d = masked_mean(s2d, max_dist, dev)
     stage("s2d", t0)
     out = {"mean_d2s": mean_d2s, "mean_s2d": mean_s2d, "overall": (mean_d2s + mean_s2d) / 2,
@@ -264,76 +218,6 @@ def evaluate_mesh(vertices, triangles, stl, obs_mask, bb, res, plane, downsample
 
 
 # ---- files -------------------------------------------------------------------------------------------------------------------
-
-_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "<i2", "int16": "<i2", "ushort": "<u2",
-              "uint16": "<u2", "int": "<i4", "int32": "<i4", "uint": "<u4", "uint32": "<u4", "float": "<f4", "float32": "<f4",
-              "double": "<f8", "float64": "<f8"}
-
-
-def read_ply(file):
-    """Binary little-endian PLY -> (vertices (V, 3) fp64, triangles (F, 3) int32; empty without a face element).  Vertex
-    coordinates are widened to fp64 exactly as stored (float or double); other scalar properties are skipped."""
-    with open(str(file), "rb") as f:
-        data = f.read()
-    if not data.startswith(b"ply"):
-        raise ValueError(f"{file}: not a PLY file")
-    end = data.find(b"end_header\n")
-    if end < 0:
-        raise ValueError(f"{file}: PLY header without end_header")
-    end += len(b"end_header\n")
-    lines = data[:end].decode("ascii", "replace").split("\n")
-    fmt = [ln for ln in lines if ln.startswith("format")]
-    if not fmt or fmt[0].split()[1] != "binary_little_endian":
-        raise ValueError(f"{file}: {fmt[0] if fmt else 'no format line'}: only binary little-endian PLY is read (convert ASCII PLY first)")
-    elems = []
-    for ln in lines:
-        p = ln.split()
-        if not p:
-            continue
-        if p[0] == "element":
-            elems.append([p[1], int(p[2]), []])
-        elif p[0] == "property":
-            elems[-1][2].append(p[1:])
-    off, verts, tris = end, np.zeros((0, 3), np.float64), np.zeros((0, 3), np.int32)
-    for name, n, props in elems:
-        if props and props[0][0] == "list":
-            if len(props) != 1:
-                raise ValueError(f"{file}: element {name}: a list with other properties is not read")
-            dt = np.dtype([("n", _PLY_TYPES[props[0][1]]), ("v", _PLY_TYPES[props[0][2]], (3,))])
-            a = np.frombuffer(data, dt, n, off)
-            if n and not np.all(a["n"] == 3):
-                raise ValueError(f"{file}: only triangle faces are read")
-            off += dt.itemsize * n
-            if name == "face":
-                tris = a["v"].astype(np.int32)
-            continue
-        dt = np.dtype([(q[1], _PLY_TYPES[q[0]]) for q in props])
-        a = np.frombuffer(data, dt, n, off)
-        off += dt.itemsize * n
-        if name == "vertex":
-            verts = np.stack([a[k].astype(np.float64) for k in "xyz"], axis=1) if n else np.zeros((0, 3), np.float64)
-    return verts, tris
-
-
-def write_point_cloud(file, points, colors=None):
-    """Binary little-endian PLY: double x y z, uchar red green blue (colour * 255 rounded to nearest)."""
-    p = np.asarray(points, np.float64).reshape(-1, 3)
-    fields = [("x", "<f8"), ("y", "<f8"), ("z", "<f8")]
-    if colors is not None:
-        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
-    a = np.zeros(len(p), np.dtype(fields))
-    for k, n in enumerate("xyz"):
-        a[n] = p[:, k]
-    head = f"ply\nformat binary_little_endian 1.0\nelement vertex {len(p)}\nproperty double x\nproperty double y\nproperty double z\n"
-    if colors is not None:
-        c = np.clip(np.rint(np.asarray(colors, np.float64).reshape(-1, 3) * 255.0), 0, 255).astype(np.uint8)
-        for k, n in enumerate(("red", "green", "blue")):
-            a[n] = c[:, k]
-        head += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
-    with open(str(file), "wb") as f:
-        f.write((head + "end_header\n").encode("ascii"))
-        f.write(a.tobytes())
-
 
 def load_dtu_ground_truth(dtu_dir, scan):
     """The DTU evaluation files of `scan`: Points/stl/stl{scan:03}_total.ply, ObsMask/ObsMask{scan}_10.mat (ObsMask, BB, Res)

@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 import gs2m_native as N
+from gs2m_eval_util import workspace_for
 
 BLOCK = 16
 POOL_FULL = 1  # include/gs2m_mesh.h GS2M_TSDF_POOL_FULL
@@ -76,12 +77,10 @@ class TSDFVolume:
             raise ValueError(f"gs2m_mesh: empty domain {domain_min} .. {domain_max}")
         self.index_bytes = 4 * self.dom[3] * self.dom[4] * self.dom[5]
         self.ignored_points = 0
-        tb = C.c_longlong()
-        N.check(N.lib().gs2m_tsdf_workspace_bytes(self._dom, 0, C.byref(tb), None), "gs2m_tsdf_workspace_bytes")
         with N.device_guard(self.device):
             self.index = torch.full((self.dom[3] * self.dom[4] * self.dom[5],), -1, dtype=torch.int32, device=self.device)
             self.state = torch.zeros(4, dtype=torch.int32, device=self.device)
-            self.touch_ws = torch.zeros(tb.value, dtype=torch.uint8, device=self.device)
+            self.touch_ws = workspace_for("gs2m_tsdf_workspace_bytes", self.device, self._dom, 0, only=0).zero_()
         self.n_blocks = 0
         self.capacity = 0
         self._grow(max(1, int(capacity)))
@@ -139,9 +138,7 @@ class TSDFVolume:
         n = self.n_blocks
         if n == 0:
             return TriangleMesh()
-        mb = C.c_longlong()
-        N.check(N.lib().gs2m_tsdf_workspace_bytes(self._dom, n, None, C.byref(mb)), "gs2m_tsdf_workspace_bytes")
-        ws = torch.empty(mb.value, dtype=torch.uint8, device=self.device)
+        ws = workspace_for("gs2m_tsdf_workspace_bytes", self.device, self._dom, n, only=1)
         tot = (C.c_longlong * 2)()
         N.launch("gs2m_tsdf_mesh_count", self.device, self._dom, n, _ptr(self.index), _ptr(self.block_coords), _ptr(self.tsdf),
                  _ptr(self.weight), _ptr(ws), tot)

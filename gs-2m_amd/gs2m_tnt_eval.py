@@ -27,8 +27,8 @@ import numpy as np
 import torch
 
 import gs2m_native as N
-from gs2m_dtu_eval import grid_cell, masked_mean, read_ply  # noqa: F401  (read_ply: the PLY reader)
-from gs2m_eval_util import compact as _compact, device as _dev, points as _points, ptr as _ptr, workspace as _ws
+from gs2m_eval_util import (TargetGrid, compact as _compact, device as _dev, grid_cell, masked_mean, points as _points,  # noqa: F401
+                            ptr as _ptr, read_ply, triangles_i32, workspace as _ws, workspace_for)
 
 # scripts/eval_tnt/config.py: the distance threshold tau of every scene
 SCENES_TAU = {"Barn": 0.01, "Caterpillar": 0.005, "Church": 0.025, "Courthouse": 0.025, "Ignatius": 0.003, "Meetingroom": 0.01,
@@ -44,8 +44,7 @@ def mesh_points(vertices, triangles, device=None):
     """The source cloud: the vertices in file order, then ((p0 + p1) + p2) / 3 of every triangle.  -> (V + F, 3) tensor."""
     dev = _dev(device)
     v = _points(vertices, dev)
-    f = torch.as_tensor(np.asarray(triangles, dtype=np.int64).reshape(-1, 3) if not torch.is_tensor(triangles) else triangles)
-    f = f.to(device=dev, dtype=torch.int32).reshape(-1, 3).contiguous()
+    f = triangles_i32(triangles, dev)
     cloud = torch.empty((len(v) + len(f), 3), dtype=torch.float64, device=dev)
     ws = _ws(8, dev)
     N.launch("gs2m_tnt_mesh_points", dev, len(v), _ptr(v), len(f), _ptr(f), _ptr(ws), _ptr(cloud))
@@ -98,9 +97,7 @@ def voxel_downsample(points, s, device=None):
     (ix, iy, iz) order."""
     dev = _dev(device)
     p = _points(points, dev)
-    wb = C.c_longlong()
-    N.check(N.lib().gs2m_tnt_voxel_workspace_bytes(len(p), C.byref(wb)), "gs2m_tnt_voxel_workspace_bytes")
-    ws = _ws(wb.value, dev)
+    ws = workspace_for("gs2m_tnt_voxel_workspace_bytes", dev, len(p))
     out = torch.empty_like(p)
     cnt = C.c_longlong()
     N.launch("gs2m_tnt_voxel_downsample", dev, len(p), _ptr(p), float(s), _ptr(ws), _ptr(out), C.byref(cnt))
@@ -119,28 +116,6 @@ def uniform_downsample(points, limit=MAX_POINT_NUMBER, device=None):
     return out
 
 
-class TargetGrid:
-    """The hashed grid over a target cloud, built once and queried many times (an ICP stage: once per iteration)."""
-
-    def __init__(self, targets, max_dist, cell=None, device=None):
-        self.dev = _dev(device)
-        self.targets = _points(targets, self.dev)
-        self.cell = float(cell) if cell else grid_cell(self.targets, max_dist)
-        gb, bb = C.c_longlong(), C.c_longlong()
-        N.check(N.lib().gs2m_eval_grid_bytes(len(self.targets), C.byref(gb), C.byref(bb)), "gs2m_eval_grid_bytes")
-        self.grid, bws = _ws(gb.value, self.dev), _ws(bb.value, self.dev)
-        N.launch("gs2m_eval_grid_build", self.dev, len(self.targets), _ptr(self.targets), self.cell, _ptr(self.grid), _ptr(bws))
-
-    def query(self, queries, max_dist):
-        """-> (index int64 tensor, dist tensor): index -1 and dist +inf where nothing lies within max_dist"""
-        q = _points(queries, self.dev)
-        index = torch.empty(len(q), dtype=torch.int64, device=self.dev)
-        dist = torch.empty(len(q), dtype=torch.float64, device=self.dev)
-        N.launch("gs2m_eval_nearest_index", self.dev, len(q), _ptr(q), len(self.targets), self.cell, _ptr(self.grid), float(max_dist),
-                 _ptr(index), _ptr(dist))
-        return index, dist
-
-
 def nearest(queries, targets, max_dist, cell=None, device=None):
     """For every query the index (in the targets' given order; the lowest among equals) and the distance of its nearest target
     where that is < max_dist; else -1 and +inf.  -> (index, dist) tensors."""
@@ -153,9 +128,7 @@ def icp_moments(source, targets, index, device=None):
     dev = _dev(device)
     x, t = _points(source, dev), _points(targets, dev)
     idx = torch.as_tensor(index).to(dev, torch.int64).contiguous()
-    wb = C.c_longlong()
-    N.check(N.lib().gs2m_tnt_icp_workspace_bytes(C.byref(wb)), "gs2m_tnt_icp_workspace_bytes")
-    ws = _ws(wb.value, dev)
+    ws = workspace_for("gs2m_tnt_icp_workspace_bytes", dev)
     cnt, out = C.c_longlong(), (C.c_double * 17)()
     N.launch("gs2m_tnt_icp_moments", dev, len(x), _ptr(x), len(t), _ptr(t), _ptr(idx), _ptr(ws), C.byref(cnt), out)
     o = np.array(out[:], np.float64)

@@ -108,6 +108,38 @@ def masked_mean(d, max_dist):
     return float(s.mean()) if len(s) else float("nan")
 
 
+def fixed_order_sum(terms):
+    """The device's fixed-order fp64 sum of `terms` (n,) or (n, Q), column by column -> (Q,).
+    256 workgroups of 256 threads: thread t of workgroup b adds the elements b * 256 + t + m * 65536 in m order, starting
+    from +0.0; the 64 lanes of a wave fold by halves (lane l += lane l + o for o = 32, 16, 8, 4, 2, 1); the four waves add
+    as (w0 + w1) + (w2 + w3); the 256 workgroup sums are added in workgroup order, starting from +0.0.  An element the
+    device skips is a row of +0.0 here: no running sum is ever -0.0 (they start at +0.0), so adding +0.0 changes no bit."""
+    t = np.asarray(terms, np.float64)
+    t = t[:, None] if t.ndim == 1 else t
+    n, Q = t.shape
+    padded = np.zeros((max(-(-n // 65536), 1) * 65536, Q))
+    padded[:n] = t
+    acc = np.zeros((256, 256, Q))  # [workgroup, thread]
+    for step in padded.reshape(-1, 256, 256, Q):
+        acc = acc + step
+    lanes = acc.reshape(256, 4, 64, Q)  # [workgroup, wave, lane]
+    for o in (32, 16, 8, 4, 2, 1):
+        lanes = lanes[:, :, :o] + lanes[:, :, o:2 * o]
+    w = lanes[:, :, 0]
+    part = (w[:, 0] + w[:, 1]) + (w[:, 2] + w[:, 3])
+    s = np.zeros(Q)
+    for b in range(256):
+        s = s + part[b]
+    return s
+
+
+def masked_sum_fixed_order(d, max_dist):
+    """gs2m_eval_masked_mean's two outputs: the fixed-order sum of the entries < max_dist and their count."""
+    d = np.asarray(d, np.float64).reshape(-1)
+    ok = d < max_dist
+    return float(fixed_order_sum(np.where(ok, d, 0.0))[0]), int(ok.sum())
+
+
 def vis_colors(n, index, dist, max_dist, vis_dist):
     col = np.tile(np.array([[0.0, 0.0, 1.0]]), (n, 1))
     d = np.asarray(dist, np.float64).reshape(-1, 1)

@@ -89,6 +89,39 @@ def test_steps_match_the_restatement(seed, n_tris, scale, thresh):
     assert np.array_equal(E.above_plane(stl, P).cpu().numpy() != 0, R.above_plane(stl, P))
 
 
+def _bits(a):
+    return np.asarray(a, np.float64).view(np.uint64)
+
+
+# n = 0; below one workgroup; not a multiple of 256; beyond 256 x 256, so that a thread adds more than one element
+FIXED_ORDER_SIZES = [0, 100, 1000, 70001, 200000]
+
+
+@pytest.mark.parametrize("n", FIXED_ORDER_SIZES)
+def test_masked_mean_sums_in_the_fixed_order(n):
+    """The sum and the count of gs2m_eval_masked_mean are, to the bit, those of the numpy restatement of the fixed order."""
+    import ctypes as C
+    import gs2m_native as N
+    rng = np.random.default_rng(n)
+    md = 20.0
+    d = rng.uniform(0, 25, n) * 10.0 ** rng.uniform(-9, 0, n)  # magnitudes apart: the order of the additions shows
+    d[rng.random(n) < 0.1] = np.inf
+    d[rng.random(n) < 0.05] = md
+    dev = torch.device("cuda")
+    t = torch.as_tensor(d).to(dev)
+    wb = C.c_longlong()
+    N.check(N.lib().gs2m_eval_scan_workspace_bytes(0, C.byref(wb)), "gs2m_eval_scan_workspace_bytes")
+    ws = torch.empty(wb.value, dtype=torch.uint8, device=dev)
+    tot, cnt = C.c_double(), C.c_longlong()
+    N.launch("gs2m_eval_masked_mean", dev, n, N.ptr(t), md, N.ptr(ws), C.byref(tot), C.byref(cnt))
+    want, want_n = R.masked_sum_fixed_order(d, md)
+    print("masked mean: n", n, "count", cnt.value, want_n, "sum", tot.value.hex(), want.hex(), "numpy's sum", float(d[d < md].sum()).hex())
+    assert cnt.value == want_n
+    assert _bits(tot.value) == _bits(want)
+    m, c = E.masked_mean(d, md)
+    assert c == want_n and (_bits(m) == _bits(want / want_n) if want_n else math.isnan(m))
+
+
 def test_thinning_adversarial_orders():
     r = 0.2
     # a chain spaced 0.9 r visited in index order: every other point is kept, one decision per round at worst

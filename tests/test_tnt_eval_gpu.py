@@ -233,6 +233,26 @@ def test_one_icp_evaluation():
         E.icp_moments(src, tgt[: widx.max()], stale)
 
 
+# n = 0; below one workgroup; not a multiple of 256; beyond 256 x 256, so that a thread adds more than one pair
+@pytest.mark.parametrize("n", [0, 100, 1000, 70001, 200000])
+def test_icp_moments_sum_in_the_fixed_order(n):
+    """All 17 outputs and the count of gs2m_tnt_icp_moments are, to the bit, those of the numpy restatement of the fixed order."""
+    rng = np.random.default_rng(n)
+    nt = 5000
+    tgt = rng.normal(0, 1, (nt, 3)) * 10.0 ** rng.uniform(-3, 1, (nt, 1)) + np.array([3.0, -1.0, 0.5])
+    idx = rng.integers(0, nt, n)
+    idx[rng.random(n) < 0.2] = -1  # queries without a partner
+    src = tgt[idx] + rng.normal(0, 0.05, (n, 3))
+    m = E.icp_moments(src, tgt, idx)
+    got = np.concatenate([[m["sum_d2"]], m["mx"], m["my"], m["sigma"].ravel(), [m["sx2"]]])
+    c, want = R.icp_moments_fixed_order(src, tgt, idx)
+    w = R.icp_moments(src, tgt, idx)
+    loose = np.concatenate([[w["sum_d2"]], w["mx"], w["my"], w["sigma"].ravel(), [w["sx2"]]])
+    print("icp moments: n", n, "count", m["c"], c, "outputs that differ from numpy's own sums:", int((got != loose).sum()))
+    assert m["c"] == c == int((idx >= 0).sum())
+    assert np.array_equal(got.view(np.uint64), want.view(np.uint64)), np.nonzero(got != want)[0]
+
+
 def test_icp_and_registration_end_to_end():
     sc = icp_scene()
     src = R.mesh_points(sc["V"], sc["F"])

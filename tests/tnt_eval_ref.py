@@ -8,6 +8,8 @@ import math
 
 import numpy as np
 
+from dtu_eval_ref import fixed_order_sum
+
 AXES = {"X": (1, 2, 0), "Y": (0, 2, 1), "Z": (0, 1, 2)}
 MAX_POINT_NUMBER = 4e6
 
@@ -139,6 +141,34 @@ def icp_moments(source, targets, index, exact=False):
     sx2 = float(_sum(n2, exact)) / c
     terms = np.concatenate([[d2.sum()], np.abs(x).sum(0), np.abs(y).sum(0), np.abs(prod).reshape(-1, 9).sum(0), [n2.sum()]])
     return {"c": c, "sum_d2": float(_sum(d2, exact)), "mx": mx, "my": my, "sigma": sigma, "sx2": sx2, "terms": terms}
+
+
+def icp_moments_fixed_order(source, targets, index):
+    """gs2m_tnt_icp_moments as the device and its host part compute it, to the bit.  -> (count, out (17,)): out = [sum_d2,
+    mx (3), my (3), sigma (9, rows y, columns x), sx2].  Two passes of `fixed_order_sum` over the pairs with index >= 0: first
+    d^2 = (dx dx + dy dy) + dz dz, x and y, whose sums the host divides by the count; then the products about those means,
+    divided by the count as well.  Every output is 0 when no pair has index >= 0."""
+    x = np.asarray(source, np.float64).reshape(-1, 3)
+    t = np.asarray(targets, np.float64).reshape(-1, 3)
+    index = np.asarray(index, np.int64).reshape(-1)
+    ok = index >= 0
+    c = int(ok.sum())
+    out = np.zeros(17)
+    if c == 0:
+        return 0, out
+    y = t[np.where(ok, index, 0)]
+    keep = ok[:, None]
+    d = x - y
+    d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+    s0 = fixed_order_sum(np.where(keep, np.concatenate([d2[:, None], x, y], 1), 0.0))
+    cd = np.float64(c)
+    out[0] = s0[0]
+    out[1:7] = s0[1:7] / cd
+    a, b = x - out[1:4], y - out[4:7]
+    prod = (b[:, :, None] * a[:, None, :]).reshape(-1, 9)
+    n2 = (a[:, 0] * a[:, 0] + a[:, 1] * a[:, 1]) + a[:, 2] * a[:, 2]
+    out[7:17] = fixed_order_sum(np.where(keep, np.concatenate([prod, n2[:, None]], 1), 0.0)) / cd
+    return c, out
 
 
 def umeyama_update(m):

@@ -229,8 +229,8 @@ ImageState gs2m_carve_image(char* base, size_t N, size_t tiles);
 
 // hand-written onesweep radix sort of (u32 key, u32 value) pairs (radix_sort.hip).  Users: the stable sort of the emitted
 // instances by tile (api.hip: digit histogram from emit_kernel through ext_hist, tile ranges out through range_raw), distCUDA2's
-// Morton order (knn.hip), the grid buckets of the mesh evaluations (mesh_eval.hip) and the voxel downsample's keys, low word then
-// high word (tnt_eval.hip).
+// Morton order (knn.hip), the grid buckets of the mesh evaluations (mesh_eval.hip), the voxel downsample's keys, low word then
+// high word (tnt_eval.hip), and the edge pairs of the triangle clusters, hi id then lo id (mesh_post.hip).
 size_t gs2m_radix_temp_bytes(size_t n, int total_bits);
 hipError_t gs2m_radix_sort_pairs(void* temp, size_t temp_bytes, const uint32_t* kin, const uint32_t* vin, uint32_t* kA,
                                  uint32_t* vA, uint32_t* kB, uint32_t* vB, size_t n, int total_bits, bool prezeroed, hipStream_t s,

@@ -1,4 +1,4 @@
-// Host and device primitives shared by the mesh units: tsdf.hip, mesh_eval.hip and tnt_eval.hip.
+// Host and device primitives shared by the mesh units: tsdf.hip, mesh_eval.hip, tnt_eval.hip and mesh_post.hip.
 #pragma once
 #include <initializer_list>
 #include "common.h"

@@ -3,8 +3,9 @@
 Drop-ins for the three functions the reference's render.py imports from utils/mesh_utils.py -- `fuse_depths`,
 `post_process_mesh`, `write_mesh` -- and the volume behind them, `TSDFVolume`, which follows Open3D's legacy
 ScalableTSDFVolume as DESIGN.md §9 writes it down (16^3-voxel blocks, allocation from the stride-4 back-projected depth,
-per-voxel projective TSDF, marching cubes with shared vertices).  Fusion and extraction run in HIP kernels; the volume's
-memory is torch tensors owned here (the library allocates nothing).  The blocks live in a dense block-index table over a
+per-voxel projective TSDF, marching cubes with shared vertices).  Fusion, extraction and the post-processing
+(`post_process_mesh_gpu`: csrc/mesh_post.hip on a `DeviceMesh`; `post_process_mesh` is its host statement) run in HIP kernels;
+the memory is torch tensors owned here (the library allocates nothing).  The blocks live in a dense block-index table over a
 box fixed at creation: `fuse_depths` derives it from the depth maps (or `bounds`).
 
     python gs-2m_amd/gs2m_mesh.py --ply point_cloud.ply -s SCENE -o OUT [--dtu | --tnt [--scene NAME]]
@@ -42,6 +43,36 @@ class TriangleMesh:
                               else np.ascontiguousarray(vertex_colors, dtype=np.float32))
 
 
+class DeviceMesh:
+    """A TriangleMesh whose arrays are torch tensors on one device: vertices (V, 3) float32, triangles (F, 3) int32,
+    vertex_colors (V, 3) float32.  What extraction hands to the post-processing without a host round trip."""
+
+    def __init__(self, vertices, triangles, vertex_colors=None):
+        self.vertices = torch.as_tensor(vertices).to(torch.float32).reshape(-1, 3).contiguous()
+        dev = self.vertices.device
+        self.triangles = torch.as_tensor(triangles).to(torch.int32).reshape(-1, 3).contiguous()
+        self.vertex_colors = (torch.zeros_like(self.vertices) if vertex_colors is None
+                              else torch.as_tensor(vertex_colors).to(torch.float32).reshape(-1, 3).contiguous())
+        if self.triangles.device != dev or self.vertex_colors.device != dev:
+            raise ValueError(f"gs2m_mesh: DeviceMesh arrays on {dev}, {self.triangles.device} and {self.vertex_colors.device}")
+        if len(self.vertex_colors) != len(self.vertices):
+            raise ValueError(f"gs2m_mesh: {len(self.vertex_colors)} colours for {len(self.vertices)} vertices")
+
+    @property
+    def device(self):
+        return self.vertices.device
+
+    @classmethod
+    def from_mesh(cls, mesh, device="cuda"):
+        dev = torch.device(device)
+        return cls(torch.from_numpy(np.asarray(mesh.vertices, dtype=np.float32)).to(dev),
+                   torch.from_numpy(np.asarray(mesh.triangles, dtype=np.int32)).to(dev),
+                   torch.from_numpy(np.asarray(mesh.vertex_colors, dtype=np.float32)).to(dev))
+
+    def cpu(self):
+        return TriangleMesh(self.vertices.cpu().numpy(), self.triangles.cpu().numpy(), self.vertex_colors.cpu().numpy())
+
+
 _ptr = N.ptr
 
 
@@ -60,8 +91,9 @@ class TSDFVolume:
     """A TSDF volume over the world box [domain_min, domain_max] (cut to whole blocks of 16 * voxel_length).
 
     integrate(depth (H, W), color (H, W, 3) uint8 or float in [0, 1], fx, fy, cx, cy, w2c (4, 4)) fuses one view;
-    extract_triangle_mesh() runs marching cubes.  Depths <= 0 or above `depth_trunc` are empty.  `ignored_points`: points of
-    the integrated views whose trunc box left the domain (counted, not fused)."""
+    extract_triangle_mesh() runs marching cubes (to_host=False: the mesh stays on the device, a DeviceMesh).  Depths <= 0 or
+    above `depth_trunc` are empty.  `ignored_points`: points of the integrated views whose trunc box left the domain (counted,
+    not fused)."""
 
     def __init__(self, voxel_length, sdf_trunc, depth_trunc, domain_min, domain_max, device="cuda", capacity=256):
         self.voxel = float(np.float32(voxel_length))
@@ -134,10 +166,10 @@ class TSDFVolume:
                  int(info[1]), _ptr(self.touched), _ptr(self.block_coords), _ptr(self.tsdf), _ptr(self.weight), _ptr(self.color))
         return int(info[1])
 
-    def extract_triangle_mesh(self):
+    def extract_triangle_mesh(self, to_host=True):
         n = self.n_blocks
         if n == 0:
-            return TriangleMesh()
+            return TriangleMesh() if to_host else DeviceMesh.from_mesh(TriangleMesh(), self.device)
         ws = workspace_for("gs2m_tsdf_workspace_bytes", self.device, self._dom, n, only=1)
         tot = (C.c_longlong * 2)()
         N.launch("gs2m_tsdf_mesh_count", self.device, self._dom, n, _ptr(self.index), _ptr(self.block_coords), _ptr(self.tsdf),
@@ -148,6 +180,8 @@ class TSDFVolume:
         tris = torch.empty((max(F, 1), 3), dtype=torch.int32, device=self.device)
         N.launch("gs2m_tsdf_mesh_emit", self.device, self._dom, self.voxel, n, _ptr(self.index), _ptr(self.block_coords), _ptr(self.tsdf),
                  _ptr(self.color), _ptr(ws), V, F, _ptr(verts), _ptr(cols), _ptr(tris))
+        if not to_host:
+            return DeviceMesh(verts[:V], tris[:F], cols[:V])
         return TriangleMesh(verts[:V].cpu().numpy(), tris[:F].cpu().numpy(), cols[:V].cpu().numpy())
 
     def state_arrays(self):
@@ -282,12 +316,89 @@ def post_process_mesh(mesh, cluster_to_keep=1):
     return TriangleMesh(np.asarray(mesh.vertices)[used], t, np.asarray(mesh.vertex_colors)[used])
 
 
+def _post_device(mesh, device, who):
+    """The DeviceMesh the device post-processing works on (a TriangleMesh is copied to `device`).  No CPU path."""
+    dm = mesh if isinstance(mesh, DeviceMesh) else None
+    dev = dm.device if dm is not None else torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError(f"{who}: the mesh must be on a HIP device, got `{dev}`; there is no CPU path (post_process_mesh and "
+                           "cluster_connected_triangles are the host functions)")
+    return dm if dm is not None else DeviceMesh.from_mesh(mesh, dev)
+
+
+def post_workspace_bytes(n_vertices, n_triangles):
+    """-> (cluster workspace, compaction workspace) in bytes, as the library sizes them."""
+    a, b = C.c_longlong(), C.c_longlong()
+    N.check(N.lib().gs2m_mesh_post_workspace_bytes(int(n_vertices), int(n_triangles), C.byref(a), C.byref(b)), "gs2m_mesh_post_workspace_bytes")
+    return a.value, b.value
+
+
+def _cluster_device(triangles, n_vertices):
+    """triangles (F, 3) int32 on a HIP device -> (tri_cluster int32 (F,), cluster_size int32 (F,), C)."""
+    dev, F = triangles.device, len(triangles)
+    with N.device_guard(dev):
+        lab = torch.empty(F, dtype=torch.int32, device=dev)
+        size = torch.empty(F, dtype=torch.int32, device=dev)
+    if F == 0:
+        return lab, size, 0
+    ws = workspace_for("gs2m_mesh_post_workspace_bytes", dev, int(n_vertices), F, only=0)
+    n = C.c_longlong()
+    N.launch("gs2m_mesh_cluster_triangles", dev, int(n_vertices), F, _ptr(triangles), _ptr(ws), _ptr(lab), _ptr(size), C.byref(n))
+    return lab, size, int(n.value)
+
+
+def cluster_connected_triangles_gpu(mesh_or_triangles, n_vertices=None, device="cuda"):
+    """cluster_connected_triangles on the device (csrc/mesh_post.hip).  A TriangleMesh, a DeviceMesh or a (F, 3) array of
+    triangles (`n_vertices`: the vertex count they index; default: the largest id + 1).  -> (cluster index per triangle,
+    triangles per cluster) as int32 tensors; clusters are numbered by increasing smallest triangle index."""
+    who = "cluster_connected_triangles_gpu"
+    if isinstance(mesh_or_triangles, (TriangleMesh, DeviceMesh)):
+        dm = _post_device(mesh_or_triangles, device, who)
+        tris, nv = dm.triangles, len(dm.vertices) if n_vertices is None else int(n_vertices)
+    else:
+        t = mesh_or_triangles
+        dev = t.device if torch.is_tensor(t) else torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError(f"{who}: the triangles must be on a HIP device, got `{dev}`; there is no CPU path")
+        tris = torch.as_tensor(t).to(dev, torch.int32).reshape(-1, 3).contiguous()
+        nv = int(n_vertices) if n_vertices is not None else (int(tris.max()) + 1 if len(tris) else 0)
+    lab, size, n = _cluster_device(tris, nv)
+    return lab, size[:n].clone()
+
+
+def post_process_mesh_gpu(mesh, cluster_to_keep=1, device="cuda"):
+    """post_process_mesh on the device: the same arrays, element for element.  A DeviceMesh is processed where it is and a
+    DeviceMesh comes back; a TriangleMesh goes to `device` and comes back as a TriangleMesh.  One scalar (the size bound)
+    and the three counts are read back; the mesh is not."""
+    dm = _post_device(mesh, device, "post_process_mesh_gpu")
+    dev, V, F = dm.device, len(dm.vertices), len(dm.triangles)
+    if F == 0:
+        out = DeviceMesh(dm.vertices[:0], dm.triangles[:0], dm.vertex_colors[:0])
+    else:
+        lab, size, n = _cluster_device(dm.triangles, V)
+        nth = int(torch.sort(size[:n]).values[-min(int(cluster_to_keep), n)])  # numpy's indexing, as the host function's
+        with N.device_guard(dev):
+            keep = torch.empty(F, dtype=torch.uint8, device=dev)
+            ov, oc, ot = torch.empty_like(dm.vertices), torch.empty_like(dm.vertex_colors), torch.empty_like(dm.triangles)
+        N.launch("gs2m_mesh_keep_clusters", dev, F, _ptr(lab), _ptr(size), max(nth, 50), _ptr(keep))
+        ws = workspace_for("gs2m_mesh_post_workspace_bytes", dev, V, F, only=1)
+        tot = (C.c_longlong * 2)()
+        N.launch("gs2m_mesh_compact", dev, V, F, _ptr(dm.vertices), _ptr(dm.vertex_colors), _ptr(dm.triangles), _ptr(keep), _ptr(ws),
+                 _ptr(ov), _ptr(oc), _ptr(ot), tot)
+        nv, nt = int(tot[0]), int(tot[1])
+        out = DeviceMesh(ov[:nv].clone(), ot[:nt].clone(), oc[:nv].clone())  # clones: the input-sized buffers go
+    return out if isinstance(mesh, DeviceMesh) else out.cpu()
+
+
 _PLY_VERTEX = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
 _PLY_FACE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
 
 
 def write_mesh(file, mesh):
-    """Binary little-endian PLY: float x y z, uchar red green blue (colour * 255 rounded to nearest), int32 face lists."""
+    """Binary little-endian PLY: float x y z, uchar red green blue (colour * 255 rounded to nearest), int32 face lists.
+    A DeviceMesh is read back once."""
+    if isinstance(mesh, DeviceMesh):
+        mesh = mesh.cpu()
     v = np.asarray(mesh.vertices, dtype=np.float32).reshape(-1, 3)
     c = np.asarray(mesh.vertex_colors, dtype=np.float64).reshape(-1, 3)
     t = np.asarray(mesh.triangles, dtype=np.int32).reshape(-1, 3)
@@ -377,9 +488,11 @@ def render_views(gaussians, views, render_dir, device="cuda"):
 
 
 def extract_mesh(gaussians, views, cameras_extent, out_dir, max_depth=-1.0, voxel_size=-1.0, sdf_trunc=-1.0, num_clusters=1,
-                 bounds=None, device="cuda"):
-    """render.py's --extract_mesh path: render, fuse, extract; writes out_dir/{config.json, tsdf_mesh.ply, tsdf_post.ply}.
-    -> (raw mesh, post-processed mesh)."""
+                 bounds=None, device="cuda", host_post=False):
+    """render.py's --extract_mesh path: render, fuse, extract, post-process; writes out_dir/{config.json, tsdf_mesh.ply,
+    tsdf_post.ply}.  The mesh stays on the device from extraction through post_process_mesh_gpu; `host_post`: read it back
+    and run the host post_process_mesh instead (the same two files, byte for byte).  -> (raw mesh, post-processed mesh),
+    host TriangleMesh both."""
     os.makedirs(out_dir, exist_ok=True)
     max_depth = max_depth if max_depth > 0 else 2.0 * cameras_extent
     voxel_size = voxel_size if voxel_size > 0 else max_depth / 1024.0
@@ -389,9 +502,13 @@ def extract_mesh(gaussians, views, cameras_extent, out_dir, max_depth=-1.0, voxe
     render_dir = os.path.join(out_dir, "renders")
     depths = render_views(gaussians, views, render_dir, device)
     vol = fuse_depths(depths, views, render_dir, max_depth, voxel_size, sdf_trunc, bounds, device=device)
-    mesh = vol.extract_triangle_mesh()
+    if host_post:
+        mesh = vol.extract_triangle_mesh()
+        post = post_process_mesh(mesh, num_clusters)
+    else:
+        on_device = vol.extract_triangle_mesh(to_host=False)
+        mesh, post = on_device.cpu(), post_process_mesh_gpu(on_device, num_clusters).cpu()
     write_mesh(os.path.join(out_dir, "tsdf_mesh.ply"), mesh)
-    post = post_process_mesh(mesh, num_clusters)
     write_mesh(os.path.join(out_dir, "tsdf_post.ply"), post)
     print(f"[>] {len(mesh.vertices)} vertices / {len(mesh.triangles)} triangles raw, {len(post.vertices)} / {len(post.triangles)} "
           f"post-processed; {vol.n_blocks} blocks, {vol.ignored_points} points outside the domain -> {out_dir}")
@@ -421,6 +538,7 @@ def parse_args(argv=None):
                          "max(aabb_range extent) / 2048 and bounds = aabb_range from the dataset's transforms.json, else 0.002; 1 cluster")
     ap.add_argument("--scene", default="", help="--tnt: the scene's name (default: the output directory's name)")
     ap.add_argument("--sh-degree", type=int, default=3)
+    ap.add_argument("--host-post", action="store_true", help="post-process on the host (numpy / scipy) instead of the device")
     a = ap.parse_args(argv)
     if a.dtu and a.tnt:
         ap.error("--dtu and --tnt are two presets: choose one")
@@ -453,7 +571,8 @@ def main(argv=None):
             cams = cams[::8]
     model = GaussianModel(a.sh_degree)
     model.load_ply(a.ply)
-    extract_mesh(model, cams, extent, a.output, a.max_depth, a.voxel_size, a.sdf_trunc, a.num_clusters, bounds)
+    extract_mesh(model, cams, extent, a.output, a.max_depth, a.voxel_size, a.sdf_trunc, a.num_clusters, bounds,
+                 host_post=a.host_post)
 
 
 if __name__ == "__main__":

@@ -134,6 +134,10 @@ SIGNATURES = {
     "gs2m_tsdf_mesh_count": (i, [p, i, p, p, p, p, p, p, s]),
     "gs2m_tsdf_mesh_emit": (i, [p, f, i, p, p, p, p, p, ll, ll, p, p, p, s]),
     "gs2m_tsdf_block_coords": (i, [i, p, p, s]),
+    "gs2m_mesh_post_workspace_bytes": (i, [ll, ll, p, p]),
+    "gs2m_mesh_cluster_triangles": (i, [ll, ll, p, p, p, p, p, s]),
+    "gs2m_mesh_keep_clusters": (i, [ll, p, p, i, p, s]),
+    "gs2m_mesh_compact": (i, [ll, ll, p, p, p, p, p, p, p, p, p, s]),
     # include/gs2m_eval.h
     "gs2m_eval_transform": (i, [ll, p, d, p, p, s]),
     "gs2m_eval_sample_workspace_bytes": (i, [ll, ll, p, p]),

@@ -1,4 +1,5 @@
-/* gs2m_mesh.h -- C ABI of the TSDF depth fusion and marching-cubes mesh extraction (tsdf.hip), part of libgs2m_raster.so.
+/* gs2m_mesh.h -- C ABI of the TSDF depth fusion and marching-cubes mesh extraction (tsdf.hip) and of the mesh
+ * post-processing (mesh_post.hip; its contract: the block further down), part of libgs2m_raster.so.
  *
  * The reference extracts its mesh with Open3D's CPU ScalableTSDFVolume (utils/mesh_utils.py: fuse_depths,
  * render.py --extract_mesh).  This is that pipeline as DESIGN.md §9 writes it down; the contract, restated:
@@ -73,6 +74,53 @@ int gs2m_tsdf_mesh_emit(const int* dom, float voxel, int n_blocks, const int* in
 
 /* Tests: the block coordinates of the `n_blocks` slots in use, copied to HOST int[n_blocks * 3]. */
 int gs2m_tsdf_block_coords(int n_blocks, const int* block_coords, int* host_coords, void* stream);
+
+/* ---- post-processing (mesh_post.hip) -------------------------------------------------------------------------------
+ *
+ * Open3D's cluster_connected_triangles + remove_triangles_by_mask + remove_unreferenced_vertices +
+ * remove_degenerate_triangles as the reference's post_process_mesh strings them together; the contract:
+ *
+ *   Edges       triangle t has the three unordered vertex pairs (min, max) of (v0, v1), (v1, v2), (v2, v0); a degenerate
+ *               triangle contributes its pairs as they come, (a, a) included.
+ *   Connection  two triangles are connected when they have an equal pair (orientation does not matter; an edge with three
+ *               or more triangles connects them all; sharing only a vertex is no connection).  Clusters are the connected
+ *               components.
+ *   Numbering   clusters are numbered 0 .. C - 1 by increasing smallest triangle index; tri_cluster[t] is the number,
+ *               cluster_size[c] the triangle count: both a pure function of `triangles`.
+ *   Keep        keep[t] = cluster_size[tri_cluster[t]] >= min_size (the caller chooses min_size: max(n-th largest, 50)).
+ *   Compaction  a vertex survives when a kept triangle references it (a degenerate kept triangle counts); survivors keep
+ *               their order and are renumbered densely, their colours move with them; a triangle is emitted when it is
+ *               kept and its three ids are pairwise different, in input order, with the new ids.
+ *   Limits      3 F <= 0xFFFFFFF0 and V < 2^31 (else GS2M_ERR_UNSUPPORTED); vertex ids are int32.  A triangle (kept or
+ *               not) with an id outside [0, V) makes cluster_triangles and compact return GS2M_ERR_INVALID_ARG; no kernel
+ *               indexes with an id it has not tested.  F = 0 and V = 0 are valid and launch nothing.
+ *
+ * Integer atomics only where their order cannot change the result (the union-find hooks the larger root under the smaller,
+ * so a cluster's root is its smallest triangle; integer counts): two runs are bitwise identical.
+ * Workspaces (the caller's, as everything here): the cluster workspace is 104 bytes per triangle -- eight u32 arrays over
+ * the 3 F edge slots (the pairs, the second sort's input, the sort's ping-pong buffers) and a u64 per triangle for the scan
+ * -- plus the radix sort's look-back rows, 3.1 bytes per triangle: 107.1 in all, 3.53 GB at F = 33 M; the compaction
+ * workspace is 9 bytes per vertex and 8 per triangle (0.42 GB at V = 17 M, F = 33 M).  tri_cluster serves as the union-find's parent array during the call. */
+
+/* HOST outputs; either pointer may be NULL (not asked for). */
+int gs2m_mesh_post_workspace_bytes(long long n_vertices, long long n_triangles, long long* cluster_bytes,
+                                   long long* compact_bytes);
+
+/* triangles (F, 3) int32; ws: the cluster workspace.  tri_cluster int[F], cluster_size int[F] (the first C valid, the rest
+ * 0), n_clusters HOST = C; waits for the stream. */
+int gs2m_mesh_cluster_triangles(long long n_vertices, long long n_triangles, const int* triangles, void* ws, int* tri_cluster,
+                                int* cluster_size, long long* n_clusters, void* stream);
+
+/* keep[t] = cluster_size[tri_cluster[t]] >= min_size (0 for a number outside [0, F)); cluster_size int[F]. */
+int gs2m_mesh_keep_clusters(long long n_triangles, const int* tri_cluster, const int* cluster_size, int min_size,
+                            unsigned char* keep, void* stream);
+
+/* ws: the compaction workspace.  colors / out_colors may be NULL.  out_vertices, out_colors (V, 3) and out_triangles (F, 3)
+ * are sized by the caller for the input's counts; totals (HOST long long[2]) = surviving vertices, emitted triangles: the
+ * rows written.  Waits for the stream. */
+int gs2m_mesh_compact(long long n_vertices, long long n_triangles, const float* vertices, const float* colors,
+                      const int* triangles, const unsigned char* keep, void* ws, float* out_vertices, float* out_colors,
+                      int* out_triangles, long long* totals, void* stream);
 
 #ifdef __cplusplus
 }

@@ -606,4 +606,47 @@ int gs2m_debug_tile_sort(int tiles, const unsigned* ranges_raw, unsigned* ranges
     return GS2M_OK;
 }
 
+// Test hooks (tests/test_radix_sort_gpu.py): radix_sort.hip on caller-made pairs.  Nothing is allocated here: the caller owns every
+// buffer (and can put guard words around each).
+int gs2m_debug_radix_temp_bytes(long long n, int total_bits, unsigned long long* bytes) {
+    if (n < 0 || !bytes) return GS2M_ERR_INVALID_ARG;
+    *bytes = (unsigned long long)gs2m_radix_temp_bytes((size_t)n, total_bits);
+    return GS2M_OK;
+}
+
+int gs2m_debug_radix_plan(int total_bits, int* npass, int* bits4, int* shift4) {
+    if (!npass || !bits4 || !shift4) return GS2M_ERR_INVALID_ARG;
+    gs2m_radix_plan(total_bits, npass, bits4, shift4);
+    return GS2M_OK;
+}
+
+int gs2m_debug_radix_sort(long long n, int total_bits, const unsigned* kin, const unsigned* vin, unsigned* kA, unsigned* vA, unsigned* kB,
+                          unsigned* vB, void* temp, unsigned long long temp_bytes, int prezeroed, unsigned* range_raw, const unsigned* ext_hist,
+                          void* stream_) {
+    if (n < 0 || (n > 0 && (!kin || !kA || !vA || !kB || !vB || !temp))) return GS2M_ERR_INVALID_ARG;
+    const hipError_t e = gs2m_radix_sort_pairs(temp, (size_t)temp_bytes, kin, vin, kA, vA, kB, vB, (size_t)n, total_bits, prezeroed != 0,
+                                               (hipStream_t)stream_, range_raw, ext_hist);
+    return e == hipErrorInvalidValue ? GS2M_ERR_INVALID_ARG : gs2m_status(e);
+}
+
+// Test hook (tests/test_block_scans_gpu.py): blockscan_kernel, then rowscan_kernel, through the launchers of a frame on caller-made
+// count arrays of n_blocks / n_waves words (a frame has ceil(P / 256) and ceil(P / 64)).  `counters`: 64 words; `landing_out`: the
+// GS2M_LAND_* words, here in device memory (8-byte aligned: {num_rendered, heavy units} leave in one store).
+int gs2m_debug_block_scans(long long n_blocks, const unsigned* block_tt, const unsigned* block_hu, unsigned* block_pref, unsigned* block_hupref,
+                           long long n_waves, const unsigned* wave_rows, unsigned* wave_rowbase, unsigned* counters, unsigned* landing_out,
+                           void* stream_) {
+    if (n_blocks < 1 || n_blocks > 0x7FFFFFFF / 256 || n_waves < 1 || n_waves > 0x7FFFFFFF / 64) return GS2M_ERR_INVALID_ARG;
+    if (!block_tt || !block_hu || !block_pref || !block_hupref || !wave_rows || !wave_rowbase || !counters || !landing_out) return GS2M_ERR_INVALID_ARG;
+    if ((uintptr_t)landing_out & 7) return GS2M_ERR_INVALID_ARG;
+    GeomState g = {};
+    g.block_tt = const_cast<uint32_t*>(block_tt); g.block_hu = const_cast<uint32_t*>(block_hu);
+    g.block_pref = block_pref; g.block_hupref = block_hupref;
+    g.wave_rows = const_cast<uint32_t*>(wave_rows); g.wave_rowbase = wave_rowbase;
+    g.counters = counters;
+    gs2m_launch_blockscan((int)(n_blocks * 256), g, landing_out, (hipStream_t)stream_);  // (the launchers count in Gaussians)
+    gs2m_launch_rowscan((int)(n_waves * 64), g, landing_out, (hipStream_t)stream_);
+    HIP_TRY(hipGetLastError());
+    return GS2M_OK;
+}
+
 }  // extern "C"

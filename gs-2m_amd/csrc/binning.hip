@@ -437,6 +437,10 @@ void gs2m_launch_emit(int P, int W, int H, int tiles_x, int tile_bits, const Geo
     if (heavy_units > 0u)
         emit_heavy_kernel<<<(heavy_units + 3u) / 4u, 256, 0, s>>>(heavy_units, W, H, tiles_x, g.rect, g.rec, g.depth_key, g.gauss_rows, b.keys_unsorted, b.e_rec,
                                                                   b.hrec, g.tile_hist, npass, hbits, hshift);
+    gs2m_launch_rowscan(P, g, landing, s);
+}
+
+void gs2m_launch_rowscan(int P, const GeomState& g, uint32_t* landing, hipStream_t s) {
     const size_t nw = (size_t)(P + 63) / 64;
     rowscan_kernel<<<(unsigned)((nw + 1023) / 1024 > 0 ? (nw + 1023) / 1024 : 1), 1024, 0, s>>>(g.wave_rows, nw, g.wave_rowbase, g.counters, landing);
 }

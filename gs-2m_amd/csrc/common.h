@@ -262,8 +262,10 @@ void gs2m_launch_preprocess(int P, int D, int M, const float* means3D, const flo
                             float tan_fovx, float tan_fovy, float focal_x, float focal_y, int tiles_x, int tiles_y,
                             int* radii, int* observe_zero, const GeomState& g, int shrink, const ZeroJobs& zero, hipStream_t s);
 // binning.hip: blockscan (publishes num_rendered; block prefixes of tiles_touched), emit (instances in index order: tile keys,
-// quadrant masks, gradient-row numbering, the tile sort's digit counts) + rowscan (first gradient row of every wave)
+// quadrant masks, gradient-row numbering, the tile sort's digit counts) + rowscan (first gradient row of every wave; launched by
+// gs2m_launch_emit behind its kernels, and on its own by the test hook gs2m_debug_block_scans)
 void gs2m_launch_blockscan(int P, const GeomState& g, uint32_t* landing, hipStream_t s);
+void gs2m_launch_rowscan(int P, const GeomState& g, uint32_t* landing, hipStream_t s);
 void gs2m_launch_emit(int P, int W, int H, int tiles_x, int tile_bits, const GeomState& g, const BinningState& b, uint32_t heavy_units,
                       uint32_t crowded, uint32_t* landing, const ZeroJobs& zero, hipStream_t s);
 // the blocks' heavy-unit counts once more with the crowded-wave rule off (the preprocess kernel counted them with it on)

@@ -150,6 +150,7 @@ __global__ void __launch_bounds__(RS_THREADS) rs_onesweep_kernel(
         val[k] = i < n ? (vals_in ? vals_in[i] : i) : 0u;  // vals_in == nullptr: the value is the index
     }
     const unsigned long long lt = (1ull << lane) - 1ull;
+    [[maybe_unused]] uint32_t run0 = 0;  // BITS == 0: keys of this wave ranked so far
 #pragma unroll
     for (int k = 0; k < RS_ITEMS; k++) {
         const bool valid = segbase + k * 64 + lane < n;
@@ -161,11 +162,20 @@ __global__ void __launch_bounds__(RS_THREADS) rs_onesweep_kernel(
             const unsigned long long bal = __builtin_amdgcn_ballot_w64(bit);
             peers &= bit ? bal : ~bal;
         }
-        const uint32_t old = s_cnt[wave][d];  // every peer reads before the leader's write (in-order LDS)
         const unsigned long long below = peers & lt;
-        rank[k] = old + (uint32_t)__popcll(below);
-        if (valid && below == 0ull) s_cnt[wave][d] = old + (uint32_t)__popcll(peers);
+        if constexpr (BITS == 0) {
+            // one digit: the wave's count so far is the same in every lane and stays in a register.  (Through the LDS counter
+            // the address would be the same constant in every step, and the compiler may then hand a lane that did not
+            // store its own earlier load again instead of the leader's sum.)
+            rank[k] = run0 + (uint32_t)__popcll(below);
+            run0 += (uint32_t)__popcll(peers);
+        } else {
+            const uint32_t old = s_cnt[wave][d];  // every peer reads before the leader's write (in-order LDS)
+            rank[k] = old + (uint32_t)__popcll(below);
+            if (valid && below == 0ull) s_cnt[wave][d] = old + (uint32_t)__popcll(peers);
+        }
     }
+    if (BITS == 0 && lane == 0) s_cnt[wave][0] = run0;
     gs2m_sync();
 
     // per digit: tile total, exclusive scans over the digits of (a) the tile totals (local layout) and
@@ -337,15 +347,20 @@ void gs2m_radix_zero_region(void* temp, size_t n, int total_bits, uint32_t** ptr
     *words = (gs2m_align_up(RS_MAXPASS * 256 * 4) + GS2M_ALIGN + (size_t)p.npass * status_rows(tiles) * 256 * 4) / 4;
 }
 
-// Sorts n pairs by key bits [0, total_bits), stable.  The input (kin, vin) is only read (vin may be
-// nullptr: values are then the indices 0..n-1); passes alternate between (kA, vA) and (kB, vB) and the
-// number of passes is even, so the result is in (kB, vB).
+// Sorts n pairs by key bits [0, total_bits), stable: key bits at and above total_bits are IGNORED (they travel with the key,
+// so the caller may keep a payload there), and pairs whose low total_bits bits are equal keep their input order.  The input
+// (kin, vin) is only read (vin may be nullptr: values are then the indices 0..n-1); passes alternate between (kA, vA) and
+// (kB, vB) and the number of passes is even, so the result is in (kB, vB).  A pass of 0 bits (total_bits == 1 has one) ranks
+// every key as digit 0 whatever the key holds: a stable copy.
+// n must stay below 2^30: the look-back's status words carry a count in 30 bits next to their two flag bits (VAL_MASK), and
+// a digit's count can be all of n; hipErrorInvalidValue beyond that, as for a temp that is too small -- nothing is launched.
 // range_raw (optional): per key {~first position, last position + 1} of its run in the output, as atomicMax targets the
-// caller has zeroed; written by the last pass.
+// caller has zeroed; written by the last pass, indexed by the FULL key: with range_raw every key must be below 2^total_bits.
 hipError_t gs2m_radix_sort_pairs(void* temp, size_t temp_bytes, const uint32_t* kin, const uint32_t* vin, uint32_t* kA,
                                  uint32_t* vA, uint32_t* kB, uint32_t* vB, size_t n, int total_bits, bool prezeroed, hipStream_t s,
                                  uint32_t* range_raw, const uint32_t* ext_hist) {
     if (n == 0) return hipSuccess;
+    if (n > (size_t)VAL_MASK) return hipErrorInvalidValue;
     const SortPlan p = make_plan(total_bits);
     const int tiles = (int)((n + RS_TILE - 1) / RS_TILE);
     if (temp_bytes < gs2m_radix_temp_bytes(n, total_bits)) return hipErrorInvalidValue;
@@ -372,9 +387,10 @@ hipError_t gs2m_radix_sort_pairs(void* temp, size_t temp_bytes, const uint32_t* 
         uint32_t* const rr = i == p.npass - 1 ? range_raw : nullptr;
         switch (p.bits[i]) {
 #define RS_CASE(B) case B: launch_pass<B>(ki, vi, ko, vo, (uint32_t)n, p.shift[i], gh, tickets + i, st, tiles, s, rr, hc); break;
-            RS_CASE(1) RS_CASE(2) RS_CASE(3) RS_CASE(4) RS_CASE(5) RS_CASE(6) RS_CASE(7) RS_CASE(8)
+            // 0 bits: one bin, every key is digit 0 (the histogram row counts all n keys there): a stable copy
+            RS_CASE(0) RS_CASE(1) RS_CASE(2) RS_CASE(3) RS_CASE(4) RS_CASE(5) RS_CASE(6) RS_CASE(7) RS_CASE(8)
 #undef RS_CASE
-            default: launch_pass<1>(ki, vi, ko, vo, (uint32_t)n, 31, gh, tickets + i, st, tiles, s, rr, hc); break;  // 0 bits: stable copy
+            default: return hipErrorInvalidValue;  // make_plan yields no other width
         }
         ki = ko;
         vi = vo;

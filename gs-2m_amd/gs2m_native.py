@@ -69,6 +69,10 @@ SIGNATURES = {
     "gs2m_raster_dense_rows": (ll, [ull]),
     "gs2m_raster_backward_rows_hint": (i, [ll]),
     "gs2m_debug_tile_sort": (i, [i, p, p, p, p, p, p, p, p, p, p, s]),
+    "gs2m_debug_radix_temp_bytes": (i, [ll, i, C.POINTER(ull)]),
+    "gs2m_debug_radix_plan": (i, [i, C.POINTER(i), C.POINTER(i), C.POINTER(i)]),
+    "gs2m_debug_radix_sort": (i, [ll, i, p, p, p, p, p, p, p, ull, i, p, p, s]),
+    "gs2m_debug_block_scans": (i, [ll, p, p, p, p, ll, p, p, p, p, s]),
     "gs2m_profile_mode": (i, [i]),
     "gs2m_profile_sampling": (i, [i]),
     "gs2m_profile_collect": (i, [C.POINTER(C.c_float), C.POINTER(C.c_int), i]),

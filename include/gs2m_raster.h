@@ -335,6 +335,26 @@ int gs2m_debug_tile_sort(int tiles, const unsigned* ranges_raw, unsigned* ranges
                          const unsigned* wave_rowbase, unsigned* point_list, unsigned* row_tmp,
                          unsigned* qlist, unsigned* qrow, unsigned* qcount, void* stream);
 
+/* Test hooks (tests/test_radix_sort_gpu.py): the stable radix sort of (u32 key, u32 value) pairs by key bits [0, total_bits) on
+ * caller-made pairs.  Bits at and above total_bits are ignored and travel with the key; n < 2^30.  Nothing is allocated: the
+ * caller owns every buffer.  The passes alternate between (kA, vA) and (kB, vB); the result is in (kB, vB).  vin may be NULL
+ * (values: 0..n-1).  temp: at least gs2m_debug_radix_temp_bytes bytes, zeroed by the caller when prezeroed != 0.  range_raw
+ * (optional, 2 x 2^total_bits zeroed words; every key below 2^total_bits): per key {~first, last + 1} of its run.  ext_hist
+ * (optional): the digit counts of every pass of the plan (row p at word 256 p), split over 8 copies 1024 words apart.
+ * GS2M_ERR_INVALID_ARG, and nothing launched, for an n out of range or a temp that is too small.
+ * gs2m_debug_radix_plan: the passes of a sort (2 or 4), their widths (0 .. 8 bits) and shifts, four entries each. */
+int gs2m_debug_radix_temp_bytes(long long n, int total_bits, unsigned long long* bytes);
+int gs2m_debug_radix_plan(int total_bits, int* npass, int* bits4, int* shift4);
+int gs2m_debug_radix_sort(long long n, int total_bits, const unsigned* kin, const unsigned* vin, unsigned* kA, unsigned* vA,
+                          unsigned* kB, unsigned* vB, void* temp, unsigned long long temp_bytes, int prezeroed,
+                          unsigned* range_raw, const unsigned* ext_hist, void* stream);
+/* Test hook (tests/test_block_scans_gpu.py): the two prefix-scan kernels of the binning stage on caller-made counts: exclusive
+ * prefixes of block_tt / block_hu (n_blocks words each) and of wave_rows (n_waves words, offset by the heavy units' rows);
+ * counters: 64 words; landing_out: 4 words of device memory, 8-byte aligned, written as the host-visible block of a forward is. */
+int gs2m_debug_block_scans(long long n_blocks, const unsigned* block_tt, const unsigned* block_hu, unsigned* block_pref,
+                           unsigned* block_hupref, long long n_waves, const unsigned* wave_rows, unsigned* wave_rowbase,
+                           unsigned* counters, unsigned* landing_out, void* stream);
+
 /* ---- per-stage timing with HIP events recorded on the launch stream (bench.py) ----
  * mode 0 = off, 1 = the two blend kernels only, 2 = every stage, 3 = the backward blend kernel only.  Setting the mode clears
  * the records.  gs2m_profile_collect waits for the recorded events and returns, per

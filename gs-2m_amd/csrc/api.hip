@@ -649,4 +649,51 @@ int gs2m_debug_block_scans(long long n_blocks, const unsigned* block_tt, const u
     return GS2M_OK;
 }
 
+// Test hooks (tests/test_blend_gpu.py): blend_fwd_q.hip / blend_bwd_q.hip through the launchers of a frame on caller-made quadrant
+// lists (layout: common.h, BinningState::qlist / qrow).  Nothing is allocated here: the caller owns every buffer.
+int gs2m_debug_blend_forward(int W, int H, int fc, const float* bg, const unsigned* ranges, const unsigned* qlist, const unsigned* qcount,
+                             const float* rec, float* out_color, float* out_buffer, float* final_T, unsigned* n_contrib, int* observe,
+                             unsigned* qlast, void* stream_) {
+    if (W < 1 || H < 1 || fc < 0 || fc > GS2M_NUM_FEATURES) return GS2M_ERR_INVALID_ARG;
+    if (!bg || !ranges || !qlist || !qcount || !rec || !out_color || !out_buffer || !final_T || !n_contrib || !observe || !qlast) return GS2M_ERR_INVALID_ARG;
+    GeomState g = {};
+    g.rec = reinterpret_cast<float4*>(const_cast<float*>(rec));
+    BinningState b = {};
+    b.qlist = reinterpret_cast<uint2*>(const_cast<unsigned*>(qlist));
+    ImageState im = {};
+    im.ranges = reinterpret_cast<uint2*>(const_cast<unsigned*>(ranges));
+    im.qcount = const_cast<uint32_t*>(qcount);
+    im.final_T = final_T; im.n_contrib = n_contrib; im.qlast = qlast;
+    gs2m_launch_blend_fwd_q(W, H, (W + GS2M_TILE - 1) / GS2M_TILE, (H + GS2M_TILE - 1) / GS2M_TILE, fc, bg, g, b, im, out_color, out_buffer, observe,
+                            (hipStream_t)stream_);
+    HIP_TRY(hipGetLastError());
+    return GS2M_OK;
+}
+
+int gs2m_debug_blend_backward(int W, int H, int fc, const float* bg, const unsigned* ranges, const unsigned* qlist, const unsigned* qcount,
+                              const unsigned* qrow, const unsigned* qlast, const float* rec, const float* final_T, const unsigned* n_contrib,
+                              const float* grad_color, const float* grad_buffer, float* rows, void* stream_) {
+    if (W < 1 || H < 1 || fc < 0 || fc > GS2M_NUM_FEATURES) return GS2M_ERR_INVALID_ARG;
+    if (!bg || !ranges || !qlist || !qcount || !qrow || !qlast || !rec || !final_T || !n_contrib || !grad_color || !grad_buffer || !rows) return GS2M_ERR_INVALID_ARG;
+    GeomState g = {};
+    g.rec = reinterpret_cast<float4*>(const_cast<float*>(rec));
+    BinningState b = {};
+    b.qlist = reinterpret_cast<uint2*>(const_cast<unsigned*>(qlist));
+    b.qrow = const_cast<uint32_t*>(qrow);
+    ImageState im = {};
+    im.ranges = reinterpret_cast<uint2*>(const_cast<unsigned*>(ranges));
+    im.qcount = const_cast<uint32_t*>(qcount);
+    im.qlast = const_cast<uint32_t*>(qlast);
+    im.final_T = const_cast<float*>(final_T); im.n_contrib = const_cast<uint32_t*>(n_contrib);
+    gs2m_launch_blend_bwd_q(W, H, (W + GS2M_TILE - 1) / GS2M_TILE, (H + GS2M_TILE - 1) / GS2M_TILE, fc, bg, g, b, im, grad_color, grad_buffer, rows,
+                            (hipStream_t)stream_);
+    HIP_TRY(hipGetLastError());
+    return GS2M_OK;
+}
+
+int gs2m_debug_row_floats(int fc) {
+    if (fc < 0 || fc > GS2M_NUM_FEATURES) return GS2M_ERR_INVALID_ARG;
+    return gs2m_row_floats(fc);
+}
+
 }  // extern "C"

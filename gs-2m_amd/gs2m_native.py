@@ -73,6 +73,9 @@ SIGNATURES = {
     "gs2m_debug_radix_plan": (i, [i, C.POINTER(i), C.POINTER(i), C.POINTER(i)]),
     "gs2m_debug_radix_sort": (i, [ll, i, p, p, p, p, p, p, p, ull, i, p, p, s]),
     "gs2m_debug_block_scans": (i, [ll, p, p, p, p, ll, p, p, p, p, s]),
+    "gs2m_debug_blend_forward": (i, [i, i, i, p, p, p, p, p, p, p, p, p, p, p, s]),
+    "gs2m_debug_blend_backward": (i, [i, i, i, p, p, p, p, p, p, p, p, p, p, p, p, s]),
+    "gs2m_debug_row_floats": (i, [i]),
     "gs2m_profile_mode": (i, [i]),
     "gs2m_profile_sampling": (i, [i]),
     "gs2m_profile_collect": (i, [C.POINTER(C.c_float), C.POINTER(C.c_int), i]),

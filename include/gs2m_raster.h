@@ -354,6 +354,22 @@ int gs2m_debug_radix_sort(long long n, int total_bits, const unsigned* kin, cons
 int gs2m_debug_block_scans(long long n_blocks, const unsigned* block_tt, const unsigned* block_hu, unsigned* block_pref,
                            unsigned* block_hupref, long long n_waves, const unsigned* wave_rows, unsigned* wave_rowbase,
                            unsigned* counters, unsigned* landing_out, void* stream);
+/* Test hooks (tests/test_blend_gpu.py): the two blend kernels through the launchers of a frame, on caller-made quadrant lists.
+ * The tile grid is ceil(W / 16) x ceil(H / 16).  ranges: per tile {first, last + 1} of its span; the list of (tile, quadrant q) is
+ * the qcount[4 tile + q] entries {Gaussian id | quadrant mask << 28, position in the tile's span} from 4 first + q (span length)
+ * on, in qlist (2 words per entry) and, in parallel, its gradient rows in qrow.  rec: 32 floats per Gaussian (the blend record).
+ * Forward: writes out_color (3 x H x W), out_buffer (10 x H x W), final_T, n_contrib (H x W), qlast (one word per quadrant that
+ * has pixels) and ADDS to observe (one int per Gaussian).  Backward: writes one row of gs2m_debug_row_floats(fc) floats at
+ * every row index that qrow holds in a quadrant that has pixels.  Nothing is allocated: the caller owns every buffer.
+ * GS2M_ERR_INVALID_ARG for a null pointer, W or H < 1, fc outside 0 .. GS2M_NUM_FEATURES. */
+int gs2m_debug_blend_forward(int W, int H, int fc, const float* bg, const unsigned* ranges, const unsigned* qlist,
+                             const unsigned* qcount, const float* rec, float* out_color, float* out_buffer, float* final_T,
+                             unsigned* n_contrib, int* observe, unsigned* qlast, void* stream);
+int gs2m_debug_blend_backward(int W, int H, int fc, const float* bg, const unsigned* ranges, const unsigned* qlist,
+                              const unsigned* qcount, const unsigned* qrow, const unsigned* qlast, const float* rec,
+                              const float* final_T, const unsigned* n_contrib, const float* grad_color, const float* grad_buffer,
+                              float* rows, void* stream);
+int gs2m_debug_row_floats(int fc);
 
 /* ---- per-stage timing with HIP events recorded on the launch stream (bench.py) ----
  * mode 0 = off, 1 = the two blend kernels only, 2 = every stage, 3 = the backward blend kernel only.  Setting the mode clears

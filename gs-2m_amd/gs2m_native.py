@@ -163,6 +163,11 @@ SIGNATURES = {
     "gs2m_eval_nearest": (i, [ll, p, ll, d, p, d, p, s]),
     "gs2m_eval_nearest_index": (i, [ll, p, ll, d, p, d, p, p, s]),
     "gs2m_eval_masked_mean": (i, [ll, p, d, p, p, p, s]),
+    "gs2m_eval_dilate_bytes": (i, [i, i, i, p]),
+    "gs2m_eval_dilate_disk": (i, [i, i, i, p, i, p, s]),
+    "gs2m_eval_cull_flags": (i, [ll, p, i, p, i, i, p, i, i, p, s]),
+    "gs2m_eval_cull_workspace_bytes": (i, [ll, ll, p]),
+    "gs2m_eval_cull_triangles": (i, [ll, p, ll, p, p, p, p, s]),
     # include/gs2m_tnt.h
     "gs2m_tnt_mesh_points": (i, [ll, p, ll, p, p, p, s]),
     "gs2m_tnt_transform": (i, [ll, p, p, p, s]),

@@ -14,6 +14,12 @@
  *   Filter      flag bit 0 (inbound): lo <= p < hi on every axis; bit 1 (observed): inbound, g = rint((p - bb0) / res) with
  *               0 <= g < dims on every axis and mask[(g0 dims1 + g1) dims2 + g2] != 0.  Plane flag: ((P0 x + P1 y) + P2 z) + P3 > 0.
  *   Nearest     the distance sqrt((dx dx + dy dy) + dz dz) to the nearest target point when it is < max_dist, +inf otherwise.
+ *   Mask cull   (csrc/mesh_cull.hip, fp32 as written) dil = the mask (any non-zero byte is foreground) dilated by the disk
+ *               dx dx + dy dy <= r r, outside the image background.  Per vertex (cast to fp32) and view matrix M (4 x 4 fp32):
+ *               c_k = ((M[k][0] x + M[k][1] y) + M[k][2] z) + M[k][3], px = c_0 / (c_2 + 1e-6f), py alike,
+ *               nx = (px / (Wn - 1) - 0.5f) * 2, valid = -1 < nx < 1 and -1 < ny < 1, ix = rint(((nx + 1) / 2) (W - 1)), iy alike,
+ *               sample = dil[iy, ix] inside the mask, 0 outside; the view passes when sample or not valid; a vertex is kept when
+ *               every view passes.  A face is kept when its three vertices are; kept vertices keep their order, referenced or not.
  *
  * Every buffer is the caller's (the library allocates nothing); workspace sizes come from the *_bytes calls.  Calls are
  * asynchronous on `stream` except those that write a HOST result (they wait for the stream).  Return GS2M_OK (0) or a negative
@@ -88,6 +94,29 @@ int gs2m_eval_nearest_index(long long n_queries, const double* queries, long lon
 /* The sum and count of the entries < max_dist, summed in a fixed order (HOST outputs). */
 int gs2m_eval_masked_mean(long long n, const double* dist, double max_dist, void* ws, double* host_sum, long long* host_count,
                           void* stream);
+
+/* Bytes of n_views dilated masks, bit-packed: one bit per pixel (bit x & 63 of word x >> 6), rows of ceil(W / 64) 64-bit words,
+ * padding bits 0 (HOST output). */
+int gs2m_eval_dilate_bytes(int n_views, int H, int W, long long* bytes);
+
+/* packed = masks (n_views, H, W) uint8, != 0 is foreground, dilated by the disk of radius r (0 <= r <= 64), in the layout of
+ * gs2m_eval_dilate_bytes.  H, W >= 1. */
+int gs2m_eval_dilate_disk(int n_views, int H, int W, const unsigned char* masks, int r, void* packed, void* stream);
+
+/* keep[i] = 1 when vertex i passes every view (see above), else 0.  view_mats: DEVICE float (n_views, 4, 4), row major;
+ * packed: the dilated masks (n_views, H, W); Wn, Hn: the image size the pixel coordinates are normalised by.  n_views = 0 keeps
+ * every vertex. */
+int gs2m_eval_cull_flags(long long n, const double* verts, int n_views, const float* view_mats, int H, int W, const void* packed,
+                         int Wn, int Hn, unsigned char* keep, void* stream);
+
+/* Bytes of gs2m_eval_cull_triangles' workspace (HOST output). */
+int gs2m_eval_cull_workspace_bytes(long long n_verts, long long n_tris, long long* bytes);
+
+/* out_tris (room for n_tris): the triangles whose three vertices have bit 0 of keep set, in input order, renumbered to the kept
+ * vertices' positions (the vertices themselves: gs2m_eval_compact with the same flags, bit 0).  host_totals: HOST long long[2],
+ * the kept vertices and the kept triangles.  GS2M_ERR_INVALID_ARG when a triangle names a vertex outside [0, n_verts). */
+int gs2m_eval_cull_triangles(long long n_verts, const unsigned char* keep, long long n_tris, const int* tris, void* ws,
+                             int* out_tris, long long* host_totals, void* stream);
 
 #ifdef __cplusplus
 }

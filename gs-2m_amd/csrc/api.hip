@@ -649,6 +649,41 @@ int gs2m_debug_block_scans(long long n_blocks, const unsigned* block_tt, const u
     return GS2M_OK;
 }
 
+// Test hook (tests/test_emit_gpu.py): the emission stage of binning.hip through the launchers of a frame, in a frame's order, on
+// caller-made per-Gaussian arrays: the heavy units counted again (only with the crowded-wave rule off, as the forward does),
+// blockscan_kernel, emit_kernel + emit_heavy_kernel + rowscan_kernel.  Nothing is allocated here and nothing is zeroed on the side
+// (ZeroJobs is empty: the caller zeroes tile_hist, which the preprocess kernel zeroes in a frame).  `heavy_units` sizes the grid
+// of emit_heavy_kernel, as the count the forward reads back does.
+int gs2m_debug_emit(int P, int W, int H, int tiles_x, int tile_bits, unsigned int crowded, unsigned int heavy_units, const unsigned* rect,
+                    const float* rec, const unsigned* depth_key, const unsigned* block_tt, unsigned* block_hu, unsigned* block_pref,
+                    unsigned* block_hupref, unsigned* keys_unsorted, unsigned* e_rec, void* hrec, unsigned* gauss_rows, unsigned* wave_rows,
+                    unsigned* wave_rowbase, unsigned* counters, unsigned* tile_hist, unsigned* landing_out, void* stream_) {
+    if (P < 1 || W < 1 || H < 1 || tiles_x < 1 || tile_bits < 0 || tile_bits > 32 || heavy_units >= (1u << 22)) return GS2M_ERR_INVALID_ARG;
+    if (!rect || !rec || !depth_key || !block_tt || !block_hu || !block_pref || !block_hupref || !keys_unsorted || !e_rec || !hrec || !gauss_rows ||
+        !wave_rows || !wave_rowbase || !counters || !tile_hist || !landing_out)
+        return GS2M_ERR_INVALID_ARG;
+    if (((uintptr_t)landing_out & 7) || ((uintptr_t)rect & 7) || ((uintptr_t)rec & 15) || ((uintptr_t)e_rec & 15) || ((uintptr_t)hrec & 3)) return GS2M_ERR_INVALID_ARG;
+    hipStream_t s = (hipStream_t)stream_;
+    GeomState g = {};
+    g.rect = reinterpret_cast<uint2*>(const_cast<unsigned*>(rect));
+    g.rec = reinterpret_cast<float4*>(const_cast<float*>(rec));
+    g.depth_key = const_cast<uint32_t*>(depth_key);
+    g.block_tt = const_cast<uint32_t*>(block_tt); g.block_hu = block_hu;
+    g.block_pref = block_pref; g.block_hupref = block_hupref;
+    g.gauss_rows = gauss_rows; g.wave_rows = wave_rows; g.wave_rowbase = wave_rowbase;
+    g.counters = counters; g.tile_hist = tile_hist;
+    BinningState b = {};
+    b.keys_unsorted = keys_unsorted;
+    b.e_rec = reinterpret_cast<uint4*>(e_rec);
+    b.hrec = reinterpret_cast<HeavyUnit*>(hrec);
+    if (crowded == GS2M_CROWDED_OFF) gs2m_launch_recount_heavy(P, g, s);
+    gs2m_launch_blockscan(P, g, landing_out, s);
+    const ZeroJobs zj = {{nullptr, nullptr, nullptr}, {0, 0, 0}};
+    gs2m_launch_emit(P, W, H, tiles_x, tile_bits, g, b, heavy_units, crowded, landing_out, zj, s);
+    HIP_TRY(hipGetLastError());
+    return GS2M_OK;
+}
+
 // Test hooks (tests/test_blend_gpu.py): blend_fwd_q.hip / blend_bwd_q.hip through the launchers of a frame on caller-made quadrant
 // lists (layout: common.h, BinningState::qlist / qrow).  Nothing is allocated here: the caller owns every buffer.
 int gs2m_debug_blend_forward(int W, int H, int fc, const float* bg, const unsigned* ranges, const unsigned* qlist, const unsigned* qcount,

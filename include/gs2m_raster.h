@@ -354,6 +354,22 @@ int gs2m_debug_radix_sort(long long n, int total_bits, const unsigned* kin, cons
 int gs2m_debug_block_scans(long long n_blocks, const unsigned* block_tt, const unsigned* block_hu, unsigned* block_pref,
                            unsigned* block_hupref, long long n_waves, const unsigned* wave_rows, unsigned* wave_rowbase,
                            unsigned* counters, unsigned* landing_out, void* stream);
+/* Test hook (tests/test_emit_gpu.py): the instance emission of a frame on caller-made per-Gaussian arrays, through the launchers
+ * of a frame: the heavy units counted again without the crowded-wave rule (only when crowded is the rule's "off" word: block_hu
+ * is then rewritten), the block scans, the emit kernels, the row scan.  Read: rect (2 words per Gaussian), rec (32 floats per
+ * Gaussian, of which x, y, A, B, C and t2 are used; 16-byte aligned), depth_key, block_tt, block_hu (ceil(P / 256) words each: the
+ * sums of the rectangles' areas and of the heavy units under the crowded-wave rule), tile_hist (8 x 1024 words, ZEROED by the
+ * caller: the digit counts are added).  heavy_units: the units of the frame under `crowded`, counted by the caller (hrec holds
+ * that many records of 80 bytes; counters[3] has the kernels' own count afterwards).  Written: block_pref, block_hupref,
+ * keys_unsorted (one word per instance), e_rec (4 words per instance, 16-byte aligned), hrec, gauss_rows (P words), wave_rows,
+ * wave_rowbase (ceil(P / 64) words each), counters (64 words), tile_hist, landing_out (4 words of device memory, 8-byte aligned).
+ * Nothing is allocated: the caller owns every buffer.  GS2M_ERR_INVALID_ARG for a null or misaligned pointer, P < 1, an image
+ * or tile grid < 1, tile_bits outside 0 .. 32. */
+int gs2m_debug_emit(int P, int W, int H, int tiles_x, int tile_bits, unsigned int crowded, unsigned int heavy_units,
+                    const unsigned* rect, const float* rec, const unsigned* depth_key, const unsigned* block_tt, unsigned* block_hu,
+                    unsigned* block_pref, unsigned* block_hupref, unsigned* keys_unsorted, unsigned* e_rec, void* hrec,
+                    unsigned* gauss_rows, unsigned* wave_rows, unsigned* wave_rowbase, unsigned* counters, unsigned* tile_hist,
+                    unsigned* landing_out, void* stream);
 /* Test hooks (tests/test_blend_gpu.py): the two blend kernels through the launchers of a frame, on caller-made quadrant lists.
  * The tile grid is ceil(W / 16) x ceil(H / 16).  ranges: per tile {first, last + 1} of its span; the list of (tile, quadrant q) is
  * the qcount[4 tile + q] entries {Gaussian id | quadrant mask << 28, position in the tile's span} from 4 first + q (span length)

@@ -1,12 +1,16 @@
 """csrc/tile_sort.hip on caller-made spans (gs2m_debug_tile_sort): every tile's span must come out in (depth, Gaussian id)
 order -- the order the reference's 45-bit radix sort of id-ordered keys produces inside a tile (rasterizer_impl.cu:288-296) --
 and the four quadrant lists / gradient rows must be the order-preserving split of it.  Spans of every length class (one wave
-with 8 or 16 elements per lane, a workgroup with 2, 4 or 8 per lane, a workgroup over LDS, a workgroup over global memory), with many exactly equal depths."""
+with 8 or 16 elements per lane, a workgroup with 2, 4 or 8 per lane, a workgroup over LDS, a workgroup over global memory), with many exactly equal depths.  A tenth of the
+records carry the row of a heavy Gaussian's instance -- GS2M_ROWS_BIG | an absolute row, to which no wave base is added -- so that
+the spans of every size class hold some."""
 import numpy as np
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
+
+ROWS_BIG = np.uint32(0x80000000)   # common.h: GS2M_ROWS_BIG
 
 
 @pytest.fixture(params=[0, 1, 2, 3], ids=["auto", "workgroups", "waves", "waves-mid-by-workgroup"], autouse=True)
@@ -43,6 +47,12 @@ def _run(lengths, max_tile, seed, tie_levels):
         gid = np.sort(rng.choice(P, L, replace=False)).astype(np.uint32)   # a Gaussian appears once per tile; index order
         val[lo:lo + L] = gid | (rng.integers(0, 16, L).astype(np.uint32) << np.uint32(28))
         row[lo:lo + L] = rng.integers(0, 1 << 20, L)
+    # heavy instances: the row is absolute and flagged; drawn from [2^26, 2^27), which no relative row + wave base (< 2^20 + 2^24) reaches
+    big = rng.random(nn) < 0.1
+    row[big] = ROWS_BIG | rng.integers(1 << 26, 1 << 27, int(big.sum())).astype(np.uint32)
+    for t, L in enumerate(lengths):
+        if L >= 256:   # (0.9^256 = 2e-12)
+            assert big[int(starts[t]):int(starts[t]) + L].any(), f"tile {t} (length {L}) holds no flagged record"
     slot = rng.permutation(nn).astype(np.uint32)          # the emission slots the sorted values point at
     e_rec = np.zeros((nn, 4), np.uint32)
     e_rec[slot, 0] = val; e_rec[slot, 1] = row; e_rec[slot, 2] = depth_key[val & np.uint32(0x0FFFFFFF)]
@@ -70,7 +80,8 @@ def _run(lengths, max_tile, seed, tie_levels):
         d = depth_key[v & np.uint32(0x0FFFFFFF)]
         order = np.lexsort((v & np.uint32(0x0FFFFFFF), d))   # by depth, ties by Gaussian id
         assert np.array_equal(pl[lo:lo + Ln], v[order]), f"tile {t} (length {Ln}): sorted values"
-        sv, sr = v[order], r[order] + wave_rowbase[(v[order] & np.uint32(0x0FFFFFFF)) >> 6]
+        flagged = (r[order] & ROWS_BIG) != 0
+        sv, sr = v[order], np.where(flagged, r[order] & ~ROWS_BIG, r[order] + wave_rowbase[(v[order] & np.uint32(0x0FFFFFFF)) >> 6])
         m = sv >> 28
         for q in range(4):
             sel = np.nonzero((m >> q) & 1)[0]

@@ -10,7 +10,8 @@ kernel reads a pair once and returns the exact integer sum of squared difference
 
 NOT computed: LPIPS (metrics.py:57) needs VGG weights this stack neither carries nor may fetch; the `lpips` key
 is not written.  `score_views` renders and scores views without leaving the device; of render.py's per-view outputs it can
-write render/ and gt/ only (no normal, depth or material maps).
+write render/ and gt/ only.  gs2m_render.py writes the whole tree this command reads -- render, gt, normal, depth and the
+material maps.
 
 There is NO CPU fallback: `image_metrics` refuses CPU tensors.  `collect_pairs` and `merge_metrics` are host-only."""
 import argparse

@@ -182,6 +182,11 @@ SIGNATURES = {
     # include/gs2m_metrics.h
     "gs2m_image_metrics_workspace_bytes": (i, [i, i, i, i, p]),
     "gs2m_image_metrics": (i, [i, i, i, i, p, p, p, ll, p, p, s]),
+    # include/gs2m_maps.h
+    "gs2m_order_stats_workspace_bytes": (i, [ll, i, p]),
+    "gs2m_order_stats": (i, [ll, p, i, p, p, ll, p, p, s]),
+    "gs2m_depth_colorize": (i, [i, i, p, p, f, f, p, s]),
+    "gs2m_pack_image": (i, [i, i, i, i, p, p, p, p, p, i, i, p, s]),
 }
 del p, i, f, d, ll, ull, A, s
 EXPORTS = tuple(SIGNATURES)

@@ -134,6 +134,21 @@ struct StageTimer {
         if (failed_stage) return GS2M_ERR_STAGE(failed_stage - 1); \
     } while (0)
 
+// What the preprocess kernel is told about a frame besides its inputs: the tile grid and the focal lengths in pixels
+// (forward_impl and the test hook gs2m_debug_preprocess)
+struct FrameDims {
+    int tiles_x, tiles_y;
+    float focal_x, focal_y;
+};
+inline FrameDims frame_dims(int width, int height, float tan_fovx, float tan_fovy) {
+    FrameDims d;
+    d.tiles_x = (width + GS2M_TILE - 1) / GS2M_TILE;
+    d.tiles_y = (height + GS2M_TILE - 1) / GS2M_TILE;
+    d.focal_y = height / (2.0f * tan_fovy);
+    d.focal_x = width / (2.0f * tan_fovx);
+    return d;
+}
+
 }  // namespace
 
 extern "C" {
@@ -173,10 +188,10 @@ static int forward_impl(gs2m_alloc_fn geometry_alloc, void* geometry_user, gs2m_
     // the sorted values carry a 4-bit quadrant mask above the Gaussian id (binning.hip): ids stay below 2^28
     if (P >= (1 << GS2M_GID_BITS)) return GS2M_ERR_UNSUPPORTED;
 
-    const int tiles_x = (width + GS2M_TILE - 1) / GS2M_TILE, tiles_y = (height + GS2M_TILE - 1) / GS2M_TILE;
+    const FrameDims fd = frame_dims(width, height, tan_fovx, tan_fovy);
+    const int tiles_x = fd.tiles_x, tiles_y = fd.tiles_y;
     const size_t tiles = (size_t)tiles_x * tiles_y, N = (size_t)width * height;
-    const float focal_y = height / (2.0f * tan_fovy);
-    const float focal_x = width / (2.0f * tan_fovx);
+    const float focal_y = fd.focal_y, focal_x = fd.focal_x;
 
     const size_t Pn = P > 0 ? (size_t)P : 1;
     GeomState gsz = gs2m_carve_geom(nullptr, Pn);
@@ -680,6 +695,43 @@ int gs2m_debug_emit(int P, int W, int H, int tiles_x, int tile_bits, unsigned in
     gs2m_launch_blockscan(P, g, landing_out, s);
     const ZeroJobs zj = {{nullptr, nullptr, nullptr}, {0, 0, 0}};
     gs2m_launch_emit(P, W, H, tiles_x, tile_bits, g, b, heavy_units, crowded, landing_out, zj, s);
+    HIP_TRY(hipGetLastError());
+    return GS2M_OK;
+}
+
+// Test hook (tests/test_preprocess_gpu.py): preprocess_kernel through the launcher of a frame on caller-made inputs and caller-owned
+// outputs.  Nothing is allocated here.  The tile grid and the focal lengths are derived as forward_impl derives them (frame_dims);
+// what forward_impl refuses is refused here, and so is every pointer whose alignment a frame gets from its carved buffers
+// (rec, sh_dir: float4 stores; rect: uint2 stores) or from the tensor allocator (rotations: float4 loads).  One side zero-fill
+// (ZeroJobs), as the frame's digit histograms are.
+int gs2m_debug_preprocess(int P, int D, int M, const float* means3D, const float* scales, float scale_modifier, const float* rotations,
+                          const float* opacities, const float* shs, const float* shs_rest, const float* cov3D_precomp,
+                          const float* colors_precomp, const float* features, const float* viewmatrix, const float* projmatrix,
+                          const float* cam_pos, int W, int H, float tan_fovx, float tan_fovy, int shrink, int* radii, int* observe_zero,
+                          float* rec, unsigned* tiles_touched, unsigned* rect, unsigned* block_tt, unsigned* block_hu, unsigned* depth_key,
+                          unsigned char* clamped, float* sh_dir, unsigned* zero_words, unsigned long long zero_count, void* stream_) {
+    if (P < 1 || P >= (1 << GS2M_GID_BITS) || W <= 0 || H <= 0 || W > 16 * 65535 || H > 16 * 65535) return GS2M_ERR_INVALID_ARG;
+    if (!means3D || !opacities || !viewmatrix || !projmatrix) return GS2M_ERR_INVALID_ARG;
+    if (!radii || !rec || !tiles_touched || !rect || !block_tt || !block_hu || !depth_key || !clamped) return GS2M_ERR_INVALID_ARG;
+    if ((shs == nullptr) == (colors_precomp == nullptr)) return GS2M_ERR_INVALID_ARG;
+    if (((scales == nullptr) || (rotations == nullptr)) == (cov3D_precomp == nullptr)) return GS2M_ERR_INVALID_ARG;
+    if (shs && (D < 0 || D > 3 || M < (D + 1) * (D + 1) || !cam_pos || !sh_dir)) return GS2M_ERR_INVALID_ARG;
+    if (shs_rest && (!shs || M != 16 || (((uintptr_t)shs_rest) & 15))) return GS2M_ERR_INVALID_ARG;  // split SH: M = 16 only
+    if (((uintptr_t)rec & 15) || ((uintptr_t)sh_dir & 15) || ((uintptr_t)rect & 7) || ((uintptr_t)rotations & 15)) return GS2M_ERR_INVALID_ARG;
+    if (zero_count > 0 && !zero_words) return GS2M_ERR_INVALID_ARG;
+    const FrameDims fd = frame_dims(W, H, tan_fovx, tan_fovy);
+    GeomState g = {};
+    g.rec = reinterpret_cast<float4*>(rec);
+    g.tiles_touched = tiles_touched;
+    g.rect = reinterpret_cast<uint2*>(rect);
+    g.block_tt = block_tt; g.block_hu = block_hu;
+    g.depth_key = depth_key;
+    g.clamped = clamped;
+    g.sh_dir = sh_dir;
+    const ZeroJobs zj = {{zero_words, nullptr, nullptr}, {(size_t)zero_count, 0, 0}};
+    gs2m_launch_preprocess(P, D, M, means3D, scales, scale_modifier, rotations, opacities, shs, shs_rest, cov3D_precomp, colors_precomp,
+                           features, viewmatrix, projmatrix, cam_pos, W, H, tan_fovx, tan_fovy, fd.focal_x, fd.focal_y, fd.tiles_x,
+                           fd.tiles_y, radii, observe_zero, g, shrink ? 1 : 0, zj, (hipStream_t)stream_);
     HIP_TRY(hipGetLastError());
     return GS2M_OK;
 }

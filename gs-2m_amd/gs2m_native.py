@@ -74,6 +74,7 @@ SIGNATURES = {
     "gs2m_debug_radix_sort": (i, [ll, i, p, p, p, p, p, p, p, ull, i, p, p, s]),
     "gs2m_debug_block_scans": (i, [ll, p, p, p, p, ll, p, p, p, p, s]),
     "gs2m_debug_emit": (i, [i, i, i, i, i, i, i, p, p, p, p, p, p, p, p, p, p, p, p, p, p, p, p, s]),
+    "gs2m_debug_preprocess": (i, [i, i, i, p, p, f, p, p, p, p, p, p, p, p, p, p, i, i, f, f, i, p, p, p, p, p, p, p, p, p, p, p, ull, s]),
     "gs2m_debug_blend_forward": (i, [i, i, i, p, p, p, p, p, p, p, p, p, p, p, s]),
     "gs2m_debug_blend_backward": (i, [i, i, i, p, p, p, p, p, p, p, p, p, p, p, p, s]),
     "gs2m_debug_row_floats": (i, [i]),

@@ -370,6 +370,25 @@ int gs2m_debug_emit(int P, int W, int H, int tiles_x, int tile_bits, unsigned in
                     unsigned* block_pref, unsigned* block_hupref, unsigned* keys_unsorted, unsigned* e_rec, void* hrec,
                     unsigned* gauss_rows, unsigned* wave_rows, unsigned* wave_rowbase, unsigned* counters, unsigned* tile_hist,
                     unsigned* landing_out, void* stream);
+/* Test hook (tests/test_preprocess_gpu.py): the per-Gaussian forward preprocess kernel alone, through the launcher of a frame, on
+ * caller-made inputs.  The tile grid and the focal lengths follow from W, H and the tangents as in gs2m_raster_forward; shrink:
+ * 0 = the reference's rectangles (reference binning), otherwise the default, shrunk ones.  Nullable: shs_rest (with it, shs holds
+ * the DC coefficients only and M must be 16), cov3D_precomp (else scales and rotations), colors_precomp (else shs and cam_pos),
+ * features (10 floats per Gaussian; zeros are recorded without them), observe_zero.  Written, for P Gaussians: radii, observe_zero
+ * (zeros), tiles_touched, rect (2 words each, 8-byte aligned), depth_key; rec (32 floats each, 16-byte aligned) and clamped (one
+ * byte each) of the Gaussians with a radius only; sh_dir (9 floats each, 16-byte aligned; untouched with colors_precomp);
+ * block_tt and block_hu (ceil(P / 256) words each); zero_count words from zero_words on are zeroed on the side.  Nothing is
+ * allocated: the caller owns every buffer.  GS2M_ERR_INVALID_ARG, and nothing launched, for P < 1 or P >= 2^28, an image < 1, a
+ * null required pointer, both or neither of shs / colors_precomp and of scales + rotations / cov3D_precomp, D outside 0 .. 3
+ * or M < (D + 1)^2, shs_rest with M != 16 or not 16-byte aligned, rec, sh_dir or rotations not 16-byte aligned, rect not 8-byte
+ * aligned. */
+int gs2m_debug_preprocess(int P, int D, int M, const float* means3D, const float* scales, float scale_modifier,
+                          const float* rotations, const float* opacities, const float* shs, const float* shs_rest,
+                          const float* cov3D_precomp, const float* colors_precomp, const float* features, const float* viewmatrix,
+                          const float* projmatrix, const float* cam_pos, int W, int H, float tan_fovx, float tan_fovy, int shrink,
+                          int* radii, int* observe_zero, float* rec, unsigned* tiles_touched, unsigned* rect, unsigned* block_tt,
+                          unsigned* block_hu, unsigned* depth_key, unsigned char* clamped, float* sh_dir, unsigned* zero_words,
+                          unsigned long long zero_count, void* stream);
 /* Test hooks (tests/test_blend_gpu.py): the two blend kernels through the launchers of a frame, on caller-made quadrant lists.
  * The tile grid is ceil(W / 16) x ceil(H / 16).  ranges: per tile {first, last + 1} of its span; the list of (tile, quadrant q) is
  * the qcount[4 tile + q] entries {Gaussian id | quadrant mask << 28, position in the tile's span} from 4 first + q (span length)

@@ -778,6 +778,57 @@ int gs2m_debug_blend_backward(int W, int H, int fc, const float* bg, const unsig
     return GS2M_OK;
 }
 
+// Test hook (tests/test_gaussian_bwd_gpu.py): gaussian_bwd.hip through the two launchers of a frame, in backward_impl's order, on
+// caller-made row layouts and caller-owned outputs.  Nothing is allocated here.  What backward_impl refuses is refused here, and so
+// is every pointer whose alignment a frame gets from its carved buffers (sh_dir, hrec), from the aligned scratch block (rows) or
+// from the tensor allocator (rotations, the float4 outputs, the split SH tensors), and a null among the arrays the kernels of this
+// call read.  heavy_units: >= 0 known on the host, -1 read from counters[GS2M_CNT_HUNITS] on the device; windows: 0 = the
+// launcher's own rule, 2 or 3 forced.
+int gs2m_debug_gaussian_bwd(int P, int D, int M, const float* means3D, const float* shs, const float* shs_rest, const float* colors_precomp,
+                            const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                            const float* viewmatrix, const float* projmatrix, const float* campos, int W, int H, float tan_fovx, float tan_fovy,
+                            const int* radii, int fc, const float* rec, const unsigned* gauss_rows, const unsigned* tiles_touched,
+                            const unsigned* wave_rowbase, const unsigned char* clamped, const float* sh_dir, const void* hrec,
+                            const unsigned* counters, float* rows, int have_rows, long long heavy_units, int windows, float* dL_dmeans2D,
+                            float* dL_dconics, float* dL_dopacities, float* dL_dcolors, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dshs,
+                            float* dL_dshs_rest, float* dL_dscales, float* dL_drots, float* dL_dfeatures, void* stream_) {
+    auto off16 = [](const void* q) { return (((uintptr_t)q) & 15) != 0; };
+    if (P < 1 || P >= (1 << GS2M_GID_BITS) || W <= 0 || H <= 0 || fc < 0 || fc > GS2M_NUM_FEATURES) return GS2M_ERR_INVALID_ARG;
+    if (windows != 0 && windows != 2 && windows != 3) return GS2M_ERR_INVALID_ARG;
+    if (heavy_units < -1 || heavy_units >= (1ll << 22)) return GS2M_ERR_INVALID_ARG;
+    if (!means3D || !viewmatrix || !projmatrix || !radii) return GS2M_ERR_INVALID_ARG;
+    if (!dL_dmeans2D || !dL_dopacities || !dL_dmeans3D || !dL_dscales || !dL_drots || !dL_dfeatures) return GS2M_ERR_INVALID_ARG;
+    if ((shs == nullptr) == (colors_precomp == nullptr)) return GS2M_ERR_INVALID_ARG;
+    if (((scales == nullptr) || (rotations == nullptr)) == (cov3D_precomp == nullptr)) return GS2M_ERR_INVALID_ARG;
+    if ((colors_precomp && !dL_dcolors) || (cov3D_precomp && !dL_dcov3D)) return GS2M_ERR_INVALID_ARG;
+    if (shs && (D < 0 || D > 3 || M < (D + 1) * (D + 1) || !campos || !clamped || (D > 0 && !sh_dir))) return GS2M_ERR_INVALID_ARG;
+    if (shs_rest && (!shs || M != 16 || ((dL_dshs == nullptr) != (dL_dshs_rest == nullptr)) || off16(shs_rest) || off16(dL_dshs_rest))) return GS2M_ERR_INVALID_ARG;
+    if (!shs_rest && dL_dshs_rest) return GS2M_ERR_INVALID_ARG;
+    if (have_rows && (!rows || !gauss_rows || !tiles_touched || !wave_rowbase)) return GS2M_ERR_INVALID_ARG;
+    if (have_rows && heavy_units != 0 && (!hrec || !counters)) return GS2M_ERR_INVALID_ARG;
+    if ((have_rows && off16(rows)) || off16(rotations) || off16(dL_dmeans2D) || off16(dL_dconics) || off16(dL_drots) || off16(sh_dir) || (((uintptr_t)hrec) & 3))
+        return GS2M_ERR_INVALID_ARG;
+    hipStream_t s = (hipStream_t)stream_;
+    GeomState g = {};
+    g.rec = reinterpret_cast<float4*>(const_cast<float*>(rec));
+    g.gauss_rows = const_cast<uint32_t*>(gauss_rows);
+    g.tiles_touched = const_cast<uint32_t*>(tiles_touched);
+    g.wave_rowbase = const_cast<uint32_t*>(wave_rowbase);
+    g.clamped = const_cast<uint8_t*>(clamped);
+    g.sh_dir = const_cast<float*>(sh_dir);
+    g.counters = const_cast<uint32_t*>(counters);
+    BinningState b = {};
+    b.hrec = reinterpret_cast<HeavyUnit*>(const_cast<void*>(hrec));
+    const int rowf = gs2m_row_floats(fc);
+    if (have_rows) gs2m_launch_heavy_reduce(rows, rowf, b, g, heavy_units, s);
+    gs2m_launch_gaussian_bwd(P, D, M, means3D, shs, shs_rest, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix,
+                             projmatrix, campos, W, H, tan_fovx, tan_fovy, radii, fc, g, rows, rowf, have_rows != 0, dL_dmeans2D, dL_dconics,
+                             dL_dopacities, dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dshs, dL_dshs_rest, dL_dscales, dL_drots, dL_dfeatures, s,
+                             windows);
+    HIP_TRY(hipGetLastError());
+    return GS2M_OK;
+}
+
 int gs2m_debug_row_floats(int fc) {
     if (fc < 0 || fc > GS2M_NUM_FEATURES) return GS2M_ERR_INVALID_ARG;
     return gs2m_row_floats(fc);

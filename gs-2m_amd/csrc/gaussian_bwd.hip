@@ -625,7 +625,7 @@ void gs2m_launch_gaussian_bwd(int P, int D, int M, const float* means3D, const f
                               int fc, const GeomState& g, const float* rows, int rowf, bool have_rows,
                               float* dL_dmeans2D, float* dL_dconics, float* dL_dopacities, float* dL_dcolors,
                               float* dL_dmeans3D, float* dL_dcov3D, float* dL_dshs, float* dL_dshs_rest, float* dL_dscales,
-                              float* dL_drots, float* dL_dfeatures, hipStream_t s) {
+                              float* dL_drots, float* dL_dfeatures, hipStream_t s, int force_win) {
     const float h_x = W / (2.0f * tan_fovx), h_y = H / (2.0f * tan_fovy);
 #define GS2M_GB(LDS, RQ, WIN)                                                                                           \
     gaussian_bwd_kernel<LDS, RQ, WIN><<<(P + 255) / 256, 256, 0, s>>>(                                                  \
@@ -642,7 +642,8 @@ void gs2m_launch_gaussian_bwd(int P, int D, int M, const float* means3D, const f
         case 5: GS2M_GBW(LDS, 5); break;                                                                                \
         default: GS2M_GBW(LDS, 6); break;                                                                               \
     }
-    const bool few = (P + 255) / 256 < 3 * 256;  // fewer workgroups than three per CU: occupancy is not the limit, the wave's chain is
+    // fewer workgroups than three per CU: occupancy is not the limit, the wave's chain is (force_win: the test hook's choice, api.hip)
+    const bool few = force_win ? force_win == 3 : (P + 255) / 256 < 3 * 256;
     // dL_dshs == NULL with SH input: the caller does not want dL/dSH (its colour gradient is identically zero, e.g. a view rendered for
     // its depth and normals only): the per-Gaussian kernel skips the 48 stores per Gaussian; everything else is computed as usual
     const int want_sh = dL_dshs != nullptr ? 1 : 0;

@@ -77,6 +77,8 @@ SIGNATURES = {
     "gs2m_debug_preprocess": (i, [i, i, i, p, p, f, p, p, p, p, p, p, p, p, p, p, i, i, f, f, i, p, p, p, p, p, p, p, p, p, p, p, ull, s]),
     "gs2m_debug_blend_forward": (i, [i, i, i, p, p, p, p, p, p, p, p, p, p, p, s]),
     "gs2m_debug_blend_backward": (i, [i, i, i, p, p, p, p, p, p, p, p, p, p, p, p, s]),
+    "gs2m_debug_gaussian_bwd": (i, [i, i, i, p, p, p, p, p, f, p, p, p, p, p, i, i, f, f, p, i, p, p, p, p, p, p, p, p, p, i, ll, i, p, p, p, p, p, p,
+                                    p, p, p, p, p, s]),
     "gs2m_debug_row_floats": (i, [i]),
     "gs2m_profile_mode": (i, [i]),
     "gs2m_profile_sampling": (i, [i]),

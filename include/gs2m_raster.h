@@ -404,6 +404,32 @@ int gs2m_debug_blend_backward(int W, int H, int fc, const float* bg, const unsig
                               const unsigned* qcount, const unsigned* qrow, const unsigned* qlast, const float* rec,
                               const float* final_T, const unsigned* n_contrib, const float* grad_color, const float* grad_buffer,
                               float* rows, void* stream);
+/* Test hook (tests/test_gaussian_bwd_gpu.py): the per-Gaussian backward alone -- the sums of the heavy units' rows, then the row
+ * sums and the chain behind them -- through the two launchers of a frame, in the order of gs2m_raster_backward, on caller-made row
+ * layouts.  The scene inputs, radii, fc and the eleven outputs are those of gs2m_raster_backward[_split_sh] (dL_dconics, dL_dcolors,
+ * dL_dcov3D, dL_dshs and dL_dshs_rest nullable as there).  Read per Gaussian: gauss_rows (its rows in its wave's run, or
+ * 0x80000000 | first unit of a heavy one), tiles_touched (of a heavy one: ceil(/ 64) units), clamped (one byte), sh_dir (9 floats,
+ * 16-byte aligned); per wave of 64: wave_rowbase (first row of the wave's run); hrec: 80 bytes per heavy unit (4-byte aligned) of
+ * which the 64 pop bytes are read; counters: 64 words, counters[3] = the heavy units; rec is not read and may be NULL.  rows:
+ * gs2m_debug_row_floats(fc) floats per row, 16-byte aligned, unit u's 256 rows from row 256 u on, the waves' runs behind them; the
+ * units' sums are WRITTEN over each unit's first row.  have_rows = 0: rows and the six arrays are not read, every sum is zero.
+ * heavy_units: >= 0 = the count, known on the host; -1 = read from counters[3] on the device.  windows: row windows in flight per
+ * wave, 0 = the launcher's own rule, 2 or 3 forced.  Nothing is allocated: the caller owns every buffer.  GS2M_ERR_INVALID_ARG, and
+ * nothing launched, for P < 1 or P >= 2^28, an image < 1, fc outside 0 .. GS2M_NUM_FEATURES, windows other than 0, 2, 3,
+ * heavy_units < -1 or >= 2^22, a null required pointer (with have_rows: rows, gauss_rows, tiles_touched, wave_rowbase, and hrec and
+ * counters unless heavy_units = 0; with shs: campos, clamped, and sh_dir when D > 0), both or neither of shs / colors_precomp and of
+ * scales + rotations / cov3D_precomp, colors_precomp without dL_dcolors or cov3D_precomp without dL_dcov3D, D outside 0 .. 3 or
+ * M < (D + 1)^2, shs_rest with M != 16 or only one of dL_dshs / dL_dshs_rest, dL_dshs_rest without shs_rest, and for rows,
+ * rotations, dL_dmeans2D, dL_dconics, dL_drots, sh_dir, shs_rest or dL_dshs_rest not 16-byte aligned, hrec not 4-byte aligned. */
+int gs2m_debug_gaussian_bwd(int P, int D, int M, const float* means3D, const float* shs, const float* shs_rest,
+                            const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
+                            const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix, const float* campos, int W,
+                            int H, float tan_fovx, float tan_fovy, const int* radii, int fc, const float* rec,
+                            const unsigned* gauss_rows, const unsigned* tiles_touched, const unsigned* wave_rowbase,
+                            const unsigned char* clamped, const float* sh_dir, const void* hrec, const unsigned* counters, float* rows,
+                            int have_rows, long long heavy_units, int windows, float* dL_dmeans2D, float* dL_dconics,
+                            float* dL_dopacities, float* dL_dcolors, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dshs,
+                            float* dL_dshs_rest, float* dL_dscales, float* dL_drots, float* dL_dfeatures, void* stream);
 int gs2m_debug_row_floats(int fc);
 
 /* ---- per-stage timing with HIP events recorded on the launch stream (bench.py) ----

@@ -254,13 +254,27 @@ void gs2m_radix_zero_region(void* temp, size_t n, int total_bits, uint32_t** ptr
 #define GS2M_CNT_SPAN_MID 4
 #define GS2M_CNT_SPAN_LONG 5
 
+// One frame as the entry points (api.hip, debug_hooks.hip) hand it to the launchers, which unpack it into the kernels' flat lists
+struct RasterFrame {
+    int P, D, M, W, H, fc;
+    float scale_modifier, tan_fovx, tan_fovy;
+    int tiles_x, tiles_y; float focal_x, focal_y;  // the tile grid, the focal lengths in pixels: derived by gs2m_raster_frame, nowhere else
+    const float *means3D, *shs, *shs_rest, *colors_precomp, *opacities, *scales, *rotations, *cov3D_precomp, *features, *viewmatrix, *projmatrix, *cam_pos;
+};
+static inline RasterFrame gs2m_raster_frame(int W, int H, float tan_fovx, float tan_fovy) {
+    RasterFrame f = {};
+    f.W = W; f.H = H; f.tan_fovx = tan_fovx; f.tan_fovy = tan_fovy;
+    f.tiles_x = W / GS2M_TILE + (W % GS2M_TILE != 0); f.tiles_y = H / GS2M_TILE + (H % GS2M_TILE != 0);  // (rounded up; any int may arrive)
+    f.focal_y = H / (2.0f * tan_fovy); f.focal_x = W / (2.0f * tan_fovx);
+    return f;
+}
+struct RasterGrads {  // the gradient tensors of a backward (include/gs2m_raster.h: which of them may be NULL)
+    float *means2D, *conics, *opacities, *colors, *means3D, *cov3D, *shs, *shs_rest, *scales, *rots, *features;
+};
+
 // kernel launchers
-void gs2m_launch_preprocess(int P, int D, int M, const float* means3D, const float* scales, float scale_modifier,
-                            const float* rotations, const float* opacities, const float* shs, const float* shs_rest,
-                            const float* cov3D_precomp, const float* colors_precomp, const float* features,
-                            const float* viewmatrix, const float* projmatrix, const float* cam_pos, int W, int H,
-                            float tan_fovx, float tan_fovy, float focal_x, float focal_y, int tiles_x, int tiles_y,
-                            int* radii, int* observe_zero, const GeomState& g, int shrink, const ZeroJobs& zero, hipStream_t s);
+void gs2m_launch_preprocess(const RasterFrame& f, int* radii, int* observe_zero, const GeomState& g, int shrink, const ZeroJobs& zero,
+                            hipStream_t s);
 // binning.hip: blockscan (publishes num_rendered; block prefixes of tiles_touched), emit (instances in index order: tile keys,
 // quadrant masks, gradient-row numbering, the tile sort's digit counts) + rowscan (first gradient row of every wave; launched by
 // gs2m_launch_emit behind its kernels, and on its own by the test hook gs2m_debug_block_scans)
@@ -286,15 +300,8 @@ void gs2m_launch_blend_bwd_q(int W, int H, int tiles_x, int tiles_y, int fc, con
                              const BinningState& b, const ImageState& im, const float* grad_color,
                              const float* grad_buffer, float* rows, hipStream_t s);
 int gs2m_row_floats(int fc);  // floats per partial-gradient row: 11 + fc, padded to a multiple of 4
-void gs2m_launch_gaussian_bwd(int P, int D, int M, const float* means3D, const float* shs, const float* shs_rest,
-                              const float* colors_precomp,
-                              const float* scales, float scale_modifier, const float* rotations,
-                              const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
-                              const float* campos, int W, int H, float tan_fovx, float tan_fovy, const int* radii,
-                              int fc, const GeomState& g, const float* rows, int rowf, bool have_rows,
-                              float* dL_dmeans2D, float* dL_dconics, float* dL_dopacities, float* dL_dcolors,
-                              float* dL_dmeans3D, float* dL_dcov3D, float* dL_dshs, float* dL_dshs_rest, float* dL_dscales,
-                              float* dL_drots, float* dL_dfeatures, hipStream_t s, int force_win = 0);
+void gs2m_launch_gaussian_bwd(const RasterFrame& f, const int* radii, const GeomState& g, const float* rows, int rowf, bool have_rows,
+                              const RasterGrads& d, hipStream_t s, int force_win = 0);
 void gs2m_launch_prefiltered_check(int P, const float* means3D, const float* viewmatrix, uint32_t* flag, hipStream_t s);
 void gs2m_launch_mark_visible(int P, const float* means3D, const float* viewmatrix, uint8_t* present, hipStream_t s);
 

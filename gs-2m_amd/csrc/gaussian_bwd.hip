@@ -9,45 +9,11 @@
 // Semantics: computeCov2DCUDA backward.cu:153-281, preprocessCUDA (bwd) backward.cu:352-410,
 // computeColorFromSH (bwd) backward.cu:23-148, computeCov3D (bwd) backward.cu:285-347 of
 // diff-gaussian-rasterization/cuda_rasterizer, including the quirks listed in SURVEY.md A.5
-// (+0.3 low-pass only here, clamp masks, no quaternion normalisation).
+// (+0.3 low-pass only here, clamp masks, no quaternion normalisation).  The forward's own chain is not restated here: gaussian_math.h.
 #include "common.h"
+#include "gaussian_math.h"
 
 namespace {
-
-struct M3 {
-    float m[3][3];  // m[col][row]
-};
-__device__ __forceinline__ M3 m3_cols(float a, float b, float c, float d, float e, float f, float g, float h, float i) {
-    M3 r;
-    r.m[0][0] = a; r.m[0][1] = b; r.m[0][2] = c;
-    r.m[1][0] = d; r.m[1][1] = e; r.m[1][2] = f;
-    r.m[2][0] = g; r.m[2][1] = h; r.m[2][2] = i;
-    return r;
-}
-__device__ __forceinline__ M3 m3_mul(const M3& A, const M3& B) {
-    M3 R;
-#pragma unroll
-    for (int c = 0; c < 3; c++)
-#pragma unroll
-        for (int r = 0; r < 3; r++)
-            R.m[c][r] = A.m[0][r] * B.m[c][0] + A.m[1][r] * B.m[c][1] + A.m[2][r] * B.m[c][2];
-    return R;
-}
-__device__ __forceinline__ M3 m3_t(const M3& A) {
-    M3 R;
-#pragma unroll
-    for (int c = 0; c < 3; c++)
-#pragma unroll
-        for (int r = 0; r < 3; r++) R.m[c][r] = A.m[r][c];
-    return R;
-}
-
-__constant__ float kC2[5] = {1.0925484305920792f, -1.0925484305920792f, 0.31539156525252005f, -1.0925484305920792f,
-                             0.5462742152960396f};
-__constant__ float kC3[7] = {-0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f, 0.3731763325901154f,
-                             -0.4570457994644658f, 1.445305721320277f, -0.5900435899266435f};
-#define SH_C0 0.28209479177387814f
-#define SH_C1 0.4886025119029199f
 
 // Phase 1 of the kernel below: the sum of the partial-gradient rows of each of the workgroup's 256 Gaussians, into LDS.
 // The backward blend (blend_bwd_q.hip) numbers its rows DENSELY in index order: wave w of this workgroup (the same 64
@@ -398,7 +364,7 @@ __global__ void __launch_bounds__(256) gaussian_bwd_kernel(
     float drot[4] = {0.f, 0.f, 0.f, 0.f};
 
     if (visible) {
-        // ---- 3D covariance (recomputed exactly as preprocess.hip does) ----
+        // ---- 3D covariance and its projection: the forward's own chain (gaussian_math.h) ----
         float c3[6];
         float sx = 0.f, sy = 0.f, sz = 0.f, qr = 0.f, qx = 0.f, qy = 0.f, qz = 0.f;
         M3 R, Mm;
@@ -408,32 +374,17 @@ __global__ void __launch_bounds__(256) gaussian_bwd_kernel(
         } else {
             sx = scale_modifier * s_in[0]; sy = scale_modifier * s_in[1]; sz = scale_modifier * s_in[2];
             qr = q_in.x; qx = q_in.y; qy = q_in.z; qz = q_in.w;
-            const float r = qr, x = qx, y = qy, z = qz;
-            M3 S = m3_cols(sx, 0.f, 0.f, 0.f, sy, 0.f, 0.f, 0.f, sz);
-            R = m3_cols(1.f - 2.f * (y * y + z * z), 2.f * (x * y - r * z), 2.f * (x * z + r * y),
-                        2.f * (x * y + r * z), 1.f - 2.f * (x * x + z * z), 2.f * (y * z - r * x),
-                        2.f * (x * z - r * y), 2.f * (y * z + r * x), 1.f - 2.f * (x * x + y * y));
-            Mm = m3_mul(S, R);
-            M3 Sig = m3_mul(m3_t(Mm), Mm);
-            c3[0] = Sig.m[0][0]; c3[1] = Sig.m[0][1]; c3[2] = Sig.m[0][2];
-            c3[3] = Sig.m[1][1]; c3[4] = Sig.m[1][2]; c3[5] = Sig.m[2][2];
+            gs2m_cov3d(sx, sy, sz, q_in, c3, R, Mm);
         }
         // ---- computeCov2DCUDA ----
         const float dcx = acc[4], dcy = acc[5], dcz = acc[6];
-        float tx = vm[0] * mx + vm[4] * my + vm[8] * mz + vm[12];
-        float ty = vm[1] * mx + vm[5] * my + vm[9] * mz + vm[13];
-        const float tz_ = vm[2] * mx + vm[6] * my + vm[10] * mz + vm[14];
-        const float limx = 1.3f * tan_fovx, limy = 1.3f * tan_fovy;
-        const float txtz = tx / tz_, tytz = ty / tz_;
-        tx = fminf(limx, fmaxf(-limx, txtz)) * tz_;
-        ty = fminf(limy, fmaxf(-limy, tytz)) * tz_;
-        const float x_grad_mul = (txtz < -limx || txtz > limx) ? 0.f : 1.f;
-        const float y_grad_mul = (tytz < -limy || tytz > limy) ? 0.f : 1.f;
-        M3 J = m3_cols(h_x / tz_, 0.0f, -(h_x * tx) / (tz_ * tz_), 0.0f, h_y / tz_, -(h_y * ty) / (tz_ * tz_), 0.f, 0.f, 0.f);
-        M3 Wm = m3_cols(vm[0], vm[4], vm[8], vm[1], vm[5], vm[9], vm[2], vm[6], vm[10]);
-        M3 Vrk = m3_cols(c3[0], c3[1], c3[2], c3[1], c3[3], c3[4], c3[2], c3[4], c3[5]);
-        M3 T = m3_mul(Wm, J);
-        M3 cov2D = m3_mul(m3_mul(m3_t(T), m3_t(Vrk)), T);
+        const float3 v = gs2m_view_point(vm, mx, my, mz);
+        Cov2D pr;
+        gs2m_cov2d(v, c3, vm, h_x, h_y, tan_fovx, tan_fovy, pr, true);
+        const float tz_ = v.z, tx = pr.tx, ty = pr.ty;
+        const float x_grad_mul = (pr.txtz < -pr.limx || pr.txtz > pr.limx) ? 0.f : 1.f;
+        const float y_grad_mul = (pr.tytz < -pr.limy || pr.tytz > pr.limy) ? 0.f : 1.f;
+        const M3 &T = pr.T, &Vrk = pr.Vrk, &Wm = pr.W, &cov2D = pr.cov;
         const float a = cov2D.m[0][0] + 0.3f;  // low-pass appears only in the backward (backward.cu:205-207)
         const float b = cov2D.m[0][1];
         const float c = cov2D.m[1][1] + 0.3f;
@@ -530,19 +481,19 @@ __global__ void __launch_bounds__(256) gaussian_bwd_kernel(
                 DSH(2, SH_C1 * z);
                 DSH(3, -SH_C1 * x);
                 if (D > 1) {
-                    DSH(4, kC2[0] * xy);
-                    DSH(5, kC2[1] * yz);
-                    DSH(6, kC2[2] * (2.f * zz - xx - yy));
-                    DSH(7, kC2[3] * xz);
-                    DSH(8, kC2[4] * (xx - yy));
+                    DSH(4, kSH_C2[0] * xy);
+                    DSH(5, kSH_C2[1] * yz);
+                    DSH(6, kSH_C2[2] * (2.f * zz - xx - yy));
+                    DSH(7, kSH_C2[3] * xz);
+                    DSH(8, kSH_C2[4] * (xx - yy));
                     if (D > 2) {
-                        DSH(9, kC3[0] * y * (3.f * xx - yy));
-                        DSH(10, kC3[1] * xy * z);
-                        DSH(11, kC3[2] * y * (4.f * zz - xx - yy));
-                        DSH(12, kC3[3] * z * (2.f * zz - 3.f * xx - 3.f * yy));
-                        DSH(13, kC3[4] * x * (4.f * zz - xx - yy));
-                        DSH(14, kC3[5] * z * (xx - yy));
-                        DSH(15, kC3[6] * x * (xx - 3.f * yy));
+                        DSH(9, kSH_C3[0] * y * (3.f * xx - yy));
+                        DSH(10, kSH_C3[1] * xy * z);
+                        DSH(11, kSH_C3[2] * y * (4.f * zz - xx - yy));
+                        DSH(12, kSH_C3[3] * z * (2.f * zz - 3.f * xx - 3.f * yy));
+                        DSH(13, kSH_C3[4] * x * (4.f * zz - xx - yy));
+                        DSH(14, kSH_C3[5] * z * (xx - yy));
+                        DSH(15, kSH_C3[6] * x * (xx - 3.f * yy));
                     }
                 }
             }
@@ -617,22 +568,14 @@ __global__ void __launch_bounds__(256) gaussian_bwd_kernel(
 
 }  // namespace
 
-void gs2m_launch_gaussian_bwd(int P, int D, int M, const float* means3D, const float* shs, const float* shs_rest,
-                              const float* colors_precomp,
-                              const float* scales, float scale_modifier, const float* rotations,
-                              const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
-                              const float* campos, int W, int H, float tan_fovx, float tan_fovy, const int* radii,
-                              int fc, const GeomState& g, const float* rows, int rowf, bool have_rows,
-                              float* dL_dmeans2D, float* dL_dconics, float* dL_dopacities, float* dL_dcolors,
-                              float* dL_dmeans3D, float* dL_dcov3D, float* dL_dshs, float* dL_dshs_rest, float* dL_dscales,
-                              float* dL_drots, float* dL_dfeatures, hipStream_t s, int force_win) {
-    const float h_x = W / (2.0f * tan_fovx), h_y = H / (2.0f * tan_fovy);
+void gs2m_launch_gaussian_bwd(const RasterFrame& f, const int* radii, const GeomState& g, const float* rows, int rowf, bool have_rows,
+                              const RasterGrads& d, hipStream_t s, int force_win) {
 #define GS2M_GB(LDS, RQ, WIN)                                                                                           \
-    gaussian_bwd_kernel<LDS, RQ, WIN><<<(P + 255) / 256, 256, 0, s>>>(                                                  \
-        P, D, M, means3D, shs, shs_rest, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix,   \
-        projmatrix, campos, h_x, h_y, tan_fovx, tan_fovy, radii, fc, g.rec, g.gauss_rows, g.tiles_touched, g.wave_rowbase, g.clamped, \
-        g.sh_dir, have_rows ? rows : nullptr, want_sh, dL_dmeans2D, dL_dconics, dL_dopacities, dL_dcolors, dL_dmeans3D, dL_dcov3D, \
-        dL_dshs, dL_dshs_rest, dL_dscales, dL_drots, dL_dfeatures)
+    gaussian_bwd_kernel<LDS, RQ, WIN><<<(f.P + 255) / 256, 256, 0, s>>>(                                                \
+        f.P, f.D, f.M, f.means3D, f.shs, f.shs_rest, f.colors_precomp, f.scales, f.scale_modifier, f.rotations, f.cov3D_precomp, \
+        f.viewmatrix, f.projmatrix, f.cam_pos, f.focal_x, f.focal_y, f.tan_fovx, f.tan_fovy, radii, f.fc, g.rec, g.gauss_rows,   \
+        g.tiles_touched, g.wave_rowbase, g.clamped, g.sh_dir, have_rows ? rows : nullptr, want_sh, d.means2D, d.conics,  \
+        d.opacities, d.colors, d.means3D, d.cov3D, d.shs, d.shs_rest, d.scales, d.rots, d.features)
 #define GS2M_GBW(LDS, RQ)                                                                                               \
     if (few) GS2M_GB(LDS, RQ, 3); else GS2M_GB(LDS, RQ, 2)
 #define GS2M_GBQ(LDS)                                                                                                   \
@@ -642,14 +585,14 @@ void gs2m_launch_gaussian_bwd(int P, int D, int M, const float* means3D, const f
         case 5: GS2M_GBW(LDS, 5); break;                                                                                \
         default: GS2M_GBW(LDS, 6); break;                                                                               \
     }
-    // fewer workgroups than three per CU: occupancy is not the limit, the wave's chain is (force_win: the test hook's choice, api.hip)
-    const bool few = force_win ? force_win == 3 : (P + 255) / 256 < 3 * 256;
-    // dL_dshs == NULL with SH input: the caller does not want dL/dSH (its colour gradient is identically zero, e.g. a view rendered for
+    // fewer workgroups than three per CU: occupancy is not the limit, the wave's chain is (force_win: the test hook's choice, debug_hooks.hip)
+    const bool few = force_win ? force_win == 3 : (f.P + 255) / 256 < 3 * 256;
+    // d.shs == NULL with SH input: the caller does not want dL/dSH (its colour gradient is identically zero, e.g. a view rendered for
     // its depth and normals only): the per-Gaussian kernel skips the 48 stores per Gaussian; everything else is computed as usual
-    const int want_sh = dL_dshs != nullptr ? 1 : 0;
-    const bool lds = want_sh && shs != nullptr && M == 16 &&
-                     (shs_rest ? ((((uintptr_t)shs_rest) | ((uintptr_t)dL_dshs_rest)) & 15) == 0
-                               : ((((uintptr_t)shs) | ((uintptr_t)dL_dshs)) & 15) == 0);
+    const int want_sh = d.shs != nullptr ? 1 : 0;
+    const bool lds = want_sh && f.shs != nullptr && f.M == 16 &&
+                     (f.shs_rest ? ((((uintptr_t)f.shs_rest) | ((uintptr_t)d.shs_rest)) & 15) == 0
+                                 : ((((uintptr_t)f.shs) | ((uintptr_t)d.shs)) & 15) == 0);
     if (lds) { GS2M_GBQ(true) } else { GS2M_GBQ(false) }
 #undef GS2M_GBQ
 #undef GS2M_GBW

@@ -6,47 +6,13 @@
 // computeCov2D :70-104, computeColorFromSH :20-67, in_frustum auxiliary.h:140-162,
 // ndc2Pix/getRect auxiliary.h:40-53) but the data layout is different: instead of six SoA
 // arrays it emits ONE aligned 128-B record per visible Gaussian (common.h) plus the
-// fp32-bit depth key the tiles' lists are ordered by.  This file is compiled with
-// -ffp-contract=off: the values that decide integers (radius, tile rect, depth key) are
-// evaluated in exactly the written order.
+// fp32-bit depth key the tiles' lists are ordered by.  The projection chain itself is gaussian_math.h,
+// shared with the backward.  Compiled with -ffp-contract=off: the values that decide integers
+// (radius, tile rect, depth key) are evaluated in exactly the written order.
 #include "common.h"
+#include "gaussian_math.h"
 
 namespace {
-
-struct M3 {  // column-major 3x3, m[col][row]
-    float m[3][3];
-};
-__device__ __forceinline__ M3 m3_cols(float a, float b, float c, float d, float e, float f, float g, float h, float i) {
-    M3 r;
-    r.m[0][0] = a; r.m[0][1] = b; r.m[0][2] = c;
-    r.m[1][0] = d; r.m[1][1] = e; r.m[1][2] = f;
-    r.m[2][0] = g; r.m[2][1] = h; r.m[2][2] = i;
-    return r;
-}
-__device__ __forceinline__ M3 m3_mul(const M3& A, const M3& B) {
-    M3 R;
-#pragma unroll
-    for (int c = 0; c < 3; c++)
-#pragma unroll
-        for (int r = 0; r < 3; r++)
-            R.m[c][r] = A.m[0][r] * B.m[c][0] + A.m[1][r] * B.m[c][1] + A.m[2][r] * B.m[c][2];
-    return R;
-}
-__device__ __forceinline__ M3 m3_t(const M3& A) {
-    M3 R;
-#pragma unroll
-    for (int c = 0; c < 3; c++)
-#pragma unroll
-        for (int r = 0; r < 3; r++) R.m[c][r] = A.m[r][c];
-    return R;
-}
-
-__constant__ float kSH_C2[5] = {1.0925484305920792f, -1.0925484305920792f, 0.31539156525252005f,
-                                -1.0925484305920792f, 0.5462742152960396f};
-__constant__ float kSH_C3[7] = {-0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f, 0.3731763325901154f,
-                                -0.4570457994644658f, 1.445305721320277f, -0.5900435899266435f};
-#define SH_C0 0.28209479177387814f
-#define SH_C1 0.4886025119029199f
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(hi, max(lo, v)); }
 
@@ -94,14 +60,13 @@ __global__ void __launch_bounds__(256) preprocess_kernel(
     uint32_t out_key = 0xFFFFFFFFu;
     uint2 out_rect = make_uint2(0u, 0u);
 
-    // view-space point (transformPoint4x3), near-plane cull at 0.2
-    const float vx = vm[0] * px + vm[4] * py + vm[8] * pz + vm[12];
-    const float vy = vm[1] * px + vm[5] * py + vm[9] * pz + vm[13];
-    const float vz = vm[2] * px + vm[6] * py + vm[10] * pz + vm[14];
+    // view-space point, near-plane cull (gaussian_math.h)
+    const float3 v = gs2m_view_point(vm, px, py, pz);
+    const float vz = v.z;
     float4 rq[REC_Q];  // the blend record (zeros for a Gaussian that emits nothing: its record is never read)
 #pragma unroll
     for (int k = 0; k < REC_Q; k++) rq[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (inr && vz > 0.2f) {
+    if (inr && vz > kNearZ) {
         const float hx_ = pm[0] * px + pm[4] * py + pm[8] * pz + pm[12];
         const float hy_ = pm[1] * px + pm[5] * py + pm[9] * pz + pm[13];
         const float hw_ = pm[3] * px + pm[7] * py + pm[11] * pz + pm[15];
@@ -113,30 +78,13 @@ __global__ void __launch_bounds__(256) preprocess_kernel(
 #pragma unroll
             for (int k = 0; k < 6; k++) c3[k] = cov3D_precomp[6 * (size_t)idx + k];
         } else {
-            const float sx = scale_modifier * in_s[0], sy = scale_modifier * in_s[1], sz = scale_modifier * in_s[2];
-            const float4 q = in_q;
-            const float r = q.x, x = q.y, y = q.z, z = q.w;
-            M3 S = m3_cols(sx, 0.f, 0.f, 0.f, sy, 0.f, 0.f, 0.f, sz);
-            M3 R = m3_cols(1.f - 2.f * (y * y + z * z), 2.f * (x * y - r * z), 2.f * (x * z + r * y),
-                           2.f * (x * y + r * z), 1.f - 2.f * (x * x + z * z), 2.f * (y * z - r * x),
-                           2.f * (x * z - r * y), 2.f * (y * z + r * x), 1.f - 2.f * (x * x + y * y));
-            M3 Mm = m3_mul(S, R);
-            M3 Sig = m3_mul(m3_t(Mm), Mm);
-            c3[0] = Sig.m[0][0]; c3[1] = Sig.m[0][1]; c3[2] = Sig.m[0][2];
-            c3[3] = Sig.m[1][1]; c3[4] = Sig.m[1][2]; c3[5] = Sig.m[2][2];
+            M3 R, Mm;  // (the backward's: unused here)
+            gs2m_cov3d(scale_modifier * in_s[0], scale_modifier * in_s[1], scale_modifier * in_s[2], in_q, c3, R, Mm);
         }
         // EWA projection of the covariance (no +0.3 low-pass in this fork's forward)
-        const float limx = 1.3f * tan_fovx, limy = 1.3f * tan_fovy;
-        const float txtz = vx / vz, tytz = vy / vz;
-        const float tx = fminf(limx, fmaxf(-limx, txtz)) * vz;
-        const float ty = fminf(limy, fmaxf(-limy, tytz)) * vz;
-        M3 J = m3_cols(focal_x / vz, 0.0f, -(focal_x * tx) / (vz * vz), 0.0f, focal_y / vz, -(focal_y * ty) / (vz * vz),
-                       0.f, 0.f, 0.f);
-        M3 Wm = m3_cols(vm[0], vm[4], vm[8], vm[1], vm[5], vm[9], vm[2], vm[6], vm[10]);
-        M3 T = m3_mul(Wm, J);
-        M3 Vrk = m3_cols(c3[0], c3[1], c3[2], c3[1], c3[3], c3[4], c3[2], c3[4], c3[5]);
-        M3 cov = m3_mul(m3_mul(m3_t(T), m3_t(Vrk)), T);
-        const float cova = cov.m[0][0], covb = cov.m[0][1], covc = cov.m[1][1];
+        Cov2D pr;
+        gs2m_cov2d(v, c3, vm, focal_x, focal_y, tan_fovx, tan_fovy, pr);
+        const float cova = pr.cov.m[0][0], covb = pr.cov.m[0][1], covc = pr.cov.m[1][1];
         const float det = cova * covc - covb * covb;
         if (det != 0.0f) {
             const float det_inv = 1.f / det;
@@ -354,8 +302,7 @@ __global__ void mark_visible_kernel(int P, const float* __restrict__ means3D, co
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= P) return;
     const float px = means3D[3 * idx], py = means3D[3 * idx + 1], pz = means3D[3 * idx + 2];
-    const float vz = vm[2] * px + vm[6] * py + vm[10] * pz + vm[14];
-    present[idx] = vz <= 0.2f ? 0 : 1;
+    present[idx] = gs2m_view_z(vm, px, py, pz) <= kNearZ ? 0 : 1;
 }
 
 // `prefiltered` (auxiliary.h:155-158): the caller promises that no Gaussian is behind the near plane; the reference traps
@@ -366,7 +313,7 @@ __global__ void prefiltered_check_kernel(int P, const float* __restrict__ means3
     bool bad = false;
     if (idx < P) {
         const float px = means3D[3 * idx], py = means3D[3 * idx + 1], pz = means3D[3 * idx + 2];
-        bad = !(vm[2] * px + vm[6] * py + vm[10] * pz + vm[14] > 0.2f);  // the complement of preprocess_kernel's test
+        bad = !(gs2m_view_z(vm, px, py, pz) > kNearZ);  // the complement of preprocess_kernel's test
     }
     if (__builtin_amdgcn_ballot_w64(bad) != 0ull && (threadIdx.x & 63) == 0)
         __hip_atomic_store(flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -378,21 +325,17 @@ void gs2m_launch_prefiltered_check(int P, const float* means3D, const float* vie
     prefiltered_check_kernel<<<(P + 255) / 256, 256, 0, s>>>(P, means3D, viewmatrix, flag);
 }
 
-void gs2m_launch_preprocess(int P, int D, int M, const float* means3D, const float* scales, float scale_modifier,
-                            const float* rotations, const float* opacities, const float* shs, const float* shs_rest,
-                            const float* cov3D_precomp, const float* colors_precomp, const float* features,
-                            const float* viewmatrix, const float* projmatrix, const float* cam_pos, int W, int H,
-                            float tan_fovx, float tan_fovy, float focal_x, float focal_y, int tiles_x, int tiles_y,
-                            int* radii, int* observe_zero, const GeomState& g, int shrink, const ZeroJobs& zero, hipStream_t s) {
+void gs2m_launch_preprocess(const RasterFrame& f, int* radii, int* observe_zero, const GeomState& g, int shrink, const ZeroJobs& zero,
+                            hipStream_t s) {
 #define GS2M_PRE(LDS)                                                                                                  \
-    preprocess_kernel<LDS><<<(P + 255) / 256, 256, 0, s>>>(P, D, M, means3D, scales, scale_modifier, rotations, opacities, \
-                                                           shs, shs_rest, cov3D_precomp, colors_precomp, features, viewmatrix,      \
-                                                           projmatrix, cam_pos, W, H, tan_fovx, tan_fovy, focal_x,        \
-                                                           focal_y, tiles_x, tiles_y, shrink, radii, observe_zero, g.rec,             \
-                                                           g.tiles_touched, g.rect, g.block_tt, g.block_hu, g.depth_key, g.clamped, g.sh_dir, zero)
-    // split SH (shs = DC, shs_rest = the other 15 coefficients) exists in the LDS-staged form only: api.hip checks
-    const bool lds = colors_precomp == nullptr && shs != nullptr && M == 16 &&
-                     (shs_rest ? (((uintptr_t)shs_rest) & 15) == 0 : (((uintptr_t)shs) & 15) == 0);
+    preprocess_kernel<LDS><<<(f.P + 255) / 256, 256, 0, s>>>(                                                          \
+        f.P, f.D, f.M, f.means3D, f.scales, f.scale_modifier, f.rotations, f.opacities, f.shs, f.shs_rest, f.cov3D_precomp,   \
+        f.colors_precomp, f.features, f.viewmatrix, f.projmatrix, f.cam_pos, f.W, f.H, f.tan_fovx, f.tan_fovy, f.focal_x,      \
+        f.focal_y, f.tiles_x, f.tiles_y, shrink, radii, observe_zero, g.rec, g.tiles_touched, g.rect, g.block_tt, g.block_hu, \
+        g.depth_key, g.clamped, g.sh_dir, zero)
+    // split SH (shs = DC, shs_rest = the other 15 coefficients) exists in the LDS-staged form only: the entry points check
+    const bool lds = f.colors_precomp == nullptr && f.shs != nullptr && f.M == 16 &&
+                     (f.shs_rest ? (((uintptr_t)f.shs_rest) & 15) == 0 : (((uintptr_t)f.shs) & 15) == 0);
     if (lds) GS2M_PRE(true);
     else GS2M_PRE(false);
 #undef GS2M_PRE

@@ -611,6 +611,16 @@ int fill_stack(MipStack& M, int levels, const float* const* tex, float* const* g
     return GS2M_OK;
 }
 
+// The backward's merge and table key is (level << 24) | texel (run_merge, CombineTable): a level whose texel count needs
+// more than 24 bits would be decoded by `drain` as another level at another offset.  Refused before any launch.
+constexpr long long KEY_TEXELS = 1LL << 24;
+bool cube_fits_key(int w) { return 6LL * w * w <= KEY_TEXELS; }
+bool stack_fits_key(const int* width, int levels) {
+    for (int l = 0; l < levels; l++)
+        if (!cube_fits_key(width[l])) return false;
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -633,6 +643,7 @@ int gs2m_texture_cube_backward(int n, int channels, int levels, float* const* gr
     MipStack M;
     const int rc = fill_stack(M, levels, nullptr, grad_tex, width, true);
     if (rc != GS2M_OK) return rc;
+    if (!stack_fits_key(width, levels)) return GS2M_ERR_UNSUPPORTED;
     if (mip_level_bias) return launch_bwd<1>(channels, n, image_width, M, 0, dirs, mip_level_bias, dL_dout, (hipStream_t)stream);
     return launch_bwd<0>(channels, n, image_width, M, 0, dirs, nullptr, dL_dout, (hipStream_t)stream);
 }
@@ -650,6 +661,7 @@ int gs2m_texture_2d_clamp_backward(int n, int channels, int width, int height, f
                                    const float* dL_dout, void* stream) {
     if (n == 0) return GS2M_OK;
     if (n < 0 || width < 1 || height < 1 || !grad_tex || !uv || !dL_dout) return GS2M_ERR_INVALID_ARG;
+    if ((long long)width * height > KEY_TEXELS) return GS2M_ERR_UNSUPPORTED;
     MipStack M;
     M.levels = 1; M.tex[0] = nullptr; M.grad[0] = grad_tex; M.width[0] = width;
     return launch_bwd<2>(channels, n, 0, M, height, uv, nullptr, dL_dout, (hipStream_t)stream);
@@ -686,6 +698,7 @@ int gs2m_pbr_shade_backward(int n, const float* normals, const float* view_dirs,
     MipStack M;
     int rc = fill_stack(M, levels, specular, nullptr, width, false);
     if (rc != GS2M_OK) return rc;
+    if (!stack_fits_key(width, levels) || !cube_fits_key(diffuse_width)) return GS2M_ERR_UNSUPPORTED;
     M.lds_floats = 0;
     for (int l = 0; l < levels; l++) {
         if (!dL_dspecular[l]) return GS2M_ERR_INVALID_ARG;

@@ -11,6 +11,8 @@
  * Backward: gradients to albedo, metallic (optional) and -- accumulated, zero them first -- the diffuse map and every level
  * of the specular stack; normals, view directions and roughness get none (pbr_render detaches them).  `image_width`: the pixels
  * are an image of that width in row-major order (n a multiple of it) -- lets the backward work on 2-D pixel tiles -- or 0.
+ * The backward refuses (GS2M_ERR_UNSUPPORTED, nothing launched) a specular level or a diffuse map with 6 * width^2 > 2^24
+ * (width >= 1673): its accumulation key holds the texel index in 24 bits (gs2m_texture.h).
  * Device pointers, fp32; pixel arrays are (n, 3) / (n, 1); `specular`, `dL_dspecular`, `width` are HOST arrays of `levels`
  * entries.  Asynchronous on `stream`; return GS2M_OK (0) or a negative GS2M_ERR_* code (gs2m_raster.h). */
 #ifndef GS2M_PBR_H

@@ -16,6 +16,9 @@
  * All pointers are DEVICE pointers, fp32; textures are channels-last: cube level l is (6, width[l], width[l], C),
  * 2-D is (height, width, C); 1 <= C <= 4.  `tex`, `grad_tex`, `width` are HOST arrays of `levels` entries
  * (read before the call returns).  Gradient tensors are ACCUMULATED into (atomic adds): zero them first.
+ * The backward keys its accumulation by (level, texel index) with 24 bits for the index: a cube level with
+ * 6 * width^2 > 2^24 (width >= 1673) or a 2-D texture with width * height > 2^24 is refused with GS2M_ERR_UNSUPPORTED
+ * before anything is launched (the forward has no such limit).
  * Asynchronous on `stream`; return GS2M_OK (0) or a negative GS2M_ERR_* code (gs2m_raster.h). */
 #ifndef GS2M_TEXTURE_H
 #define GS2M_TEXTURE_H

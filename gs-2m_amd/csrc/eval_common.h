@@ -59,6 +59,52 @@ static inline int gs2m_read_back(hipStream_t s, std::initializer_list<ReadBack> 
 long long gs2m_scan_blocks(long long n);
 hipError_t gs2m_scan_u64(u64* a, long long n, u64* bsum, hipStream_t s);
 
+// ---- hashed uniform grid (built by mesh_eval.hip: gs2m_eval_grid_build; read there and by tnt_clouds.hip) ----
+// The cell (floor(p / cell) per axis) hashes to a bucket of 2^bits; a bucket holds every point whose cell hashes to it, so a
+// reader that needs one cell's points alone compares each candidate's own cell.
+constexpr int CELL_LIMIT = 1 << 30;
+
+__device__ __forceinline__ int cell_coord(double x, double inv) {
+    const double f = floor(x * inv);
+    return f < -(double)CELL_LIMIT ? -CELL_LIMIT : (f > (double)CELL_LIMIT ? CELL_LIMIT : (int)f);  // NaN -> the upper bound
+}
+
+__device__ __forceinline__ uint32_t hash3(int x, int y, int z, uint32_t mask) {
+    uint64_t h = (uint64_t)(uint32_t)x * 0x9E3779B97F4A7C15ull;
+    h ^= (uint64_t)(uint32_t)y * 0xC2B2AE3D27D4EB4Full;
+    h ^= (uint64_t)(uint32_t)z * 0x165667B19E3779F9ull;
+    h ^= h >> 31;
+    h *= 0xBF58476D1CE4E5B9ull;
+    h ^= h >> 29;
+    return (uint32_t)h & mask;
+}
+
+static inline int grid_bits(long long n) {
+    int k = 10;
+    while (k < 28 && (1ll << k) < n) k++;
+    return k;
+}
+
+struct Grid {
+    double* spts;    // n x 3: the points in bucket order
+    uint32_t* sidx;  // n: their original indices
+    uint32_t* start; // 2^bits + 1: first sorted slot of every bucket
+    uint8_t* occ;    // 2^bits: 1 = a coarse cell hashing here holds a point
+    int bits;
+    size_t bytes;
+};
+static inline Grid carve_grid(char* base, long long n) {
+    Carver c{base, 0};
+    Grid g;
+    g.bits = grid_bits(n);
+    const size_t nb = (size_t)1 << g.bits;
+    g.spts = c.take<double>(3 * (size_t)n);
+    g.sidx = c.take<uint32_t>(n);
+    g.start = c.take<uint32_t>(nb + 1);
+    g.occ = c.take<uint8_t>(nb);
+    g.bytes = c.off;
+    return g;
+}
 // a triangle's vertex indices against the vertex count; err[0] = 1 tells the host of one out of range
 __device__ __forceinline__ bool tri_in_range(int a, int b, int c, long long nv, int* __restrict__ err) {
     if (a < 0 || b < 0 || c < 0 || a >= nv || b >= nv || c >= nv) {

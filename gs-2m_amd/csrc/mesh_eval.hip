@@ -23,7 +23,6 @@ namespace {
 constexpr int TILE = 1024;           // scan: entries per workgroup (256 threads x 4)
 constexpr int COARSE_SHIFT = 3;      // coarse cell = 8^3 fine cells
 constexpr int COARSE_SHELLS_MAX = 24;
-constexpr int CELL_LIMIT = 1 << 30;
 
 // ---- device-wide exclusive scan of u64 counts (in place; a[n] = total): gs2m_scan_u64 of eval_common.h ----
 
@@ -214,49 +213,8 @@ RowWs carve_row(char* base, long long nr) {
     return w;
 }
 
-// ---- hashed uniform grid ----
+// ---- hashed uniform grid (its layout and hash: eval_common.h) ----
 
-__device__ __forceinline__ int cell_coord(double x, double inv) {
-    const double f = floor(x * inv);
-    return f < -(double)CELL_LIMIT ? -CELL_LIMIT : (f > (double)CELL_LIMIT ? CELL_LIMIT : (int)f);  // NaN -> the upper bound
-}
-
-__device__ __forceinline__ uint32_t hash3(int x, int y, int z, uint32_t mask) {
-    uint64_t h = (uint64_t)(uint32_t)x * 0x9E3779B97F4A7C15ull;
-    h ^= (uint64_t)(uint32_t)y * 0xC2B2AE3D27D4EB4Full;
-    h ^= (uint64_t)(uint32_t)z * 0x165667B19E3779F9ull;
-    h ^= h >> 31;
-    h *= 0xBF58476D1CE4E5B9ull;
-    h ^= h >> 29;
-    return (uint32_t)h & mask;
-}
-
-int grid_bits(long long n) {
-    int k = 10;
-    while (k < 28 && (1ll << k) < n) k++;
-    return k;
-}
-
-struct Grid {
-    double* spts;    // n x 3: the points in bucket order
-    uint32_t* sidx;  // n: their original indices
-    uint32_t* start; // 2^bits + 1: first sorted slot of every bucket
-    uint8_t* occ;    // 2^bits: 1 = a coarse cell hashing here holds a point
-    int bits;
-    size_t bytes;
-};
-Grid carve_grid(char* base, long long n) {
-    Carver c{base, 0};
-    Grid g;
-    g.bits = grid_bits(n);
-    const size_t nb = (size_t)1 << g.bits;
-    g.spts = c.take<double>(3 * (size_t)n);
-    g.sidx = c.take<uint32_t>(n);
-    g.start = c.take<uint32_t>(nb + 1);
-    g.occ = c.take<uint8_t>(nb);
-    g.bytes = c.off;
-    return g;
-}
 struct BuildWs {
     uint32_t* keys;  // max(n, 1), as the sort's arrays
     SortBufs sort;

@@ -157,16 +157,28 @@ def read_ply(file):
     return verts, tris
 
 
-def write_point_cloud(file, points, colors=None):
-    """Binary little-endian PLY: double x y z, uchar red green blue (colour * 255 rounded to nearest)."""
+def write_point_cloud(file, points, colors=None, normals=None):
+    """Binary little-endian PLY: double x y z, uchar red green blue (colour * 255 rounded to nearest).  With `normals` the file
+    is what Open3D's write_point_cloud writes by default: its comment line, then double x y z, double nx ny nz, uchar red
+    green blue."""
     p = np.asarray(points, np.float64).reshape(-1, 3)
     fields = [("x", "<f8"), ("y", "<f8"), ("z", "<f8")]
+    if normals is not None:
+        fields += [("nx", "<f8"), ("ny", "<f8"), ("nz", "<f8")]
     if colors is not None:
         fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
     a = np.zeros(len(p), np.dtype(fields))
     for k, n in enumerate("xyz"):
         a[n] = p[:, k]
-    head = f"ply\nformat binary_little_endian 1.0\nelement vertex {len(p)}\nproperty double x\nproperty double y\nproperty double z\n"
+    head = "ply\nformat binary_little_endian 1.0\n" + ("comment Created by Open3D\n" if normals is not None else "")
+    head += f"element vertex {len(p)}\nproperty double x\nproperty double y\nproperty double z\n"
+    if normals is not None:
+        nrm = np.asarray(normals, np.float64).reshape(-1, 3)
+        if len(nrm) != len(p):
+            raise ValueError(f"write_point_cloud: {len(nrm)} normals for {len(p)} points")
+        for k, n in enumerate(("nx", "ny", "nz")):
+            a[n] = nrm[:, k]
+        head += "property double nx\nproperty double ny\nproperty double nz\n"
     if colors is not None:
         c = np.clip(np.rint(np.asarray(colors, np.float64).reshape(-1, 3) * 255.0), 0, 255).astype(np.uint8)
         for k, n in enumerate(("red", "green", "blue")):

@@ -182,6 +182,9 @@ SIGNATURES = {
     "gs2m_tnt_icp_workspace_bytes": (i, [p]),
     "gs2m_tnt_icp_moments": (i, [ll, p, ll, p, p, p, p, p, s]),
     "gs2m_tnt_histogram": (i, [ll, p, i, p, p, s]),
+    "gs2m_tnt_knn_normals_workspace_bytes": (i, [ll, p]),
+    "gs2m_tnt_knn_normals": (i, [ll, p, d, p, i, p, p, p, s]),
+    "gs2m_tnt_distance_colors": (i, [ll, p, d, p, p, s]),
     # include/gs2m_metrics.h
     "gs2m_image_metrics_workspace_bytes": (i, [i, i, i, i, p]),
     "gs2m_image_metrics": (i, [i, i, i, i, p, p, p, ll, p, p, s]),

@@ -9,7 +9,10 @@ the 3 x 3 similarity update is numpy on the host.  Every buffer is a torch tenso
 reference computes, the contract is Open3D's behaviour as read, unpinned: Open3D is not part of this stack.
 
     python gs-2m_amd/gs2m_tnt_eval.py --dataset-dir TNT/Barn --traj-path TNT/Barn/Barn_COLMAP_SfM.log --ply-path tsdf_post.ply
-writes evaluation/{results.json, Barn.precision.txt, Barn.recall.txt, Barn.prf_tau_plotstr.txt} beside the ply.
+writes evaluation/{results.json, Barn.precision.txt, Barn.recall.txt, Barn.prf_tau_plotstr.txt, Barn.precision.ply,
+Barn.recall.ply} beside the ply: the two scored clouds, each point with its 20-neighbour normal and hot_r of its distance to the
+other cloud, capped at 3 tau (csrc/tnt_clouds.hip; --no-clouds skips them).  --plot adds plot.py's PR_<scene>_@d_th_0_<tau>.png
+and .pdf (matplotlib, on the host).
 """
 import argparse
 import ctypes as C
@@ -28,13 +31,15 @@ import torch
 
 import gs2m_native as N
 from gs2m_eval_util import (TargetGrid, compact as _compact, device as _dev, grid_cell, masked_mean, points as _points,  # noqa: F401
-                            ptr as _ptr, read_ply, triangles_i32, workspace as _ws, workspace_for)
+                            ptr as _ptr, read_ply, triangles_i32, workspace as _ws, workspace_for, write_point_cloud)
 
 # scripts/eval_tnt/config.py: the distance threshold tau of every scene
 SCENES_TAU = {"Barn": 0.01, "Caterpillar": 0.005, "Church": 0.025, "Courthouse": 0.025, "Ignatius": 0.003, "Meetingroom": 0.01,
               "Truck": 0.005}
 MAX_POINT_NUMBER = 4e6  # registration.py: clouds above it are thinned by rows for the last ICP stage
 PLOT_STRETCH = 5
+KNN = 20            # evaluation.py: estimate_normals(KDTreeSearchParamKNN(knn=20))
+COLOR_STRETCH = 3   # evaluation.py: write_color_distances(..., 3 * threshold)
 _AXES = {"X": 0, "Y": 1, "Z": 2}
 
 
@@ -271,10 +276,54 @@ def histogram(dist, edges, device=None):
     return counts[:len(e) - 1].cpu().numpy()
 
 
-def evaluate(source, gt, T, volume, tau, details=False, device=None):
+def _device_tensor(t, name, who):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise RuntimeError(f"{who}: `{name}` must be a tensor on a HIP device; there is no CPU path")
+    return t
+
+
+def knn_normals(points, k=KNN, device=None, return_index=False, cell=None):
+    """estimate_normals(KDTreeSearchParamKNN(knn=k)) of the cloud `points` ((n, 3) device tensor): per point the unit
+    eigenvector of the smallest eigenvalue of its k nearest neighbours' covariance (the point itself among them, ties to the
+    lower index; include/gs2m_tnt.h states the rules and the fixed sign).  cell: the grid's edge (default: grid_cell over the
+    cloud's extent).  -> (n, 3) fp64 device tensor; with `return_index` also the (n, k) int64 neighbour indices in (d2, index)
+    order, -1 beyond min(k, n)."""
+    dev = _dev(device)
+    p = _points(_device_tensor(points, "points", "knn_normals"), dev)
+    n = len(p)
+    if not 1 <= int(k) <= 32:  # the library's own refusal, whatever the cloud
+        N.launch("gs2m_tnt_knn_normals", dev, n, None, 1.0, None, int(k), None, None, None)
+    normals = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    index = torch.empty((n, int(k)), dtype=torch.int64, device=dev) if return_index else None
+    if n:
+        if not cell:
+            lo, hi = torch.aminmax(p, dim=0)
+            ext = float((hi - lo).max())
+            cell = grid_cell(p, ext) if ext > 0 and math.isfinite(ext) else 1.0
+        grid = TargetGrid(p, cell, cell=cell, device=dev)
+        ws = workspace_for("gs2m_tnt_knn_normals_workspace_bytes", dev, n)
+        N.launch("gs2m_tnt_knn_normals", dev, n, _ptr(p), float(cell), _ptr(grid.grid), int(k), _ptr(ws), _ptr(normals), _ptr(index))
+    return (normals, index) if return_index else normals
+
+
+def distance_colors(dist, max_distance, device=None):
+    """write_color_distances' colours: hot_r(min(d, max_distance) / max_distance) as matplotlib indexes its 256 entries, each
+    channel round(c * 255).  dist: (n,) device tensor (+inf takes the cap's colour; NaN is refused).  -> (n, 3) uint8 device
+    tensor."""
+    dev = _dev(device)
+    d = _device_tensor(dist, "dist", "distance_colors").to(dev, torch.float64).reshape(-1).contiguous()
+    rgb = torch.empty((len(d), 3), dtype=torch.uint8, device=dev)
+    ws = _ws(8, dev)
+    N.launch("gs2m_tnt_distance_colors", dev, len(d), _ptr(d), float(max_distance), _ptr(ws), _ptr(rgb))
+    return rgb
+
+
+def evaluate(source, gt, T, volume, tau, details=False, device=None, clouds=False):
     """EvaluateHisto: source moved by T, both clouds cropped and voxel-downsampled at tau / 2, distances capped at 5 tau (+inf
     there: every number below treats values from 5 tau on alike).  -> dict(precision, recall, fscore, n_source, n_target,
-    edges, cum_source, cum_target); with `details` also the clouds and distances (numpy)."""
+    edges, cum_source, cum_target); with `details` also the clouds and distances (numpy); with `clouds` also "clouds": the
+    precision cloud (the source, coloured by distance1) and the recall cloud (the target, by distance2) as device tensors:
+    dict(precision / recall: dict(points, normals, colors)), colours capped at 3 tau."""
     dev = _dev(device)
     g = _gt(gt, volume, dev)
     s = voxel_downsample(crop(transform(source, T, device=dev), volume, dev), tau / 2.0, dev)
@@ -296,6 +345,16 @@ def evaluate(source, gt, T, volume, tau, details=False, device=None):
            "edges": edges, "cum_source": cum1, "cum_target": cum2}
     if details:
         out["arrays"] = {"source": s.cpu().numpy(), "target": t.cpu().numpy(), "distance1": d1.cpu().numpy(), "distance2": d2.cpu().numpy()}
+    if clouds:  # after everything above, which it leaves as it is; timed on its own
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        # a voxel downsample at tau / 2 leaves about one point per tau / 2 of surface: cells of three spacings hold the 20
+        # neighbours within the first shell for most points
+        out["clouds"] = {name: {"points": p, "normals": knn_normals(p, KNN, dev, cell=1.5 * tau),
+                                "colors": distance_colors(d, COLOR_STRETCH * tau, dev)}
+                         for name, p, d in (("precision", s, d1), ("recall", t, d2))}
+        torch.cuda.synchronize(dev)
+        out["clouds_ms"] = 1e3 * (time.perf_counter() - t0)
     return out
 
 
@@ -305,11 +364,41 @@ def rotation_y(theta):
     return np.array([[c, 0, s, 0], [0, 1, 0, 0], [-s, 0, c, 0], [0, 0, 0, 1]], np.float64)
 
 
+def plot_graph(scene, fscore, tau, edges, cum_source, cum_target, out_dir, stretch=PLOT_STRETCH):
+    """plot.py's plot_graph: precision (red) and recall (blue) in per cent over the distance, tau dashed, as
+    PR_<scene>_@d_th_0_<tau * 10000, four digits>.png and .pdf in out_dir.  matplotlib is imported here, with the Agg backend.
+    -> (png, pdf)."""
+    import matplotlib
+    matplotlib.use("Agg")
+    import matplotlib.pyplot as plt
+    fig = plt.figure(figsize=(14, 7))
+    ax = fig.add_subplot(111)
+    ax.plot(np.asarray(edges)[1:], np.asarray(cum_source) * 100, c="red", label="precision", linewidth=2.0)
+    ax.plot(np.asarray(edges)[1:], np.asarray(cum_target) * 100, c="blue", label="recall", linewidth=2.0)
+    ax.grid(True)
+    ax.set_title("Precision and Recall: " + scene + ", " + "%02.2f f-score" % (fscore * 100))
+    ax.axvline(x=tau, c="black", ls="dashed", linewidth=2.0)
+    ax.set_ylabel("# of points (%)", fontsize=15)
+    ax.set_xlabel("Meters", fontsize=15)
+    ax.axis([0, tau * stretch, 0, 100])
+    box = ax.get_position()
+    ax.set_position([box.x0, box.y0, box.width * 0.8, box.height])
+    ax.legend(loc="center left", bbox_to_anchor=(1, 0.5), fontsize="medium")
+    stem = os.path.join(out_dir, "PR_{0}_@d_th_0_{1}".format(scene, "%04d" % (tau * 10000)))
+    fig.savefig(stem + ".png", format="png", bbox_inches="tight")
+    fig.savefig(stem + ".pdf", format="pdf", bbox_inches="tight")
+    plt.close(fig)
+    return stem + ".png", stem + ".pdf"
+
+
 def evaluate_scene(vertices, triangles, gt_points, volume, tau, est_traj, gt_traj, gt_trans, scene="scene", out_dir=None,
-                   rotate_y=0.0, details=False, device=None):
+                   rotate_y=0.0, details=False, device=None, clouds=None, plot=False):
     """run.py's run_evaluation.  vertices (V, 3), triangles (F, 3): the mesh; gt_points (M, 3); volume: the crop (dict);
     est_traj, gt_traj: (n, 4, 4) poses; gt_trans (4, 4).  -> dict(precision, recall, fscore, tau, counts, the stages, the final
-    transformation, times in ms; cum_source / cum_target; with `details` the arrays); out_dir: the reference's files."""
+    transformation, times in ms; cum_source / cum_target; with `details` the arrays); out_dir: the reference's files:
+    results.json, the three .txt files, with `clouds` (default: when there is an out_dir) <scene>.precision.ply and
+    <scene>.recall.ply, with `plot` plot_graph's figure.  ms["clouds"]: the normals and colours on the device (the score's time
+    does not hold them); writing the two files is host time and is not in it."""
     dev = _dev(device)
     times = {}
     torch.cuda.synchronize(dev)
@@ -326,9 +415,12 @@ def evaluate_scene(vertices, triangles, gt_points, volume, tau, est_traj, gt_tra
     for k, st in enumerate(stages):
         times[f"register{k}"] = st["ms"]
     t0 = time.perf_counter()
-    r = evaluate(source, g, T, volume, tau, details, dev)
+    clouds = out_dir is not None if clouds is None else bool(clouds)
+    r = evaluate(source, g, T, volume, tau, details, dev, clouds)
     torch.cuda.synchronize(dev)
-    times["score"] = round(1e3 * (time.perf_counter() - t0), 3)
+    times["score"] = round(1e3 * (time.perf_counter() - t0) - r.get("clouds_ms", 0.0), 3)
+    if clouds:
+        times["clouds"] = round(r["clouds_ms"], 3)
     out = {"precision": r["precision"], "recall": r["recall"], "fscore": r["fscore"], "tau": tau, "scene": scene,
            "n_vertices": int(len(v)), "n_triangles": int(len(triangles)), "n_source": int(len(source)), "n_gt": int(g.n_raw),
            "n_gt_cropped": int(len(g.cropped)), "n_source_scored": r["n_source"], "n_target_scored": r["n_target"],
@@ -340,9 +432,17 @@ def evaluate_scene(vertices, triangles, gt_points, volume, tau, est_traj, gt_tra
         np.savetxt(os.path.join(out_dir, f"{scene}.recall.txt"), r["cum_target"])
         np.savetxt(os.path.join(out_dir, f"{scene}.precision.txt"), r["cum_source"])
         np.savetxt(os.path.join(out_dir, f"{scene}.prf_tau_plotstr.txt"), np.array([r["precision"], r["recall"], r["fscore"], tau, PLOT_STRETCH]))
+        if clouds:
+            for name, c in r["clouds"].items():
+                write_point_cloud(os.path.join(out_dir, f"{scene}.{name}.ply"), c["points"].cpu().numpy(),
+                                  c["colors"].cpu().numpy() / 255.0, c["normals"].cpu().numpy())
+        if plot:
+            plot_graph(scene, r["fscore"], tau, r["edges"], r["cum_source"], r["cum_target"], out_dir)
     out["edges"], out["cum_source"], out["cum_target"] = r["edges"], r["cum_source"], r["cum_target"]
     if details:
         out["arrays"] = r["arrays"]
+    if clouds:
+        out["clouds"] = r["clouds"]
     return out
 
 
@@ -398,6 +498,8 @@ def main(argv=None):
     ap.add_argument("--scene", default="", help="default: the dataset folder's name")
     ap.add_argument("--tau", type=float, default=None, help="the distance threshold (default: the scene's)")
     ap.add_argument("--rotate-y", type=float, default=0.0, help="rotate the mesh about y first (run_tnt.py: pi / 8 for Truck)")
+    ap.add_argument("--no-clouds", action="store_true", help="do not write <scene>.precision.ply and <scene>.recall.ply")
+    ap.add_argument("--plot", action="store_true", help="write the precision / recall figure (png and pdf; needs matplotlib)")
     a = ap.parse_args(argv)
     scene = a.scene or os.path.basename(os.path.normpath(a.dataset_dir))
     if a.tau is None and scene not in SCENES_TAU:
@@ -408,7 +510,8 @@ def main(argv=None):
     gt, _ = read_ply(os.path.join(a.dataset_dir, scene + ".ply"))
     r = evaluate_scene(verts, tris, gt, read_crop_volume(os.path.join(a.dataset_dir, scene + ".json")), tau,
                        read_trajectory(a.traj_path), read_trajectory_log(os.path.join(a.dataset_dir, scene + "_COLMAP_SfM.log")),
-                       np.loadtxt(os.path.join(a.dataset_dir, scene + "_trans.txt")), scene=scene, out_dir=out_dir, rotate_y=a.rotate_y)
+                       np.loadtxt(os.path.join(a.dataset_dir, scene + "_trans.txt")), scene=scene, out_dir=out_dir, rotate_y=a.rotate_y,
+                       clouds=not a.no_clouds, plot=a.plot)
     print(f"[>] {scene}: tau {tau:.3f} precision {r['precision']:.4f} recall {r['recall']:.4f} f-score {r['fscore']:.4f}")
     return r
 

@@ -71,6 +71,35 @@ int gs2m_tnt_icp_moments(long long n, const double* source, long long n_targets,
 int gs2m_tnt_histogram(long long n, const double* dist, int n_edges, const double* edges, unsigned long long* counts,
                        void* stream);
 
+/* ---- the error-coloured clouds (tnt_clouds.hip): EvaluateHisto's <scene>.precision.ply and <scene>.recall.ply ----
+ *
+ *   Neighbours   of point i: the min(k, n) points of the cloud with the smallest (d2, index), d2 = (dx dx + dy dy) + dz dz
+ *                evaluated as written; point i itself is among them at d2 = 0 (Open3D's KNN search includes the query point),
+ *                and equal d2 goes to the lower index.
+ *   Normal       the unit eigenvector of the smallest eigenvalue of the neighbours' covariance about their own mean (two passes
+ *                in neighbour order; Open3D accumulates raw moments in one), by 8 cyclic Jacobi sweeps.  Open3D leaves the sign
+ *                to its solver; here it is fixed: n . (0, 0, 1) >= 0, and where that product is exactly 0 the first non-zero
+ *                component is positive.  Fewer than 3 neighbours, a zero covariance or a non-finite vector: (0, 0, 1), Open3D's
+ *                fallback.
+ *   Colour       x = min(d, max_distance) / max_distance; entry min(trunc(x * 256), 255) of matplotlib's hot_r table
+ *                (csrc/tnt_hot_r.h), each channel stored as round-half-even(c * 255). */
+
+/* Bytes of gs2m_tnt_knn_normals' workspace for n points (HOST output). */
+int gs2m_tnt_knn_normals_workspace_bytes(long long n, long long* bytes);
+
+/* normals (n, 3) of the cloud pts (n, 3) from each point's k nearest neighbours; knn_index (n, k) long long or NULL: the
+ * neighbours in (d2, index) order, -1 beyond min(k, n).  grid: gs2m_eval_grid_build's (gs2m_eval.h) over pts itself with the
+ * edge `cell`.  1 <= k <= 32 or GS2M_ERR_INVALID_ARG (nothing is launched).  Waits for the stream once (the cloud's box in
+ * cells is read back): GS2M_ERR_INVALID_ARG for a NaN or infinite coordinate, GS2M_ERR_UNSUPPORTED when the box is wider than
+ * 65535 cells on an axis (the walk's shells are bounded by the box). */
+int gs2m_tnt_knn_normals(long long n, const double* pts, double cell, const void* grid, int k, void* ws, double* normals,
+                         long long* knn_index, void* stream);
+
+/* rgb (n, 3) unsigned char: the colour (see above) of every distance; +inf takes the cap's colour.  max_distance > 0 and
+ * finite.  ws: 8 bytes of device scratch.  Waits for the stream: GS2M_ERR_INVALID_ARG when a distance is NaN (rgb is then
+ * undefined). */
+int gs2m_tnt_distance_colors(long long n, const double* dist, double max_distance, void* ws, unsigned char* rgb, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

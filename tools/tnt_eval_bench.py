@@ -2,12 +2,14 @@
 the ground disc, 49 orbit views) fused and extracted as the mesh, `--gt` ground-truth points on the analytic surface with
 scanner-like noise (tau / 10), a camera trajectory that carries a known similarity error (2 degrees, 1 % scale, a few tau)
 into the initial transform, and a concave crop polygon along Y.  One warm-up evaluation, then a timed one; prints one JSON
-line: the GPU stage times (load, the three registration stages with their iterations, score; each ends with a device
-synchronisation), the point counts, the scores, how far the recovered transform leaves analytic surface points from the
+line: the GPU stage times (load, the three registration stages with their iterations, score, clouds -- the 20-neighbour normals
+and the distance colours of the two scored clouds; each ends with a device synchronisation), the point counts, the scores, how far the recovered transform leaves analytic surface points from the
 surface (the scene is symmetric about its vertical axis, so the offset's rotation about that axis cannot be observed and
 stays in the transform: the transform itself is not compared with the identity), and the CPU
 restatement's (tests/tnt_eval_ref.py: numpy + scipy's cKDTree -- NOT the reference's evaluator, which needs Open3D) time on the
-stated fraction of the job.  There is no reference timing to compare with: no threshold.  All data is synthetic.
+stated fraction of the job, and the host formulation of the clouds stage (scipy's cKDTree.query(k=20) on all cores and numpy's
+batched eigh, standing in for Open3D's estimate_normals) for `--cpu-points` queries of each scored cloud against the whole
+cloud.  There is no reference timing to compare with: no threshold.  All data is synthetic.
 
     python tools/tnt_eval_bench.py [--views 49] [--voxel 0.004] [--tau 0.01] [--gt 4000000]
 
@@ -106,7 +108,7 @@ def main():
     pa = np.linspace(0, 2 * np.pi, 8, endpoint=False)
     vol = {"orthogonal_axis": "Y", "axis_min": -2.0, "axis_max": 1.6,
            "bounding_polygon": np.stack([r8 * np.cos(pa), np.zeros(8), 6.0 + r8 * np.sin(pa)], axis=1)}
-    run = lambda: E.evaluate_scene(mesh.vertices, mesh.triangles, gt, vol, tau, est, ref, np.eye(4), scene="synthetic")  # noqa: E731
+    run = lambda: E.evaluate_scene(mesh.vertices, mesh.triangles, gt, vol, tau, est, ref, np.eye(4), scene="synthetic", clouds=True)  # noqa: E731
     run()
     torch.cuda.reset_peak_memory_stats()
     r = run()
@@ -127,6 +129,21 @@ def main():
     t0 = time.perf_counter()
     R.nearest(down, tgt, 5 * tau, kdtree=True)
     t_nn = time.perf_counter() - t0
+    # the clouds stage's host formulation on a part of the same clouds
+    from scipy.spatial import cKDTree
+    host = {}
+    for name, c in r["clouds"].items():
+        pts = c["points"].cpu().numpy()
+        q = pts[: a.cpu_points]
+        t0 = time.perf_counter()
+        _, idx = cKDTree(pts).query(q, k=20, workers=-1)
+        t_knn = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        nb = pts[idx]
+        nb = nb - nb.mean(axis=1, keepdims=True)
+        np.linalg.eigh(np.einsum("nki,nkj->nij", nb, nb))
+        t_eig = time.perf_counter() - t0
+        host[name] = {"points": len(pts), "queries": len(q), "tree_and_knn_ms": round(1e3 * t_knn, 1), "eigh_ms": round(1e3 * t_eig, 1)}
     print(json.dumps({
         "workload": f"{a.views} views {a.width}x{a.height}, voxel {a.voxel}, synthetic surface scene, tau {tau}, {a.gt} ground-truth points, "
                     "initial transform off by 2 degrees / 1 % / a few tau",
@@ -135,6 +152,7 @@ def main():
         "counts": {k: r[k] for k in ("n_vertices", "n_triangles", "n_source", "n_gt", "n_gt_cropped", "n_source_scored", "n_target_scored")},
         "scores": {k: r[k] for k in ("precision", "recall", "fscore")},
         "surface_to_surface_under_T": {"mean": float(off_surface.mean()), "max": float(off_surface.max()), "tau": tau},
+        "clouds_host_formulation_not_open3d": host,
         "cpu_restatement_not_the_reference": {"gt_points": len(part), "of": a.gt, "crop_voxel_ms": round(1e3 * t_down, 1),
                                               "nearest_queries": len(down), "nearest_targets": len(tgt), "nearest_ms": round(1e3 * t_nn, 1)}}))
 

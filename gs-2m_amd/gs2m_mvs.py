@@ -256,12 +256,20 @@ def patch_ncc_roughness(pixels, normals, dists, ref_cam, near_cam, ncc_scale, pa
     if not pixels.is_cuda:
         raise RuntimeError("patch_ncc_roughness: HIP kernel, there is no CPU path")
     h, w = rg.shape[-2:]
+    assert ng.shape[-2:] == (h, w), "both grey images must have the same size"
     N = pixels.shape[0]
     out = torch.empty((3, N, 1), dtype=torch.float32, device=pixels.device)
     consts = tuple((C.c_float * len(v))(*[float(x) for x in v]) for v in (M.reshape(-1).tolist(), b.reshape(-1).tolist(), Kinv.reshape(-1).tolist()))
     _native.launch("gs2m_patch_ncc_roughness", pixels.device, N, pixels.data_ptr(), normals.data_ptr(), dists.data_ptr(), rg.data_ptr(),
                    ng.data_ptr(), w, h, *consts, float(ncc_scale), int(patch), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr())
-    return out[0], out[1], torch.sqrt(out[2]) < 0.01
+    return out[0], out[1], _low_texture(out[2])
+
+
+def _low_texture(ref_var):
+    """The low-texture switch sqrt(ref_var) < 0.01.  ref_var is a difference of two float32 sums; the kernel's centred sums have not
+    been seen to round below zero, so the clamp is defensive: sqrt of a negative value is NaN, which compares False, and the switch
+    must be ON for a patch without texture."""
+    return torch.sqrt(ref_var.clamp_min(0.0)) < 0.01
 
 
 # ---------------------------------------------------------------- the same, op by op (utils/loss_utils.py:303-349, 451-509)

@@ -25,7 +25,10 @@ int gs2m_patch_ncc_backward(int N, const float* pixels, const float* normals, co
 
 /* roughness_loss (utils/loss_utils.py:138-243), forward only as there: the grey-value NCC, the NCC of the 3x3-Sobel gradient
  * magnitudes of the two patches (_patch_gradient :232-238) and the reference patch's unnormalised variance (the low-texture
- * switch sqrt(ref_var) < 0.01, :209-211), each (N).  patch <= 3. */
+ * switch sqrt(ref_var) < 0.01, :209-211), each (N).  patch <= 3: the patches are staged at 7 x 7 at most.  Order of the checks: N == 0
+ * returns GS2M_OK; N < 0 or a NULL array returns GS2M_ERR_INVALID_ARG; then patch > 3 returns GS2M_ERR_UNSUPPORTED (also for a patch
+ * that the other two entry points would refuse as invalid, such as 9); then the remaining arguments (M, b, Kinv, ncc_scale, patch < 0,
+ * width, height) return GS2M_ERR_INVALID_ARG.  Nothing is written in any of these cases. */
 int gs2m_patch_ncc_roughness(int N, const float* pixels, const float* normals, const float* dists, const float* ref_gray,
                              const float* near_gray, int width, int height, const float* M, const float* b, const float* Kinv,
                              float ncc_scale, int patch, float* ncc_gray, float* ncc_grad, float* ref_var, void* stream);
@@ -33,7 +36,10 @@ int gs2m_patch_ncc_roughness(int N, const float* pixels, const float* normals, c
 /* The two backwards below scatter bilinear footprints into the neighbour's maps.  Deterministic mode (default ON): the sums are
  * formed in 64-bit fixed point scaled by the call's largest contribution (integer atomics: independent of the order of the
  * additions, bitwise reproducible run to run) in a per-(device, stream) workspace of the library's own; off: fp32 atomics (the
- * last bits of a texel then depend on the order in which the hardware retires them).  Process-wide. */
+ * last bits of a texel then depend on the order in which the hardware retires them).  Process-wide.
+ * Non-finite upstream gradients: the two modes DIFFER.  Deterministic mode drops an infinite or NaN contribution (it has no
+ * fixed-point value, and it does not enter the call's scale either): the texel receives the sum of its finite contributions.
+ * The fp32-atomic mode adds it, so the texel becomes infinite or NaN.  Texels that no such sample touches are the same in both. */
 void gs2m_mvs_set_deterministic(int on);
 int gs2m_mvs_get_deterministic(void);
 

@@ -25,6 +25,8 @@
 // (<= 19 MB) and stay in L2 / MALL; the forward is bound by the streaming uv read and output write, the backward by
 // the atomic rate.
 #include "common.h"
+#include <algorithm>
+#include <atomic>
 #include "../../include/gs2m_texture.h"
 #include "../../include/gs2m_pbr.h"
 
@@ -206,9 +208,32 @@ __device__ __forceinline__ bool run_merge(int key, float (&v)[C]) {
     return key >= 0 && (lr == 15 || next != key);  // this lane holds its run's sum and issues the add
 }
 
-// A combining table in LDS in front of the global atomics of the levels that are too large to privatise: key = (level, texel),
-// open addressing, 8 probes, then straight to memory; drained after every pixel tile.  A 32 x 32 tile of a smooth image puts its
-// ~8000 contributions on a few hundred distinct texels.
+// The merge and table key of one texel: (slot << 24) | texel index.  A slot is one gradient tensor: the levels of a stack are
+// slots 0 .. levels - 1, the irradiance map of the shading backward is the one behind every possible level.
+constexpr int KEY_TEXEL_BITS = 24;
+constexpr long long KEY_TEXELS = 1LL << KEY_TEXEL_BITS;  // a tensor with more texels is refused before any launch
+struct SlotTexel { int slot, texel; };
+__host__ __device__ constexpr int make_key(int slot, int texel) { return (slot << KEY_TEXEL_BITS) | texel; }
+__host__ __device__ constexpr SlotTexel split_key(int key) { return {key >> KEY_TEXEL_BITS, key & (int)(KEY_TEXELS - 1)}; }
+constexpr int IRRADIANCE_SLOT = GS2M_TEX_MAX_LEVELS;
+constexpr int SINK_SLOTS = IRRADIANCE_SLOT + 1;
+static_assert(IRRADIANCE_SLOT > GS2M_TEX_MAX_LEVELS - 1, "the irradiance slot must lie behind every level of a stack");
+static_assert(make_key(IRRADIANCE_SLOT, (int)(KEY_TEXELS - 1)) >= 0, "a key is never negative: -1 is 'nothing to add' and the empty table entry");
+
+struct SinkSlots {  // what the host plans (plan_sink) and the kernels accumulate into (TexelSink)
+    struct Slot {
+        float* grad;  // the gradient tensor in memory
+        int floats;   // its size
+        int lds_off;  // float offset of the workgroup-private copy in dynamic LDS, or -1
+        int table;    // not private: adds may go through the combining table (else straight to memory)
+    } slot[SINK_SLOTS];
+    int lds_floats;   // all private copies; the table sits behind them
+};
+
+// A combining table in LDS in front of the global atomics of the slots that are too large to privatise: open addressing by
+// the key, 8 probes, then straight to memory; drained after every pixel tile.  A 32 x 32 tile of a smooth image puts its
+// ~8000 contributions on a few hundred distinct texels, where one global atomic per (pixel, texel, channel) is what the
+// backward otherwise spends its time on (the shading backward: 0.83 ms against 0.27 ms without them).
 constexpr int COMB_HT = 2048;
 
 template <int C>
@@ -222,8 +247,7 @@ struct CombineTable {
             for (int c = 0; c < C; c++) val[C * k + c] = 0.f;
         }
     }
-    __device__ __forceinline__ void add(int level, int texel, float* gptr, const float (&v)[C]) {
-        const int k = (level << 24) | texel;
+    __device__ __forceinline__ void add(int k, float* gptr, const float (&v)[C]) {
         unsigned h = ((unsigned)k * 2654435761u) >> 21;  // 11 bits
 #pragma unroll 1
         for (int probe = 0; probe < 8; probe++) {
@@ -236,21 +260,79 @@ struct CombineTable {
             h = (h + 1) & (COMB_HT - 1);
         }
 #pragma unroll
-        for (int c = 0; c < C; c++) unsafeAtomicAdd(&gptr[(size_t)texel * C + c], v[c]);
+        for (int c = 0; c < C; c++) unsafeAtomicAdd(&gptr[(size_t)split_key(k).texel * C + c], v[c]);
     }
-    template <class GradOf>
-    __device__ __forceinline__ void drain(int tid, int nthreads, GradOf grad_of) {  // all threads of the workgroup
+    __device__ __forceinline__ void drain(int tid, int nthreads, const SinkSlots::Slot* slot) {  // all threads of the workgroup
         __syncthreads();
         for (int k = tid; k < COMB_HT; k += nthreads) {
             const int kk = key[k];
             if (kk >= 0) {
-                float* g = grad_of(kk >> 24) + (size_t)(kk & 0xFFFFFF) * C;
+                const SlotTexel st = split_key(kk);
+                float* g = slot[st.slot].grad + (size_t)st.texel * C;
 #pragma unroll
                 for (int c = 0; c < C; c++) { unsafeAtomicAdd(&g[c], val[C * k + c]); val[C * k + c] = 0.f; }
                 key[k] = -1;
             }
         }
         __syncthreads();
+    }
+};
+
+constexpr int TEX_BWD_THREADS = 1024;
+
+// The backward's accumulator of texel gradients, shared by texture_bwd_kernel and shade_bwd_kernel.  Three tiers: runs of
+// equal keys inside a DPP row are summed (run_merge); the run's last lane adds into the slot's workgroup-private LDS copy,
+// into the combining table, or straight to memory; the table is drained after every pixel tile and the private copies are
+// flushed once per workgroup.  init / drain / flush are called by every thread of the workgroup.
+template <int C>
+struct TexelSink : SinkSlots {
+    __device__ __forceinline__ static float* lds() { extern __shared__ float s_acc[]; return s_acc; }
+    __device__ __forceinline__ CombineTable<C> table() const { return {reinterpret_cast<int*>(lds() + lds_floats), lds() + lds_floats + COMB_HT}; }
+    __device__ __forceinline__ void init() const {
+        for (int k = threadIdx.x; k < lds_floats; k += TEX_BWD_THREADS) lds()[k] = 0.f;
+        table().clear(threadIdx.x, TEX_BWD_THREADS);
+        __syncthreads();
+    }
+    // wave-uniform: called by all lanes of the wave, every lane with a slot that exists; `on == false` lanes carry key -1
+    __device__ __forceinline__ void add(bool on, int s, const Footprint& F, const float (&g)[C], float scale) const {
+        float wt[4];
+        footprint_weights(F, wt);
+        const int loff = slot[s].lds_off;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const bool live = on && F.t[k] >= 0;
+            float v[C];
+#pragma unroll
+            for (int c = 0; c < C; c++) v[c] = live ? wt[k] * scale * g[c] : 0.f;
+            const int key = live ? make_key(s, F.t[k]) : -1;
+            if (run_merge<C>(key, v)) {
+                if (loff >= 0) {
+#pragma unroll
+                    for (int c = 0; c < C; c++) atomicAdd(&lds()[loff + F.t[k] * C + c], v[c]);  // ds_add_f32
+                } else if (slot[s].table) {
+                    table().add(key, slot[s].grad, v);
+                } else {
+#pragma unroll
+                    for (int c = 0; c < C; c++) unsafeAtomicAdd(&slot[s].grad[(size_t)F.t[k] * C + c], v[c]);
+                }
+            }
+        }
+    }
+    __device__ __forceinline__ void drain() const { table().drain(threadIdx.x, TEX_BWD_THREADS, slot); }
+    __device__ __forceinline__ void flush() const {
+        __syncthreads();
+        for (int s = 0; s < SINK_SLOTS; s++) {
+            if (slot[s].lds_off < 0) continue;
+            const int cnt = slot[s].floats;
+            // every workgroup starts somewhere else: they all get here at about the same time, and atomics to one address serialise
+            const int start = (int)(((long long)blockIdx.x * cnt) / gridDim.x);
+            for (int k0 = threadIdx.x; k0 < cnt; k0 += TEX_BWD_THREADS) {
+                int k = k0 + start;
+                if (k >= cnt) k -= cnt;
+                const float v = lds()[slot[s].lds_off + k];
+                if (v != 0.f) unsafeAtomicAdd(&slot[s].grad[k], v);
+            }
+        }
     }
 };
 
@@ -272,16 +354,10 @@ __host__ __device__ __forceinline__ int tile_count(int n, int img_w) {
 }
 
 struct MipStack {
-    const float* tex[GS2M_TEX_MAX_LEVELS];
-    float* grad[GS2M_TEX_MAX_LEVELS];
+    const float* tex[GS2M_TEX_MAX_LEVELS];  // NULL in the texture backward, which reads no texel
     int width[GS2M_TEX_MAX_LEVELS];
-    int lds_off[GS2M_TEX_MAX_LEVELS];  // backward: float offset of the level's private copy in dynamic LDS, or -1
-    int lds_floats;
     int levels;
 };
-
-constexpr int TEX_LDS_MAX_WIDTH = 32;      // levels up to 6 x 32 x 32 x C are privatised (98 KB at C = 4, + 24 KB for 16^2)
-constexpr int TEX_BWD_THREADS = 1024;
 
 // mode 0: cube linear (level 0 only); 1: cube linear-mipmap-linear by bias; 2: 2-D clamp linear (width x height)
 template <int C, int MODE>
@@ -313,38 +389,12 @@ __global__ void __launch_bounds__(256) texture_kernel(int n, MipStack M, int hei
     for (int c = 0; c < C; c++) out[(size_t)i * C + c] = r[c];
 }
 
-// backward: persistent workgroups (one per CU), grid-stride over the pixels; small levels accumulate in LDS and are
-// flushed once per workgroup
+// backward: persistent workgroups (one per CU), grid-stride over the pixel tiles; every lane walks the same number of pixels
+// and footprints, and the sink K gathers what they add
 template <int C, int MODE>
-__global__ void __launch_bounds__(TEX_BWD_THREADS) texture_bwd_kernel(int n, int img_w, MipStack M, int height, const float* __restrict__ uv,
+__global__ void __launch_bounds__(TEX_BWD_THREADS) texture_bwd_kernel(int n, int img_w, MipStack M, TexelSink<C> K, int height, const float* __restrict__ uv,
                                                                       const float* __restrict__ bias, const float* __restrict__ dy) {
-    extern __shared__ float s_acc[];
-    CombineTable<C> T = {reinterpret_cast<int*>(s_acc + M.lds_floats), s_acc + M.lds_floats + COMB_HT};
-    for (int k = threadIdx.x; k < M.lds_floats; k += TEX_BWD_THREADS) s_acc[k] = 0.f;
-    T.clear(threadIdx.x, TEX_BWD_THREADS);
-    __syncthreads();
-    // wave-uniform: every lane walks the same number of pixels and footprints; lanes with nothing to add carry key -1
-    auto add = [&](bool on, int level, const Footprint& F, const float (&g)[C], float scale) {
-        float wt[4];
-        footprint_weights(F, wt);
-        const int loff = M.lds_off[on ? level : 0];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const bool live = on && F.t[k] >= 0;
-            float v[C];
-#pragma unroll
-            for (int c = 0; c < C; c++) v[c] = live ? wt[k] * scale * g[c] : 0.f;
-            const int key = live ? (level << 24) | F.t[k] : -1;
-            if (run_merge<C>(key, v)) {
-                if (loff >= 0) {
-#pragma unroll
-                    for (int c = 0; c < C; c++) atomicAdd(&s_acc[loff + F.t[k] * C + c], v[c]);  // ds_add_f32
-                } else {
-                    T.add(level, F.t[k], M.grad[level], v);
-                }
-            }
-        }
-    };
+    K.init();
     const int ntiles = tile_count(n, img_w);
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         bool valid;
@@ -356,7 +406,7 @@ __global__ void __launch_bounds__(TEX_BWD_THREADS) texture_bwd_kernel(int n, int
         for (int c = 0; c < C; c++) { g[c] = dy[ii * C + c]; any |= g[c] != 0.f; }
         any &= valid;
         if (MODE == 2) {
-            add(any, 0, clamp2d_footprint(uv[2 * ii], uv[2 * ii + 1], M.width[0], height), g, 1.f);
+            K.add(any, 0, clamp2d_footprint(uv[2 * ii], uv[2 * ii + 1], M.width[0], height), g, 1.f);
         } else {
             const float x = uv[3 * ii], y = uv[3 * ii + 1], z = uv[3 * ii + 2];
             int l0 = 0, l1 = 0;
@@ -367,24 +417,12 @@ __global__ void __launch_bounds__(TEX_BWD_THREADS) texture_bwd_kernel(int n, int
                 if (fl > 0.f) { l1 = min(l0 + 1, M.levels - 1); fl -= (float)l0; }
             }
             const bool two = MODE == 1 && fl > 0.f;
-            add(any, l0, cube_footprint(x, y, z, M.width[l0]), g, two ? 1.f - fl : 1.f);
-            if (MODE == 1) add(any && two, l1, cube_footprint(x, y, z, M.width[l1]), g, fl);
+            K.add(any, l0, cube_footprint(x, y, z, M.width[l0]), g, two ? 1.f - fl : 1.f);
+            if (MODE == 1) K.add(any && two, l1, cube_footprint(x, y, z, M.width[l1]), g, fl);
         }
-        T.drain(threadIdx.x, TEX_BWD_THREADS, [&](int level) { return M.grad[level]; });
+        K.drain();
     }
-    __syncthreads();
-    for (int l = 0; l < M.levels; l++) {
-        if (M.lds_off[l] < 0) continue;
-        const int cnt = (MODE == 2 ? M.width[l] * height : 6 * M.width[l] * M.width[l]) * C;
-        // every workgroup starts somewhere else: they all get here at about the same time, and atomics to one address serialise
-        const int start = (int)(((long long)blockIdx.x * cnt) / gridDim.x);
-        for (int k0 = threadIdx.x; k0 < cnt; k0 += TEX_BWD_THREADS) {
-            int k = k0 + start;
-            if (k >= cnt) k -= cnt;
-            const float v = s_acc[M.lds_off[l] + k];
-            if (v != 0.f) unsafeAtomicAdd(&M.grad[l][k], v);
-        }
-    }
+    K.flush();
 }
 
 template <int MODE>
@@ -400,51 +438,75 @@ int launch_fwd(int C, int n, const MipStack& M, int height, const float* uv, con
     return hipGetLastError() == hipSuccess ? GS2M_OK : GS2M_ERR_HIP;
 }
 
-template <int C, int MODE>
-int launch_bwd_c(int n, int img_w, MipStack& M, int height, const float* uv, const float* bias, const float* dy, hipStream_t s) {
-    // private LDS copies for the small levels (2-D: small textures)
-    M.lds_floats = 0;
-    for (int l = 0; l < M.levels; l++) {
-        const bool small = M.width[l] <= TEX_LDS_MAX_WIDTH && (MODE != 2 || height <= 6 * TEX_LDS_MAX_WIDTH);
-        M.lds_off[l] = small ? M.lds_floats : -1;
-        if (small) M.lds_floats += (MODE == 2 ? M.width[l] * height : 6 * M.width[l] * M.width[l]) * C;
+constexpr int TEX_LDS_MAX_WIDTH = 32;          // slots up to 6 x 32 x 32 x C are privatised (98 KB at C = 4, + 24 KB for 16^2)
+constexpr int TEX_BWD_LDS_BUDGET = 159 * 1024;  // bytes of dynamic LDS a backward workgroup may ask for: private copies + table
+constexpr int TEX_BWD_MAX_BLOCKS = 256;         // one per CU: the flush costs (workgroups x private texels) atomics
+
+inline int bwd_blocks(int n) { return std::min((n + TEX_BWD_THREADS - 1) / TEX_BWD_THREADS, TEX_BWD_MAX_BLOCKS); }
+
+// Lays the sink's dynamic LDS out for a stack of `levels` widths and an irradiance map (width 0: none) at C channels;
+// height > 0: the slots are 2-D textures (height, width, C), else cube levels (6, width, width, C).  Small slots get a private
+// copy, in slot order.  The table has to fit behind them: while it does not, the widest private slot (ties: the lowest
+// slot, so a level goes before the irradiance map) gives its copy up, and the rest is packed again.  -> bytes of dynamic
+// LDS, or GS2M_ERR_UNSUPPORTED.
+int plan_sink(SinkSlots& K, const int* width, int levels, int irradiance_width, int height, int C) {
+    int w[SINK_SLOTS] = {};
+    for (int l = 0; l < levels; l++) w[l] = width[l];
+    w[IRRADIANCE_SLOT] = irradiance_width;
+    for (int s = 0; s < SINK_SLOTS; s++) {
+        const long long texels = height > 0 ? (long long)w[s] * height : 6LL * w[s] * w[s];
+        if (texels > KEY_TEXELS) return GS2M_ERR_UNSUPPORTED;  // split_key would decode such a texel as one of another slot
+        K.slot[s].floats = (int)texels * C;
+        K.slot[s].lds_off = (w[s] > 0 && w[s] <= TEX_LDS_MAX_WIDTH && height <= 6 * TEX_LDS_MAX_WIDTH) ? 0 : -1;
     }
-    // the table has to fit behind the private copies: give up the widest private level(s) if it does not (they then go
-    // through the table like the large ones)
-    while ((size_t)(M.lds_floats + COMB_HT * (1 + C)) * sizeof(float) > 159 * 1024) {
+    for (;;) {
+        K.lds_floats = 0;
         int widest = -1;
-        for (int l = 0; l < M.levels; l++)
-            if (M.lds_off[l] >= 0 && (widest < 0 || M.width[l] > M.width[widest])) widest = l;
+        for (int s = 0; s < SINK_SLOTS; s++) {
+            if (K.slot[s].lds_off < 0) continue;
+            K.slot[s].lds_off = K.lds_floats;
+            K.lds_floats += K.slot[s].floats;
+            if (widest < 0 || w[s] > w[widest]) widest = s;
+        }
+        const size_t bytes = (size_t)(K.lds_floats + COMB_HT * (1 + C)) * sizeof(float);
+        if (bytes <= (size_t)TEX_BWD_LDS_BUDGET) return (int)bytes;
         if (widest < 0) return GS2M_ERR_UNSUPPORTED;
-        M.lds_off[widest] = -1;
-        M.lds_floats = 0;
-        for (int l = 0; l < M.levels; l++)
-            if (M.lds_off[l] >= 0) { M.lds_off[l] = M.lds_floats; M.lds_floats += (MODE == 2 ? M.width[l] * height : 6 * M.width[l] * M.width[l]) * C; }
+        K.slot[widest].lds_off = -1;
     }
-    const size_t lds = (size_t)(M.lds_floats + COMB_HT * (1 + C)) * sizeof(float);
-    static bool attr_set = false;  // per instantiation
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&texture_bwd_kernel<C, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024 - 1024) != hipSuccess)
-            return GS2M_ERR_HIP;
-        attr_set = true;
-    }
-    int blocks = (n + TEX_BWD_THREADS - 1) / TEX_BWD_THREADS;
-#ifndef GS2M_TEX_BWD_BLOCKS
-#define GS2M_TEX_BWD_BLOCKS 256
-#endif
-    if (blocks > GS2M_TEX_BWD_BLOCKS) blocks = GS2M_TEX_BWD_BLOCKS;  // one per CU: the flush costs (workgroups x private texels) atomics
-    texture_bwd_kernel<C, MODE><<<blocks, TEX_BWD_THREADS, lds, s>>>(n, img_w, M, height, uv, bias, dy);
+}
+
+// More than 64 KB of dynamic LDS has to be allowed per kernel AND per device: one bit per device in a mask per kernel
+// (a device index of 64 or more has no bit and sets the attribute on every call).  Two threads that race set it twice.
+template <auto Kernel>
+int allow_budget_lds() {
+    static std::atomic<unsigned long long> allowed{0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return GS2M_ERR_HIP;
+    const unsigned long long bit = (dev >= 0 && dev < 64) ? 1ULL << dev : 0;
+    if (allowed.load(std::memory_order_acquire) & bit) return GS2M_OK;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, TEX_BWD_LDS_BUDGET) != hipSuccess)
+        return GS2M_ERR_HIP;
+    allowed.fetch_or(bit, std::memory_order_release);
+    return GS2M_OK;
+}
+
+template <int C, int MODE>
+int launch_bwd_c(int n, int img_w, const MipStack& M, SinkSlots& K, int height, const float* uv, const float* bias, const float* dy, hipStream_t s) {
+    const int lds = plan_sink(K, M.width, M.levels, 0, height, C);
+    if (lds < 0) return lds;
+    const int rc = allow_budget_lds<&texture_bwd_kernel<C, MODE>>();
+    if (rc != GS2M_OK) return rc;
+    texture_bwd_kernel<C, MODE><<<bwd_blocks(n), TEX_BWD_THREADS, lds, s>>>(n, img_w, M, TexelSink<C>{K}, height, uv, bias, dy);
     return hipGetLastError() == hipSuccess ? GS2M_OK : GS2M_ERR_HIP;
 }
 
 template <int MODE>
-int launch_bwd(int C, int n, int img_w, MipStack& M, int height, const float* uv, const float* bias, const float* dy, hipStream_t s) {
+int launch_bwd(int C, int n, int img_w, const MipStack& M, SinkSlots& K, int height, const float* uv, const float* bias, const float* dy, hipStream_t s) {
     switch (C) {
-        case 1: return launch_bwd_c<1, MODE>(n, img_w, M, height, uv, bias, dy, s);
-        case 2: return launch_bwd_c<2, MODE>(n, img_w, M, height, uv, bias, dy, s);
-        case 3: return launch_bwd_c<3, MODE>(n, img_w, M, height, uv, bias, dy, s);
-        case 4: return launch_bwd_c<4, MODE>(n, img_w, M, height, uv, bias, dy, s);
+        case 1: return launch_bwd_c<1, MODE>(n, img_w, M, K, height, uv, bias, dy, s);
+        case 2: return launch_bwd_c<2, MODE>(n, img_w, M, K, height, uv, bias, dy, s);
+        case 3: return launch_bwd_c<3, MODE>(n, img_w, M, K, height, uv, bias, dy, s);
+        case 4: return launch_bwd_c<4, MODE>(n, img_w, M, K, height, uv, bias, dy, s);
         default: return GS2M_ERR_UNSUPPORTED;
     }
 }
@@ -458,7 +520,7 @@ int launch_bwd(int C, int n, int img_w, MipStack& M, int height, const float* uv
 struct ShadeIn {
     const float* normals; const float* view_dirs; const float* albedo; const float* roughness; const float* metallic;  // metallic may be NULL
     const float* lut; int lut_w, lut_h;
-    const float* diffuse; float* d_diffuse; int diffuse_w, diffuse_lds;  // lds: float offset of the private copy or -1
+    const float* diffuse; int diffuse_w;
     float min_r, max_r;
 };
 
@@ -522,41 +584,13 @@ __global__ void __launch_bounds__(256) shade_fwd_kernel(int n, ShadeIn P, MipSta
     }
 }
 
-// The large specular levels cannot be privatised (19 MB), and one global atomic per (pixel, texel, channel) is what the
-// kernel then spends its time on (0.27 ms without them, 0.83 ms with).  A workgroup therefore works on 32 x 32 PIXEL TILES
-// (image width given) and puts a small combining table in LDS in front of the atomics: key = (level, texel), open
-// addressing, 8 probes, then straight to memory; the table is drained after every tile.  A tile of a smooth image touches a
-// few hundred distinct texels with its ~8000 contributions.
-__global__ void __launch_bounds__(TEX_BWD_THREADS) shade_bwd_kernel(int n, int img_w, ShadeIn P, MipStack M, const float* __restrict__ d_rgb,
+// Backward: the same persistent workgroups and pixel tiles as texture_bwd_kernel (32 x 32 image tiles when the image width is
+// given, so that a tile keeps to few texels).  The kernel re-evaluates the pixel, writes d_albedo / d_metallic and hands the
+// three footprints to the sink K: the irradiance map (IRRADIANCE_SLOT: private, or straight to memory when it is too large
+// for LDS, never through the table) and the one or two specular levels.
+__global__ void __launch_bounds__(TEX_BWD_THREADS) shade_bwd_kernel(int n, int img_w, ShadeIn P, MipStack M, TexelSink<3> K, const float* __restrict__ d_rgb,
                                                                     float* __restrict__ d_albedo, float* __restrict__ d_metallic) {
-    extern __shared__ float s_acc[];
-    const int lds_total = M.lds_floats + (P.diffuse_lds >= 0 ? 6 * P.diffuse_w * P.diffuse_w * 3 : 0);
-    CombineTable<3> T = {reinterpret_cast<int*>(s_acc + lds_total), s_acc + lds_total + COMB_HT};
-    for (int k = threadIdx.x; k < lds_total; k += TEX_BWD_THREADS) s_acc[k] = 0.f;
-    T.clear(threadIdx.x, TEX_BWD_THREADS);
-    __syncthreads();
-    auto add = [&](bool on, int key_hi, int loff, float* gptr, const Footprint& F, const float (&g)[3], float scale) {
-        float wt[4];
-        footprint_weights(F, wt);
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const bool live = on && F.t[k] >= 0;
-            float v[3];
-#pragma unroll
-            for (int c = 0; c < 3; c++) v[c] = live ? wt[k] * scale * g[c] : 0.f;
-            if (run_merge<3>(live ? (key_hi << 24) | F.t[k] : -1, v)) {
-                if (loff >= 0) {
-#pragma unroll
-                    for (int c = 0; c < 3; c++) atomicAdd(&s_acc[loff + F.t[k] * 3 + c], v[c]);
-                } else if (key_hi < M.levels) {
-                    T.add(key_hi, F.t[k], gptr, v);
-                } else {  // (an irradiance map too large for LDS: not a level of the stack)
-#pragma unroll
-                    for (int c = 0; c < 3; c++) unsafeAtomicAdd(&gptr[(size_t)F.t[k] * 3 + c], v[c]);
-                }
-            }
-        }
-    };
+    K.init();
     const int ntiles = tile_count(n, img_w);
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         bool valid;
@@ -579,46 +613,26 @@ __global__ void __launch_bounds__(TEX_BWD_THREADS) shade_bwd_kernel(int n, int i
             dm += dF0 * (s.a[c] - 0.04f);
         }
         if (valid && d_metallic != nullptr) d_metallic[ii] = dm;
-        add(any, 15, P.diffuse_lds, P.d_diffuse, s.Fd, gE, 1.f);
-        add(any, s.l0, M.lds_off[any ? s.l0 : 0], M.grad[any ? s.l0 : 0], s.F0, gL, s.two ? 1.f - s.fl : 1.f);
-        add(any && s.two, s.l1, M.lds_off[any ? s.l1 : 0], M.grad[any ? s.l1 : 0], s.F1, gL, s.fl);
-        T.drain(threadIdx.x, TEX_BWD_THREADS, [&](int level) { return M.grad[level]; });
+        K.add(any, IRRADIANCE_SLOT, s.Fd, gE, 1.f);
+        K.add(any, s.l0, s.F0, gL, s.two ? 1.f - s.fl : 1.f);
+        K.add(any && s.two, s.l1, s.F1, gL, s.fl);
+        K.drain();
     }
-    __syncthreads();
-    auto flush = [&](int loff, float* gptr, int cnt) {
-        const int start = (int)(((long long)blockIdx.x * cnt) / gridDim.x);
-        for (int k0 = threadIdx.x; k0 < cnt; k0 += TEX_BWD_THREADS) {
-            int k = k0 + start;
-            if (k >= cnt) k -= cnt;
-            const float v = s_acc[loff + k];
-            if (v != 0.f) unsafeAtomicAdd(&gptr[k], v);
-        }
-    };
-    for (int l = 0; l < M.levels; l++)
-        if (M.lds_off[l] >= 0) flush(M.lds_off[l], M.grad[l], 6 * M.width[l] * M.width[l] * 3);
-    if (P.diffuse_lds >= 0) flush(P.diffuse_lds, P.d_diffuse, 6 * P.diffuse_w * P.diffuse_w * 3);
+    K.flush();
 }
 
-int fill_stack(MipStack& M, int levels, const float* const* tex, float* const* grad, const int* width, bool bwd) {
-    if (levels < 1 || levels > GS2M_TEX_MAX_LEVELS || !width || (bwd ? !grad : !tex)) return GS2M_ERR_INVALID_ARG;
+// tex: the levels' texels (forward, and the shading backward, which samples them again), or NULL; grad: their gradient
+// tensors, which become slots 0 .. levels - 1 of the sink K and go through the table where they are not private, or NULL
+int fill_stack(MipStack& M, SinkSlots* K, int levels, const float* const* tex, float* const* grad, const int* width) {
+    if (levels < 1 || levels > GS2M_TEX_MAX_LEVELS || !width || (!tex && !grad)) return GS2M_ERR_INVALID_ARG;
     M.levels = levels;
     for (int l = 0; l < levels; l++) {
-        if (width[l] < 1 || (bwd ? !grad[l] : !tex[l])) return GS2M_ERR_INVALID_ARG;
+        if (width[l] < 1 || (tex && !tex[l]) || (grad && !grad[l])) return GS2M_ERR_INVALID_ARG;
         M.tex[l] = tex ? tex[l] : nullptr;
-        M.grad[l] = grad ? grad[l] : nullptr;
         M.width[l] = width[l];
+        if (grad) { K->slot[l].grad = grad[l]; K->slot[l].table = 1; }
     }
     return GS2M_OK;
-}
-
-// The backward's merge and table key is (level << 24) | texel (run_merge, CombineTable): a level whose texel count needs
-// more than 24 bits would be decoded by `drain` as another level at another offset.  Refused before any launch.
-constexpr long long KEY_TEXELS = 1LL << 24;
-bool cube_fits_key(int w) { return 6LL * w * w <= KEY_TEXELS; }
-bool stack_fits_key(const int* width, int levels) {
-    for (int l = 0; l < levels; l++)
-        if (!cube_fits_key(width[l])) return false;
-    return true;
 }
 
 }  // namespace
@@ -630,7 +644,7 @@ int gs2m_texture_cube_forward(int n, int channels, int levels, const float* cons
     if (n == 0) return GS2M_OK;
     if (n < 0 || !dirs || !out) return GS2M_ERR_INVALID_ARG;
     MipStack M;
-    const int rc = fill_stack(M, levels, tex, nullptr, width, false);
+    const int rc = fill_stack(M, nullptr, levels, tex, nullptr, width);
     if (rc != GS2M_OK) return rc;
     if (mip_level_bias) return launch_fwd<1>(channels, n, M, 0, dirs, mip_level_bias, out, (hipStream_t)stream);
     return launch_fwd<0>(channels, n, M, 0, dirs, nullptr, out, (hipStream_t)stream);
@@ -641,11 +655,11 @@ int gs2m_texture_cube_backward(int n, int channels, int levels, float* const* gr
     if (n == 0) return GS2M_OK;
     if (n < 0 || !dirs || !dL_dout || image_width < 0 || (image_width > 0 && n % image_width != 0)) return GS2M_ERR_INVALID_ARG;
     MipStack M;
-    const int rc = fill_stack(M, levels, nullptr, grad_tex, width, true);
+    SinkSlots K = {};
+    const int rc = fill_stack(M, &K, levels, nullptr, grad_tex, width);
     if (rc != GS2M_OK) return rc;
-    if (!stack_fits_key(width, levels)) return GS2M_ERR_UNSUPPORTED;
-    if (mip_level_bias) return launch_bwd<1>(channels, n, image_width, M, 0, dirs, mip_level_bias, dL_dout, (hipStream_t)stream);
-    return launch_bwd<0>(channels, n, image_width, M, 0, dirs, nullptr, dL_dout, (hipStream_t)stream);
+    if (mip_level_bias) return launch_bwd<1>(channels, n, image_width, M, K, 0, dirs, mip_level_bias, dL_dout, (hipStream_t)stream);
+    return launch_bwd<0>(channels, n, image_width, M, K, 0, dirs, nullptr, dL_dout, (hipStream_t)stream);
 }
 
 int gs2m_texture_2d_clamp_forward(int n, int channels, int width, int height, const float* tex, const float* uv, float* out,
@@ -653,7 +667,7 @@ int gs2m_texture_2d_clamp_forward(int n, int channels, int width, int height, co
     if (n == 0) return GS2M_OK;
     if (n < 0 || width < 1 || height < 1 || !tex || !uv || !out) return GS2M_ERR_INVALID_ARG;
     MipStack M;
-    M.levels = 1; M.tex[0] = tex; M.grad[0] = nullptr; M.width[0] = width;
+    M.levels = 1; M.tex[0] = tex; M.width[0] = width;
     return launch_fwd<2>(channels, n, M, height, uv, nullptr, out, (hipStream_t)stream);
 }
 
@@ -661,10 +675,11 @@ int gs2m_texture_2d_clamp_backward(int n, int channels, int width, int height, f
                                    const float* dL_dout, void* stream) {
     if (n == 0) return GS2M_OK;
     if (n < 0 || width < 1 || height < 1 || !grad_tex || !uv || !dL_dout) return GS2M_ERR_INVALID_ARG;
-    if ((long long)width * height > KEY_TEXELS) return GS2M_ERR_UNSUPPORTED;
     MipStack M;
-    M.levels = 1; M.tex[0] = nullptr; M.grad[0] = grad_tex; M.width[0] = width;
-    return launch_bwd<2>(channels, n, 0, M, height, uv, nullptr, dL_dout, (hipStream_t)stream);
+    SinkSlots K = {};
+    const int rc = fill_stack(M, &K, 1, nullptr, &grad_tex, &width);
+    if (rc != GS2M_OK) return rc;
+    return launch_bwd<2>(channels, n, 0, M, K, height, uv, nullptr, dL_dout, (hipStream_t)stream);
 }
 
 int gs2m_pbr_shade_forward(int n, const float* normals, const float* view_dirs, const float* albedo, const float* roughness,
@@ -677,10 +692,9 @@ int gs2m_pbr_shade_forward(int n, const float* normals, const float* view_dirs, 
         lut_height < 1 || diffuse_width < 1 || levels < 2)
         return GS2M_ERR_INVALID_ARG;
     MipStack M;
-    const int rc = fill_stack(M, levels, specular, nullptr, width, false);
+    const int rc = fill_stack(M, nullptr, levels, specular, nullptr, width);
     if (rc != GS2M_OK) return rc;
-    ShadeIn P = {normals, view_dirs, albedo, roughness, metallic, brdf_lut, lut_width, lut_height, diffuse, nullptr, diffuse_width, -1,
-                 min_roughness, max_roughness};
+    ShadeIn P = {normals, view_dirs, albedo, roughness, metallic, brdf_lut, lut_width, lut_height, diffuse, diffuse_width, min_roughness, max_roughness};
     shade_fwd_kernel<<<(n + 255) / 256, 256, 0, (hipStream_t)stream>>>(n, P, M, render_rgb, diffuse_rgb, specular_rgb, diffuse_light);
     return hipGetLastError() == hipSuccess ? GS2M_OK : GS2M_ERR_HIP;
 }
@@ -696,33 +710,17 @@ int gs2m_pbr_shade_backward(int n, const float* normals, const float* view_dirs,
         !dL_ddiffuse || !dL_dspecular || lut_width < 1 || lut_height < 1 || diffuse_width < 1 || levels < 2 || (dL_dmetallic && !metallic))
         return GS2M_ERR_INVALID_ARG;
     MipStack M;
-    int rc = fill_stack(M, levels, specular, nullptr, width, false);
+    SinkSlots K = {};
+    int rc = fill_stack(M, &K, levels, specular, dL_dspecular, width);
     if (rc != GS2M_OK) return rc;
-    if (!stack_fits_key(width, levels) || !cube_fits_key(diffuse_width)) return GS2M_ERR_UNSUPPORTED;
-    M.lds_floats = 0;
-    for (int l = 0; l < levels; l++) {
-        if (!dL_dspecular[l]) return GS2M_ERR_INVALID_ARG;
-        M.grad[l] = dL_dspecular[l];
-        const bool small = width[l] <= TEX_LDS_MAX_WIDTH;
-        M.lds_off[l] = small ? M.lds_floats : -1;
-        if (small) M.lds_floats += 6 * width[l] * width[l] * 3;
-    }
-    ShadeIn P = {normals, view_dirs, albedo, roughness, metallic, brdf_lut, lut_width, lut_height, diffuse, dL_ddiffuse, diffuse_width, -1,
-                 min_roughness, max_roughness};
-    int lds_floats = M.lds_floats;
-    if (diffuse_width <= TEX_LDS_MAX_WIDTH) { P.diffuse_lds = lds_floats; lds_floats += 6 * diffuse_width * diffuse_width * 3; }
-    lds_floats += COMB_HT * 4;  // the combining table behind the private copies
-    if ((size_t)lds_floats * sizeof(float) > 159 * 1024) return GS2M_ERR_UNSUPPORTED;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&shade_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024) != hipSuccess)
-            return GS2M_ERR_HIP;
-        attr_set = true;
-    }
-    int blocks = (n + TEX_BWD_THREADS - 1) / TEX_BWD_THREADS;
-    if (blocks > 256) blocks = 256;
-    shade_bwd_kernel<<<blocks, TEX_BWD_THREADS, (size_t)lds_floats * sizeof(float), (hipStream_t)stream>>>(n, image_width, P, M, dL_drender_rgb, dL_dalbedo,
-                                                                                                        dL_dmetallic);
+    K.slot[IRRADIANCE_SLOT].grad = dL_ddiffuse;  // .table stays 0: straight to memory when it is not private
+    const int lds = plan_sink(K, width, levels, diffuse_width, 0, 3);
+    if (lds < 0) return lds;
+    rc = allow_budget_lds<&shade_bwd_kernel>();
+    if (rc != GS2M_OK) return rc;
+    ShadeIn P = {normals, view_dirs, albedo, roughness, metallic, brdf_lut, lut_width, lut_height, diffuse, diffuse_width, min_roughness, max_roughness};
+    shade_bwd_kernel<<<bwd_blocks(n), TEX_BWD_THREADS, lds, (hipStream_t)stream>>>(n, image_width, P, M, TexelSink<3>{K}, dL_drender_rgb, dL_dalbedo,
+                                                                                 dL_dmetallic);
     return hipGetLastError() == hipSuccess ? GS2M_OK : GS2M_ERR_HIP;
 }
 

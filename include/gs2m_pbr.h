@@ -12,7 +12,10 @@
  * of the specular stack; normals, view directions and roughness get none (pbr_render detaches them).  `image_width`: the pixels
  * are an image of that width in row-major order (n a multiple of it) -- lets the backward work on 2-D pixel tiles -- or 0.
  * The backward refuses (GS2M_ERR_UNSUPPORTED, nothing launched) a specular level or a diffuse map with 6 * width^2 > 2^24
- * (width >= 1673): its accumulation key holds the texel index in 24 bits (gs2m_texture.h).
+ * (width >= 1673): its accumulation key holds the texel index in 24 bits (gs2m_texture.h).  The size of the light is no other
+ * reason to refuse: maps of width <= 32 accumulate in workgroup-private LDS copies, and where those together do not fit into
+ * the LDS the widest of them (a specular level before the diffuse map) accumulates like a large one instead, as in
+ * gs2m_texture_cube_backward: specular (32, 16, 8) with a 32^2 diffuse map is accepted, with level 0 treated so.
  * Device pointers, fp32; pixel arrays are (n, 3) / (n, 1); `specular`, `dL_dspecular`, `width` are HOST arrays of `levels`
  * entries.  Asynchronous on `stream`; return GS2M_OK (0) or a negative GS2M_ERR_* code (gs2m_raster.h). */
 #ifndef GS2M_PBR_H

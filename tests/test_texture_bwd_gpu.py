@@ -1,7 +1,8 @@
 """The texture backward (csrc/texture.hip: texture_bwd_kernel, shade_bwd_kernel) alone, texel by texel against the
-float64 transpose of oracle/texture_oracle.py, on every accumulation path: the 16-lane run merge, the workgroup-private LDS
-copies, the LDS combining table and its overflow to global atomics, the LDS budget fallback, both pixel orders, and the
-fused shading backward with its clamp gate.
+float64 transpose of oracle/texture_oracle.py.  Both kernels accumulate through one sink (TexelSink, laid out by plan_sink),
+and both are held to the same bound on each of its paths: the 16-lane run merge, the workgroup-private LDS copies, the LDS
+combining table and its overflow to global atomics, the LDS budget fallback, both pixel orders; for the fused shading
+backward also its clamp gate and an irradiance map that is too wide for LDS and goes straight to memory.
 
 The bound, per gradient texel and channel, is
 
@@ -362,12 +363,21 @@ def _halve(x):
     return x.view(6, w, 2, w, 2, 3).mean(dim=(2, 4))
 
 
+# name -> (specular widths, irradiance width): which path of the sink each gradient tensor takes
+LIGHTS = {
+    "table": ((128, 64, 32), 16),                # two levels through the table, one private; irradiance private
+    "demoted": ((32, 16, 8), 32),                # all four are small, together over the budget: level 0 goes to the table
+    "irradiance_direct": ((128, 64, 32), 64),    # the irradiance map is too wide for LDS: straight to memory
+}
+
+
 @functools.lru_cache(maxsize=None)
-def _shade_inputs():
-    """G-buffer and light, all on the CPU.  The light is a base map of resolution 128 with box-filtered levels: specular
-    (128, 64, 32) -- two through the table, one private -- and a 16^2 irradiance map; scaled and shifted to [-0.9, 2.7] so
-    that the clamp cuts at both ends."""
+def _shade_inputs(light="table"):
+    """G-buffer and light, all on the CPU.  The light is a base map of the first specular width, in [-0.9, 2.7] so that the
+    clamp cuts at both ends, with box-filtered levels: the specular stack, and the irradiance map (the mean of 4^k texels,
+    spread out again by 2^k)."""
     from pbr import get_brdf_lut
+    widths, irr_w = LIGHTS[light]
     H, W = SHADE_H, SHADE_W
     g = torch.Generator().manual_seed(31)
     n = torch.nn.functional.normalize(torch.randn(H, W, 3, generator=g), dim=-1)
@@ -377,19 +387,23 @@ def _shade_inputs():
     albedo, metal = torch.rand(H, W, 3, generator=g), torch.rand(H, W, 1, generator=g)
     rough = 0.02 + 0.98 * torch.rand(H, W, 1, generator=g)      # from below MIN_ROUGHNESS, across MAX_ROUGHNESS
     rough.view(-1)[300:310] = torch.tensor([0.0, 0.01, 0.04, 0.04, 0.4999, 0.5, 0.5001, 0.5, 1.0, 1.0])
-    base = torch.rand(6, 128, 128, 3, generator=g) * 3.6 - 0.9
+    base = torch.rand(6, widths[0], widths[0], 3, generator=g) * 3.6 - 0.9
     spec = [base, _halve(base), _halve(_halve(base))]
-    diffuse = ((_halve(_halve(_halve(base))) - 0.9) * 8.0 + 0.8).contiguous()   # the mean of 64 texels: spread out again, part below 0
+    assert tuple(s.shape[1] for s in spec) == widths
+    diffuse, spread = base, 1.0
+    while diffuse.shape[1] > irr_w:
+        diffuse, spread = _halve(diffuse), 2.0 * spread
+    diffuse = ((diffuse - 0.9) * spread + 0.8).contiguous()                      # part of it below 0
     d_rgb = torch.randn(H, W, 3, generator=g)
     return types.SimpleNamespace(n=n, v=v, albedo=albedo, metal=metal, rough=rough, spec=[s.contiguous() for s in spec], diffuse=diffuse,
                                  d_rgb=d_rgb, lut=get_brdf_lut())
 
 
 @functools.lru_cache(maxsize=None)
-def _shade_reference(with_metallic):
+def _shade_reference(light, with_metallic):
     """float64 evaluation through the oracle's samplers -> raw, the gated d_rgb, and every expected gradient."""
     from oracle import texture_oracle as O
-    I = _shade_inputs()
+    I = _shade_inputs(light)
     f64 = lambda t, c: t.double().numpy().reshape(-1, c)
     nn_, vv, al, ro, me = f64(I.n, 3), f64(I.v, 3), f64(I.albedo, 3), f64(I.rough, 1), f64(I.metal, 1)
     ndv = (nn_ * vv).sum(-1, keepdims=True)
@@ -419,13 +433,13 @@ def _shade_reference(with_metallic):
                                  d_metallic=d_metallic, diffuse=(dd[0], dS[0], dcnt[0]), spec=(ds, sS, scnt), shares=shares, mip=mip)
 
 
-@pytest.mark.parametrize("with_metallic", [True, False])
-def test_fused_shading_backward_against_float64(with_metallic):
+def _shade_backward_against_float64(name, with_metallic):
     from pbr import pbr_shading_fused
-    I, R = _shade_inputs(), _shade_reference(with_metallic)
+    I, R = _shade_inputs(name), _shade_reference(name, with_metallic)
     print("clamp shares:", R.shares)
     assert R.shares["excluded"] <= 0.01 and R.shares["high"] >= 0.10 and R.shares["passing"] >= 0.10 and R.shares["low"] >= 0.01
-    assert R.widths == [128, 64, 32] and tuple(I.diffuse.shape) == (6, 16, 16, 3)
+    irr_w = LIGHTS[name][1]
+    assert tuple(R.widths) == LIGHTS[name][0] and tuple(I.diffuse.shape) == (6, irr_w, irr_w, 3)
     assert (R.mip == 0).sum() >= 3 and (R.mip == 1).sum() >= 2 and (R.mip == 2).sum() >= 2 and (I.rough < 0.04).any()
     H, W = SHADE_H, SHADE_W
     for shape in ((H, W), (H * W,)):                            # (H, W, 3): image_width = W; (n, 3): image_width = 0
@@ -437,7 +451,7 @@ def test_fused_shading_backward_against_float64(with_metallic):
                                 metallic=metal, brdf_lut=I.lut.cuda())
         wrt = [albedo, light.diffuse] + light.specular + ([metal] if with_metallic else [])
         grads = torch.autograd.grad(pkg["render_rgb"], wrt, R.d_rgb.view(shape + (3,)).cuda())
-        tag = f"shade metallic={with_metallic} image_width={W if len(shape) == 2 else 0}"
+        tag = f"shade {name} metallic={with_metallic} image_width={W if len(shape) == 2 else 0}"
         err = np.abs(grads[0].cpu().double().numpy().reshape(-1, 3) - R.d_albedo).max()
         print(f"{tag}: d_albedo max err {err:.3e} of {np.abs(R.d_albedo).max():.3e}")
         assert err < 1e-4 * max(1.0, np.abs(R.d_albedo).max())
@@ -446,7 +460,31 @@ def test_fused_shading_backward_against_float64(with_metallic):
             print(f"{tag}: d_metallic max err {err:.3e} of {np.abs(R.d_metallic).max():.3e}")
             assert err < 1e-4 * max(1.0, np.abs(R.d_metallic).max())
         # the reflection vector is itself formed in fp32: 4 w_level in place of w_level
-        worst = _check(f"{tag} d_diffuse", grads[1].cpu().numpy(), *R.diffuse, 4 * 16)
+        worst = _check(f"{tag} d_diffuse", grads[1].cpu().numpy(), *R.diffuse, 4 * irr_w)
         for l, w in enumerate(R.widths):
             worst = max(worst, _check(f"{tag} d_specular[L{l}]", grads[2 + l].cpu().numpy(), R.spec[0][l], R.spec[1][l], R.spec[2][l], 4 * w))
         assert worst <= 1.0, f"{tag}: err / bound = {worst}"
+
+
+@pytest.mark.parametrize("with_metallic", [True, False])
+def test_fused_shading_backward_against_float64(with_metallic):
+    """specular (128, 64, 32) with a 16^2 irradiance map: two levels through the table, the rest private."""
+    _shade_backward_against_float64("table", with_metallic)
+
+
+@pytest.mark.parametrize("with_metallic", [True, False])
+def test_fused_shading_backward_demotes_the_widest_level(with_metallic):
+    """specular (32, 16, 8) with a 32^2 irradiance map, C = 3: all four are small enough for a private copy, 6 (1024 + 256 +
+    64 + 1024) 3 floats = 170496 B, table 32768 B, together 203264 B > 159 KiB = 162816 B.  The widest private slot goes to
+    the table: level 0 and the irradiance map tie at 32 and the level comes first, which leaves 129536 B.  The call must
+    succeed, with level 0 through the table and the other three private."""
+    assert _lds_bytes((32, 16, 8, 32), 3) == (170496, 32768) and 170496 + 32768 == 203264 > LDS_BUDGET == 162816
+    assert 203264 - 6 * 32 * 32 * 3 * 4 == 129536 <= LDS_BUDGET                   # one demotion suffices
+    _shade_backward_against_float64("demoted", with_metallic)
+
+
+@pytest.mark.parametrize("with_metallic", [True, False])
+def test_fused_shading_backward_irradiance_straight_to_memory(with_metallic):
+    """a 64^2 irradiance map gets no private copy and is not a level of the stack: its adds skip the table."""
+    assert LIGHTS["irradiance_direct"][1] > LDS_MAX_WIDTH
+    _shade_backward_against_float64("irradiance_direct", with_metallic)

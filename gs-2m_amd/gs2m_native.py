@@ -193,6 +193,12 @@ SIGNATURES = {
     "gs2m_order_stats": (i, [ll, p, i, p, p, ll, p, p, s]),
     "gs2m_depth_colorize": (i, [i, i, p, p, f, f, p, s]),
     "gs2m_pack_image": (i, [i, i, i, i, p, p, p, p, p, i, i, p, s]),
+    # include/gs2m_visibility.h
+    "gs2m_meshdepth_workspace_bytes": (i, [ll, i, p]),
+    "gs2m_meshdepth_render": (i, [ll, p, ll, p, i, p, d, d, d, d, i, i, d, d, p, p, s]),
+    "gs2m_visibility_votes": (i, [ll, p, i, p, d, d, d, d, i, i, p, d, i, p, s]),
+    "gs2m_visibility_keep": (i, [ll, p, i, p, s]),
+    "gs2m_visibility_referenced": (i, [ll, p, ll, p, p, s]),
 }
 del p, i, f, d, ll, ull, A, s
 EXPORTS = tuple(SIGNATURES)

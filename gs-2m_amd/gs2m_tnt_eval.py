@@ -487,6 +487,24 @@ def read_crop_volume(file):
             "bounding_polygon": np.asarray(d["bounding_polygon"], np.float64).reshape(-1, 3)}
 
 
+def visibility_cull(vertices, triangles, c2w, out_ply=None, device=None, **options):
+    """The mesh culled against the camera-to-world poses `c2w` (gs2m_mesh_cull.cull_mesh_by_visibility; options: its keyword
+    arguments, by default the Tanks and Temples frame and constants), written to `out_ply` when given.
+    -> (vertices, triangles) device tensors, dict(the counts before and after)."""
+    import types
+    import gs2m_mesh as M
+    import gs2m_mesh_cull as K
+    dev = _dev(device)
+    v, f = _points(vertices, dev), triangles_i32(triangles, dev)
+    o = dict(fx=K.TNT_FX, fy=K.TNT_FY, cx=K.TNT_CX, cy=K.TNT_CY, H=K.TNT_HEIGHT, W=K.TNT_WIDTH)
+    o.update(options)
+    cv, cf, _ = K.cull_mesh_by_visibility(v, f, torch.as_tensor(K.world_to_camera(c2w)).to(dev), **o)
+    if out_ply is not None:
+        os.makedirs(os.path.dirname(os.path.abspath(out_ply)), exist_ok=True)
+        M.write_mesh(out_ply, types.SimpleNamespace(vertices=cv.cpu().numpy(), triangles=cf.cpu().numpy(), vertex_colors=np.zeros((len(cv), 3))))
+    return cv, cf, {"n_vertices": int(len(v)), "n_triangles": int(len(f)), "n_vertices_kept": int(len(cv)), "n_triangles_kept": int(len(cf))}
+
+
 # ---- command line: run.py ------------------------------------------------------------------------------------------------
 
 def main(argv=None):
@@ -500,6 +518,8 @@ def main(argv=None):
     ap.add_argument("--rotate-y", type=float, default=0.0, help="rotate the mesh about y first (run_tnt.py: pi / 8 for Truck)")
     ap.add_argument("--no-clouds", action="store_true", help="do not write <scene>.precision.ply and <scene>.recall.ply")
     ap.add_argument("--plot", action="store_true", help="write the precision / recall figure (png and pdf; needs matplotlib)")
+    ap.add_argument("--visibility-cull", action="store_true", help="cull the mesh against --traj-path's cameras first (gs2m_mesh_cull.py with "
+                    "its defaults: the Tanks and Temples frame, 20 views) and write culled_mesh.ply beside the results")
     a = ap.parse_args(argv)
     scene = a.scene or os.path.basename(os.path.normpath(a.dataset_dir))
     if a.tau is None and scene not in SCENES_TAU:
@@ -507,11 +527,16 @@ def main(argv=None):
     tau = a.tau if a.tau is not None else SCENES_TAU[scene]
     out_dir = a.out_dir.strip() or os.path.join(os.path.dirname(a.ply_path), "evaluation")
     verts, tris = read_ply(a.ply_path)
+    culled = None
+    if a.visibility_cull:
+        verts, tris, culled = visibility_cull(verts, tris, read_trajectory(a.traj_path), os.path.join(out_dir, "culled_mesh.ply"))
     gt, _ = read_ply(os.path.join(a.dataset_dir, scene + ".ply"))
     r = evaluate_scene(verts, tris, gt, read_crop_volume(os.path.join(a.dataset_dir, scene + ".json")), tau,
                        read_trajectory(a.traj_path), read_trajectory_log(os.path.join(a.dataset_dir, scene + "_COLMAP_SfM.log")),
                        np.loadtxt(os.path.join(a.dataset_dir, scene + "_trans.txt")), scene=scene, out_dir=out_dir, rotate_y=a.rotate_y,
                        clouds=not a.no_clouds, plot=a.plot)
+    if culled is not None:
+        r["visibility_cull"] = culled
     print(f"[>] {scene}: tau {tau:.3f} precision {r['precision']:.4f} recall {r['recall']:.4f} f-score {r['fscore']:.4f}")
     return r
 

@@ -539,6 +539,8 @@ def parse_args(argv=None):
     ap.add_argument("--scene", default="", help="--tnt: the scene's name (default: the output directory's name)")
     ap.add_argument("--sh-degree", type=int, default=3)
     ap.add_argument("--host-post", action="store_true", help="post-process on the host (numpy / scipy) instead of the device")
+    from gs2m_ingest import add_ingest_arguments
+    add_ingest_arguments(ap)  # COLMAP datasets: the alpha masks fuse_depths cuts the depths with
     a = ap.parse_args(argv)
     if a.dtu and a.tnt:
         ap.error("--dtu and --tnt are two presets: choose one")
@@ -566,7 +568,8 @@ def main(argv=None):
     if a.blender:
         cams, _, _, _, extent = T.load_blender_dataset(a.source_path, "transforms_test.json" if a.split == "test" else "transforms_train.json")
     else:
-        cams, _, _, _, extent = T.load_colmap_dataset(a.source_path, resolution=a.resolution)
+        from gs2m_ingest import ingest_keywords
+        cams, _, _, _, extent = T.load_colmap_dataset(a.source_path, resolution=a.resolution, **ingest_keywords(a))
         if a.split == "test":
             cams = cams[::8]
     model = GaussianModel(a.sh_degree)

@@ -343,12 +343,19 @@ def patch_ncc_torch(pixels, normals, dists, ref_cam, near_cam, ncc_scale, patch,
 
 # ---------------------------------------------------------------- scene side (scene/__init__.py:125-141, 150-204)
 class MultiViewScene:
-    def __init__(self, cameras, gt_images, gaussians, opt=MultiViewParams, ncc_scale=1.0):
+    def __init__(self, cameras, gt_images, gaussians, opt=MultiViewParams, ncc_scale=1.0, gray_images=None):
+        """`gray_images`: one (1, h, w) image per camera at the NCC scale, used as they are (load_colmap_dataset(ingest="device",
+        ncc_scale=...): the reference's own, resized from the original file); None: formed from `gt_images` below."""
         self.cameras, self.gaussians, self.ncc_scale = cameras, gaussians, float(ncc_scale)
         cam = cameras[0]
         ix, iy = torch.meshgrid(torch.arange(cam.image_width), torch.arange(cam.image_height), indexing="xy")
         self.pixels = torch.stack([ix, iy], dim=-1).float().to(cam.device)
-        for c, img in zip(cameras, gt_images):
+        if gray_images is not None:
+            if len(gray_images) != len(cameras):
+                raise ValueError(f"MultiViewScene: {len(gray_images)} gray images for {len(cameras)} cameras")
+            for c, g in zip(cameras, gray_images):
+                c.gray_image = g.contiguous()
+        for c, img in zip(cameras, gt_images) if gray_images is None else ():
             if self.ncc_scale != 1.0:
                 res = (int(c.image_height / self.ncc_scale), int(c.image_width / self.ncc_scale))
                 img = F.interpolate(img[None], size=res, mode="bilinear", align_corners=False, antialias=True)[0]

@@ -199,6 +199,14 @@ SIGNATURES = {
     "gs2m_visibility_votes": (i, [ll, p, i, p, d, d, d, d, i, i, p, d, i, p, s]),
     "gs2m_visibility_keep": (i, [ll, p, i, p, s]),
     "gs2m_visibility_referenced": (i, [ll, p, ll, p, p, s]),
+    # include/gs2m_ingest.h
+    "gs2m_resize_plan_bytes": (i, [i, i, p, p]),
+    "gs2m_resize_plan": (i, [i, i, p]),
+    "gs2m_image_max_u8": (i, [ll, p, p, s]),
+    "gs2m_image_mask_u8": (i, [i, i, p, p, p, p, s]),
+    "gs2m_image_resize_workspace_bytes": (i, [i, i, i, i, i, p]),
+    "gs2m_image_resize_u8": (i, [i, i, i, p, i, i, p, p, p, p, s]),
+    "gs2m_image_unpack": (i, [i, i, i, p, p, p, p, p, p, s]),
 }
 del p, i, f, d, ll, ull, A, s
 EXPORTS = tuple(SIGNATURES)

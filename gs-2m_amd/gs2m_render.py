@@ -278,7 +278,7 @@ def parse_args(argv=None):
     ap.add_argument("--resolution", "-r", type=int, default=1)
     ap.add_argument("--sh-degree", type=int, default=3)
     ap.add_argument("--white_background", action="store_true",
-                    help="white background and RGBA normal maps; needs the views' alpha masks, which only the --blender loader provides")
+                    help="white background and RGBA normal maps; needs the views' alpha masks, which the --blender loader and --device-ingest provide")
     ap.add_argument("--skip_train", action="store_true")
     ap.add_argument("--skip_test", action="store_true")
     ap.add_argument("--extract_mesh", action="store_true")
@@ -294,6 +294,8 @@ def parse_args(argv=None):
     ap.add_argument("--blender", action="store_true", help="render.py's Blender preset: test split only, world-space normals, mesh at 8.0 / 0.004")
     ap.add_argument("--normal_world", action="store_true", help="Save normals in world space, defaults to camera space")
     ap.add_argument("--normal_sobel", action="store_true", help="Use normal estimated from depths")
+    from gs2m_ingest import add_ingest_arguments
+    add_ingest_arguments(ap)  # COLMAP datasets: the views' alpha masks from --masks or the images' alpha channel
     a = ap.parse_args(argv)
     if a.dtu + a.tnt + a.blender > 1:
         ap.error("--dtu, --tnt and --blender are presets: choose one")
@@ -380,7 +382,8 @@ def main(argv=None):
                     cam.alpha_mask = alpha
                 splits[split] = (cams, gts, extent)
     else:
-        cams, gts, _, _, extent = T.load_colmap_dataset(a.source_path, resolution=a.resolution)
+        from gs2m_ingest import ingest_keywords
+        cams, gts, _, _, extent = T.load_colmap_dataset(a.source_path, resolution=a.resolution, **ingest_keywords(a))
         if not a.skip_train:
             splits["train"] = (cams, gts, extent)
         if not a.skip_test:  # every 8th image, the reference's llffhold (as gs2m_mesh.py --split test)

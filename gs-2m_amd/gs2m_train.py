@@ -129,18 +129,63 @@ def export_colmap_dataset(folder, scene):
                   (np.asarray(cols) * 255.0 + 0.5).astype(np.uint8))
 
 
-def load_colmap_dataset(folder, images="images", device="cuda", resolution=1):
+def _device_view(info, path, mask_dir, device, resolution, mask_gt, ncc_scale):
+    """One view of load_colmap_dataset(ingest="device"): loadCam + Camera.__init__ (utils/camera_utils.py:19-48,
+    scene/cameras.py:49-56) through gs2m_ingest, one upload for the training image, the mask and the gray image.
+    -> (camera with alpha_mask [and gray_image], ground-truth image)"""
+    from PIL import Image as PILImage
+    import gs2m_ingest
+    with PILImage.open(path) as f:
+        img = f.copy()
+    assert img.size == (info.width, info.height), "image size differs from the COLMAP camera"
+    if img.mode not in ("RGB", "RGBA"):
+        raise ValueError(f"load_colmap_dataset: {path} has mode {img.mode}; the device ingestion trains on 8-bit RGB and RGBA images")
+    mask = None
+    if mask_dir != "":  # scene/dataset_readers.py:97-101
+        with PILImage.open(os.path.join(mask_dir, os.path.splitext(os.path.basename(info.image_name))[0] + ".png")) as f:
+            mask = f.convert("L")
+    w, h = gs2m_ingest.target_resolution(info.width, info.height, resolution)
+    staged = gs2m_ingest.stage(img, mask_gt, mask, device, name=path)
+    gray_res = None if ncc_scale is None else (int(w / ncc_scale), int(h / ncc_scale))
+    same = gray_res == (w, h)  # ncc_scale 1: the gray image comes out of the training image's own pass
+    out = gs2m_ingest.process_input_image(staged, (w, h), gray=same)
+    rgb, alpha, gray = out[0], out[1], (out[2] if same else None)
+    cam = Camera(S.make_camera(w, h, fx=info.Fx * w / info.width, fy=info.Fy * h / info.height, R=info.R, T=info.T), device)
+    cam.alpha_mask = alpha if alpha is not None else torch.ones_like(rgb[0:1])
+    cam.has_mask = alpha is not None  # a mask file or an alpha channel was read
+    if gray_res is not None:
+        cam.gray_image = gray if gray is not None else gs2m_ingest.gray_image(staged, gray_res)
+    return cam, rgb
+
+
+def load_colmap_dataset(folder, images="images", device="cuda", resolution=1, *, ingest="host", masks="", mask_gt=False, ncc_scale=None):
     """COLMAP-format dataset -> the `scene` tuple `train()` takes: cameras with the reference's matrices
     (scene/cameras.py:58-67), ground-truth images, the sparse points and colours, and the scene radius
-    (readColmapSceneInfo, scene/dataset_readers.py:141-197; images sorted by name, PINHOLE / SIMPLE_PINHOLE only)."""
+    (readColmapSceneInfo, scene/dataset_readers.py:141-197; images sorted by name, PINHOLE / SIMPLE_PINHOLE only).
+    `ingest="device"`: the images go through gs2m_ingest -- the reference's resize filter and target size,
+    `masks` (a folder of <stem>.png, absolute or relative to the dataset) or the alpha channel of RGBA images, `mask_gt` -- and
+    every camera gets `alpha_mask` (ones without a mask, scene/cameras.py:54) and, with `ncc_scale` not None, `gray_image` at
+    (int(w / ncc_scale), int(h / ncc_scale)) from the same upload (scene/__init__.py:193-204)."""
     import numpy as np
     from PIL import Image as PILImage
     import gs2m_colmap as C
+    if ingest not in ("host", "device"):
+        raise ValueError(f"load_colmap_dataset: ingest must be 'host' or 'device', got {ingest!r}")
+    if ingest == "host":
+        for flag, on in (("masks", masks != ""), ("mask_gt", mask_gt), ("ncc_scale", ncc_scale is not None)):
+            if on:
+                raise ValueError(f"load_colmap_dataset: `{flag}` needs ingest='device' (--device-ingest); ingest='host' reads no masks and no gray images")
     sparse = os.path.join(folder, "sparse", "0")
     intr = C.read_intrinsics_binary(os.path.join(sparse, "cameras.bin"))
     infos = sorted(C.colmap_cameras(C.read_extrinsics_binary(os.path.join(sparse, "images.bin")), intr), key=lambda c: c.image_name)
     cams, gts = [], []
+    mask_dir = "" if masks == "" else (masks if os.path.isabs(masks) else os.path.join(folder, masks))
     for info in infos:
+        if ingest == "device":
+            cam, gt = _device_view(info, os.path.join(folder, images, info.image_name), mask_dir, device, resolution, mask_gt, ncc_scale)
+            cams.append(cam)
+            gts.append(gt)
+            continue
         img = PILImage.open(os.path.join(folder, images, info.image_name)).convert("RGB")
         assert img.size == (info.width, info.height), "image size differs from the COLMAP camera"
         w, h, fx, fy = info.width, info.height, info.Fx, info.Fy
@@ -262,8 +307,10 @@ def train(iterations=1000, W=640, H=360, n_views=12, n_true=60_000, seed=0, geom
           device="cuda", scene=None, material_from_iter=None, light_res=128, lambda_smooth=0.0, lambda_normal=0.1,
           lambda_multi_view=0.0, mv_opt=None, lambda_rough=0.0, trim_interval=1000, alpha_masks=None,
           white_background=False, dp=False, dp_mode="auto", ssim_fn=None, optimizer_cls=None, pipe=None, views_per_rank=1,
-          callback=None):
-    """`dp=True`: view-parallel data parallelism over the initialised torch.distributed group: every
+          callback=None, gray_images=None, ncc_scale=1.0):
+    """`gray_images`, `ncc_scale`: the multi-view scene's gray images (one (1, h, w) per camera at `ncc_scale`, as
+    load_colmap_dataset(ingest="device", ncc_scale=...) leaves them in cam.gray_image) in place of the ones it forms itself.
+    `dp=True`: view-parallel data parallelism over the initialised torch.distributed group: every
     rank holds the full model, an iteration renders `world_size` different views (rank r takes the r-th of the next
     `world_size` entries of the shared random view order), the parameter gradients are SUMMED over the ranks with one
     blocking collective before the optimizer step, and the densification side channels are reduced with the
@@ -309,7 +356,7 @@ def train(iterations=1000, W=640, H=360, n_views=12, n_true=60_000, seed=0, geom
     if lambda_multi_view > 0 or lambda_rough > 0:  # train.py:121-130, 195: the multi-view terms
         import gs2m_mvs
         mv_opt = mv_opt or gs2m_mvs.MultiViewParams()
-        mv_scene = gs2m_mvs.MultiViewScene(cams, gts, gaussians, mv_opt)
+        mv_scene = gs2m_mvs.MultiViewScene(cams, gts, gaussians, mv_opt, ncc_scale=ncc_scale, gray_images=gray_images)
     lighting, rays, dn_weights, dn_edges = None, {}, {}, {}
     if material_from_iter < iterations:
         from pbr import pbr_render
@@ -502,6 +549,10 @@ if __name__ == "__main__":
     ap.add_argument("--source-path", "-s", default=None, help="COLMAP-format dataset (sparse/0/*.bin + images/); default: synthetic scene")
     ap.add_argument("--resolution", "-r", type=int, default=1, help="down-scale factor for a COLMAP dataset's images")
     ap.add_argument("--blender", action="store_true", help="--source-path is a NeRF-synthetic (transforms_train.json) dataset")
+    from gs2m_ingest import add_ingest_arguments, ingest_keywords
+    add_ingest_arguments(ap)
+    ap.add_argument("--multi_view_ncc_scale", type=float, default=-1.0, help="--device-ingest --multi-view: scale of the NCC gray images "
+                    "(default: 1 / r for -r 1, 2, 4, 8, as scene/__init__.py:127-132)")
     ap.add_argument("--export-colmap", default=None, help="write the synthetic scene as a COLMAP-format dataset to this folder and exit")
     ap.add_argument("--c4", default=None, metavar="FOLDER", help="BASELINE configs[3] substitute (see C4 above): write the scene to FOLDER, train --iterations on it")
     ap.add_argument("--c4-detail", type=float, default=None, help="experiment: texture frequency of the C4 substitute scene")
@@ -529,9 +580,14 @@ if __name__ == "__main__":
     if a.export_colmap:
         export_colmap_dataset(a.export_colmap, synthetic_scene(a.true_gaussians, a.views, a.width, a.height))
         sys.exit(0)
-    scene = None
-    if a.source_path:
-        scene = load_blender_dataset(a.source_path) if a.blender else load_colmap_dataset(a.source_path, resolution=a.resolution)
+    scene, ncc_scale, masked = None, None, False
+    if a.source_path and a.blender:
+        scene = load_blender_dataset(a.source_path)
+    elif a.source_path:
+        if a.device_ingest and a.multi_view:  # scene/__init__.py:127-132
+            ncc_scale = a.multi_view_ncc_scale if a.multi_view_ncc_scale > 0 else (1.0 / a.resolution if a.resolution in (1, 2, 4, 8) else 1.0)
+        scene = load_colmap_dataset(a.source_path, resolution=a.resolution, ncc_scale=ncc_scale, **ingest_keywords(a))
+        masked = any(getattr(c, "has_mask", False) for c in scene[0])
     mv = None
     if a.multi_view:
         import gs2m_mvs
@@ -541,7 +597,9 @@ if __name__ == "__main__":
     model, st = train(a.iterations, a.width, a.height, a.views, a.true_gaussians, log=max(1, a.iterations // 10), scene=scene,
                       geometry_from_iter=a.geometry_from, material_from_iter=a.material_from, mv_opt=mv,
                       lambda_multi_view=OptimizationParams.lambda_multi_view if a.multi_view else 0.0,
-                      lambda_rough=OptimizationParams.lambda_rough if a.multi_view else 0.0)
+                      lambda_rough=OptimizationParams.lambda_rough if a.multi_view else 0.0,
+                      alpha_masks=[c.alpha_mask for c in scene[0]] if masked else None,
+                      gray_images=None if ncc_scale is None else [c.gray_image for c in scene[0]], ncc_scale=ncc_scale or 1.0)
     print({k: (round(v, 4) if isinstance(v, float) else v) for k, v in st.items() if k not in ("pbr_loss", "lighting", "mv_loss")})
     if a.save_ply:
         model.save_ply(a.save_ply)

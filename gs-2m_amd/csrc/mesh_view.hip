@@ -1,0 +1,232 @@
+// Mesh visualisation: the visibility buffer, the vertex normals and the headlight shade of include/gs2m_meshview.h
+// (the contract: DESIGN.md §16).
+//
+// Visibility: the shared rasterizer core of mesh_raster.h on the sample frame (H ss, W ss), with the sink that keeps the 64-bit
+// unsigned minimum of (z bits << 32) | triangle index.  The buffer starts as all ones and stays so where nothing reaches.
+// Normals: a thread per triangle adds the unit face normal in 2^-32 units to the three vertices' int64 sums (integer atomics:
+// exact, whatever the order), then a thread per vertex normalises.
+// Shade: a thread per output pixel walks its ss x ss keys in row-major order; per covered sample it gathers the triangle's three
+// indices and vertices (84 bytes; neighbours mostly share the triangle, so the loads hit the cache), recomputes the barycentrics
+// at the sample's ray, shades, and at the end writes the four bytes.  Keys are not trusted: a triangle index or a vertex index
+// out of range makes the sample empty.  All fp64, as written.
+#include <math.h>
+#include "eval_common.h"
+#include "mesh_raster.h"
+#include "../../include/gs2m_meshview.h"
+
+using namespace mesh_raster;
+
+namespace {
+
+constexpr u64 EMPTY_KEY = ~0ull;
+constexpr double FIX = 4294967296.0;  // 2^32: the unit of the normal sums
+
+__global__ void __launch_bounds__(256) normal_sums_kernel(long long nv, const double* __restrict__ verts, long long nt,
+                                                          const int* __restrict__ tris, u64* __restrict__ sums, int* __restrict__ err) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= nt) return;
+    const int ia = tris[3 * t], ib = tris[3 * t + 1], ic = tris[3 * t + 2];
+    if (!tri_in_range(ia, ib, ic, nv, err)) return;
+    double P[9], n[3];
+    load_triangle(verts, tris, t, P);
+    const double ab[3] = {P[3] - P[0], P[4] - P[1], P[5] - P[2]}, ac[3] = {P[6] - P[0], P[7] - P[1], P[8] - P[2]};
+    cross3(ab, ac, n);
+    if (n[0] == 0.0 && n[1] == 0.0 && n[2] == 0.0) return;
+    const double len = sqrt(dot3(n, n));
+    const double u[3] = {n[0] / len, n[1] / len, n[2] / len};
+    if (!(isfinite(u[0]) && isfinite(u[1]) && isfinite(u[2]))) return;
+    const int id[3] = {ia, ib, ic};
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const u64 q = (u64)llrint(u[k] * FIX);  // |u| <= 1: two's complement sums of at most 2^31 terms stay within int64
+        if (q == 0) continue;
+#pragma unroll
+        for (int j = 0; j < 3; j++) atomicAdd(sums + 3 * (size_t)id[j] + k, q);
+    }
+}
+
+__global__ void __launch_bounds__(256) normalise_kernel(long long nv, const long long* __restrict__ sums, double* __restrict__ normals) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nv) return;
+    const long long q[3] = {sums[3 * i], sums[3 * i + 1], sums[3 * i + 2]};
+    double o[3] = {0.0, 0.0, 0.0};
+    if (q[0] != 0 || q[1] != 0 || q[2] != 0) {
+        const double s[3] = {(double)q[0], (double)q[1], (double)q[2]};
+        const double len = sqrt(dot3(s, s));
+        o[0] = s[0] / len, o[1] = s[1] / len, o[2] = s[2] / len;
+    }
+    normals[3 * i] = o[0], normals[3 * i + 1] = o[1], normals[3 * i + 2] = o[2];
+}
+
+struct Shade {
+    const double* normals;  // null: flat
+    const float* colors;    // null: base
+    double base[3], ambient, diffuse;
+    int srgb, ss;
+};
+
+__device__ __forceinline__ double encode(double x, int srgb) {
+    if (!srgb) return x;
+    return x <= 0.0031308 ? 12.92 * x : 1.055 * pow(x, 1.0 / 2.4) - 0.055;
+}
+
+// q: the SAMPLE frame; W, H: the output frame
+__global__ void __launch_bounds__(256) shade_kernel(long long nv, const double* __restrict__ verts, long long nt,
+                                                    const int* __restrict__ tris, const double* __restrict__ w2c, Frame q, int W, int H,
+                                                    const u64* __restrict__ vis, Shade sh, unsigned char* __restrict__ rgba,
+                                                    float* __restrict__ depth, int* __restrict__ tri_id) {
+    const int v = blockIdx.y;
+    const long long pix = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (pix >= (long long)W * H) return;
+    const int px = (int)(pix % W), py = (int)(pix / W);
+    const int ss = sh.ss;
+    const double* M = w2c + 16 * (size_t)v;
+    const u64* keys = vis + (size_t)v * q.W * q.H;
+    double sum[3] = {0.0, 0.0, 0.0};
+    int m = 0;
+    float zc = 0.f;
+    int tc = -1;
+    for (int k = 0; k < ss * ss; k++) {
+        const int i = px * ss + k % ss, j = py * ss + k / ss;
+        const u64 key = keys[(size_t)j * q.W + i];
+        if (key == EMPTY_KEY) continue;
+        const long long t = (long long)(key & 0xFFFFFFFFull);
+        if (t >= nt) continue;
+        const int id[3] = {tris[3 * t], tris[3 * t + 1], tris[3 * t + 2]};
+        if (id[0] < 0 || id[1] < 0 || id[2] < 0 || id[0] >= nv || id[1] >= nv || id[2] >= nv) continue;
+        double P[9], a[3], b[3], c[3], r[3], x[3];
+        load_triangle(verts, tris, t, P);
+        to_camera(M, P, a);
+        to_camera(M, P + 3, b);
+        to_camera(M, P + 6, c);
+        pixel_ray(q, i, j, r);
+        cross3(b, c, x);
+        const double e0 = dot3(x, r);
+        cross3(c, a, x);
+        const double e1 = dot3(x, r);
+        cross3(a, b, x);
+        const double e2 = dot3(x, r);
+        const double s = (e0 + e1) + e2;
+        const double l0 = e0 / s, l1 = e1 / s, l2 = e2 / s;
+        const double ab[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, ac[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
+        double N[3];
+        cross3(ab, ac, N);
+        if (sh.normals) {
+            double S[3];
+            bool ok = true;
+#pragma unroll
+            for (int w = 0; w < 3; w++) S[w] = 0.0;
+            const double l[3] = {l0, l1, l2};
+            double C3[3][3];
+#pragma unroll
+            for (int w = 0; w < 3; w++) {
+                const double* nw = sh.normals + 3 * (size_t)id[w];
+                const double n0 = nw[0], n1 = nw[1], n2 = nw[2];
+                ok = ok && !(n0 == 0.0 && n1 == 0.0 && n2 == 0.0);
+#pragma unroll
+                for (int d = 0; d < 3; d++) C3[w][d] = (M[4 * d] * n0 + M[4 * d + 1] * n1) + M[4 * d + 2] * n2;
+            }
+#pragma unroll
+            for (int d = 0; d < 3; d++) S[d] = (l[0] * C3[0][d] + l[1] * C3[1][d]) + l[2] * C3[2][d];
+            ok = ok && isfinite(S[0]) && isfinite(S[1]) && isfinite(S[2]) && !(S[0] == 0.0 && S[1] == 0.0 && S[2] == 0.0);
+            if (ok) N[0] = S[0], N[1] = S[1], N[2] = S[2];
+        }
+        const double cosv = fabs(dot3(N, r)) / sqrt(dot3(N, N) * dot3(r, r));
+        const double light = sh.ambient + sh.diffuse * cosv;
+#pragma unroll
+        for (int d = 0; d < 3; d++) {
+            double alb = sh.base[d];
+            if (sh.colors)
+                alb = (l0 * (double)sh.colors[3 * (size_t)id[0] + d] + l1 * (double)sh.colors[3 * (size_t)id[1] + d]) +
+                      l2 * (double)sh.colors[3 * (size_t)id[2] + d];
+            sum[d] = sum[d] + fmin(fmax(alb * light, 0.0), 1.0);
+        }
+        m++;
+        if (k == (ss / 2) * (ss + 1)) zc = __uint_as_float((unsigned)(key >> 32)), tc = (int)t;
+    }
+    const size_t o = (size_t)v * W * H + (size_t)pix;
+    uchar4 out = make_uchar4(0, 0, 0, 0);
+    if (m > 0) {
+        unsigned char by[3];
+#pragma unroll
+        for (int d = 0; d < 3; d++) by[d] = (unsigned char)floor(255.0 * encode(sum[d] / (double)m, sh.srgb) + 0.5);
+        out = make_uchar4(by[0], by[1], by[2], (unsigned char)floor(255.0 * (double)m / (double)(ss * ss) + 0.5));
+    }
+    reinterpret_cast<uchar4*>(rgba)[o] = out;
+    if (depth) depth[o] = zc;
+    if (tri_id) tri_id[o] = tc;
+}
+
+bool view_frame_ok(int n_views, int W, int H, int ss, double fx, double fy, double cx, double cy) {
+    return ss >= 1 && ss <= 4 && W >= 1 && H >= 1 && frame_ok(n_views, (long long)W * ss, (long long)H * ss, fx, fy, cx, cy);
+}
+
+}  // namespace
+
+extern "C" {
+
+int gs2m_meshview_workspace_bytes(long long n_tris, int n_views, long long* bytes) {
+    if (n_tris < 0 || n_views < 0 || !bytes) return GS2M_ERR_INVALID_ARG;
+    if (n_tris > 0x7FFFFFFFll || n_views > 65535) return GS2M_ERR_UNSUPPORTED;
+    *bytes = (long long)carve_raster(nullptr, n_tris, n_views).bytes;
+    return GS2M_OK;
+}
+
+int gs2m_meshview_visibility(long long n_verts, const double* verts, long long n_tris, const int* tris, int n_views,
+                             const double* w2c, double fx, double fy, double cx, double cy, int W, int H, int ss, double near_z,
+                             double far_z, void* ws, unsigned long long* vis, void* stream) {
+    if (n_verts < 0 || n_tris < 0 || n_tris > 0xFFFFFFFEll || !view_frame_ok(n_views, W, H, ss, fx, fy, cx, cy) || !ws)
+        return GS2M_ERR_INVALID_ARG;
+    if (!(near_z > 0.0 && near_z <= far_z && isfinite(far_z))) return GS2M_ERR_INVALID_ARG;
+    if (n_views > 0 && (!w2c || !vis)) return GS2M_ERR_INVALID_ARG;
+    if (n_tris > 0 && (!tris || (n_verts > 0 && !verts))) return GS2M_ERR_INVALID_ARG;
+    if (n_tris > 0x7FFFFFFFll || n_verts > 0x7FFFFFFFll) return GS2M_ERR_UNSUPPORTED;  // ids are int, list entries 32-bit
+    hipStream_t s = (hipStream_t)stream;
+    const RasterWs w = carve_raster((char*)ws, n_tris, n_views);
+    const Frame q{ss * fx, ss * fy, ss * cx, ss * cy, near_z, far_z, W * ss, H * ss};
+    const size_t samples = (size_t)n_views * q.W * q.H;
+    if (n_views > 0 && hipMemsetAsync(vis, 0xFF, sizeof(u64) * samples, s) != hipSuccess) return GS2M_ERR_HIP;
+    if (raster_launch(n_verts, verts, n_tris, tris, n_views, w2c, q, w, KeySink{(u64*)vis}, s) != GS2M_OK) return GS2M_ERR_HIP;
+    int err;
+    if (gs2m_read_back(s, {{&err, w.err, sizeof(err)}}) != GS2M_OK) return GS2M_ERR_HIP;
+    return err ? GS2M_ERR_INVALID_ARG : GS2M_OK;
+}
+
+int gs2m_meshview_normals_workspace_bytes(long long* bytes) {
+    if (!bytes) return GS2M_ERR_INVALID_ARG;
+    *bytes = GS2M_ALIGN;  // the flag
+    return GS2M_OK;
+}
+
+int gs2m_meshview_normals(long long n_verts, const double* verts, long long n_tris, const int* tris, void* ws, long long* sums,
+                          double* normals, void* stream) {
+    if (n_verts < 0 || n_tris < 0 || !ws || (n_verts > 0 && (!verts || !sums || !normals)) || (n_tris > 0 && !tris)) return GS2M_ERR_INVALID_ARG;
+    if (n_tris > 0x7FFFFFFFll || n_verts > 0x7FFFFFFFll) return GS2M_ERR_UNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    int* d_err = (int*)ws;
+    if (hipMemsetAsync(d_err, 0, sizeof(int), s) != hipSuccess) return GS2M_ERR_HIP;
+    if (n_verts > 0 && hipMemsetAsync(sums, 0, sizeof(long long) * 3 * (size_t)n_verts, s) != hipSuccess) return GS2M_ERR_HIP;
+    if (n_tris > 0) normal_sums_kernel<<<blocks_of(n_tris), 256, 0, s>>>(n_verts, verts, n_tris, tris, (u64*)sums, d_err);
+    if (n_verts > 0) normalise_kernel<<<blocks_of(n_verts), 256, 0, s>>>(n_verts, sums, normals);
+    int err;
+    if (gs2m_read_back(s, {{&err, d_err, sizeof(err)}}) != GS2M_OK) return GS2M_ERR_HIP;
+    return err ? GS2M_ERR_INVALID_ARG : GS2M_OK;
+}
+
+int gs2m_meshview_shade(long long n_verts, const double* verts, long long n_tris, const int* tris, int n_views, const double* w2c,
+                        double fx, double fy, double cx, double cy, int W, int H, int ss, const unsigned long long* vis,
+                        const double* normals, const float* colors, double base_r, double base_g, double base_b, double ambient,
+                        double diffuse, int srgb, unsigned char* rgba, float* depth, int* tri_id, void* stream) {
+    if (n_verts < 0 || n_tris < 0 || !view_frame_ok(n_views, W, H, ss, fx, fy, cx, cy)) return GS2M_ERR_INVALID_ARG;
+    if (n_views > 0 && (!w2c || !vis || !rgba)) return GS2M_ERR_INVALID_ARG;
+    if (n_tris > 0 && (!tris || (n_verts > 0 && !verts))) return GS2M_ERR_INVALID_ARG;
+    if (n_tris > 0x7FFFFFFFll || n_verts > 0x7FFFFFFFll) return GS2M_ERR_UNSUPPORTED;
+    if (n_views == 0) return GS2M_OK;
+    const Frame q{ss * fx, ss * fy, ss * cx, ss * cy, 0.0, 0.0, W * ss, H * ss};
+    const Shade sh{normals, colors, {base_r, base_g, base_b}, ambient, diffuse, srgb ? 1 : 0, ss};
+    shade_kernel<<<dim3(blocks_of((long long)W * H), (unsigned)n_views), 256, 0, (hipStream_t)stream>>>(
+        n_verts, verts, n_tris, tris, w2c, q, W, H, (const u64*)vis, sh, rgba, depth, tri_id);
+    return gs2m_status(hipGetLastError());
+}
+
+}  // extern "C"

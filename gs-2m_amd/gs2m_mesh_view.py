@@ -1,0 +1,292 @@
+"""Shaded views and turntable frames of a mesh on the GPU (csrc/mesh_view.hip; include/gs2m_meshview.h).
+
+The reference's scripts/vis_dtu.py and scripts/vis_shiny.py, which need Blender and Cycles, as DESIGN.md §16 writes the contract
+down: the mesh is rasterized into a visibility buffer (nearest triangle per sample, the z-buffer rasterizer of the visibility
+cull), shaded grey with a light at the camera (a Lambert term above an ambient floor), resolved over ss x ss samples per pixel and
+encoded as straight-alpha sRGB bytes.  Everything is fp64 on device tensors owned here; there is no CPU path.
+
+    python gs-2m_amd/gs2m_mesh_view.py --ply-path M.ply --cameras MODEL/cameras.json --rendering --still --animation
+    python gs-2m_amd/gs2m_mesh_view.py --ply-path M.ply -s SCENE -r 2 --rendering --shading smooth --colour vertex
+write views/<stem>.png, still.png, frames/000.png .. 119.png, anim.gif and anim.webp under --out-dir (default: visual/ beside the
+mesh's directory).
+"""
+import argparse
+import json
+import math
+import os
+import sys
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+if _HERE not in sys.path:
+    sys.path.insert(0, _HERE)
+
+import numpy as np
+import torch
+
+import gs2m_native as N
+from gs2m_eval_util import device as _dev, ptr as _ptr, workspace_for
+from gs2m_mesh_cull import FAR, NEAR, _mesh_args, _on_device
+
+VIS_BUDGET = 512 << 20  # bytes of visibility buffer a batch of views may take
+BASE, AMBIENT, DIFFUSE = (0.7, 0.7, 0.7), 0.15, 0.85
+STILL_SIZE, FRAMES, FPS, VIEW_IDX = 600, 120, 24, 23
+
+
+def vertex_normals(vertices, triangles):
+    """Open3D's compute_vertex_normals: per vertex the sum of its triangles' unit normals, kept exactly as int64 in units of
+    2^-32, and that sum normalised.  -> (normals (V, 3) fp64, sums (V, 3) int64), device tensors."""
+    who = "vertex_normals"
+    v = _on_device(vertices, "vertices", who, torch.float64, (3,))
+    f = _on_device(triangles, "triangles", who, torch.int32, (3,))
+    sums = torch.empty((len(v), 3), dtype=torch.int64, device=v.device)
+    normals = torch.empty((len(v), 3), dtype=torch.float64, device=v.device)
+    ws = workspace_for("gs2m_meshview_normals_workspace_bytes", v.device)
+    N.launch("gs2m_meshview_normals", v.device, len(v), _ptr(v), len(f), _ptr(f), _ptr(ws), _ptr(sums), _ptr(normals))
+    return normals, sums
+
+
+def _check_frame(H, W, ss, who):
+    """what the library would refuse, before a buffer is sized by it -> (H, W, ss) as int"""
+    if int(ss) != ss or not 1 <= int(ss) <= 4:
+        raise RuntimeError(f"{who}: invalid argument: `ss` must be 1, 2, 3 or 4, got {ss!r}")
+    H, W, ss = int(H), int(W), int(ss)
+    if H < 1 or W < 1 or H * ss * W * ss > 2 ** 31 - 1:
+        raise RuntimeError(f"{who}: invalid argument: a frame of {W} x {H} at ss = {ss} is empty or has more than 2^31 - 1 samples")
+    return H, W, ss
+
+
+def visibility_buffer(vertices, triangles, w2c, fx, fy, cx, cy, H, W, ss=1, near=NEAR, far=FAR, out=None):
+    """The nearest triangle through every sample: (n_views, H ss, W ss) int64 on the device whose bits are the unsigned key
+    (bits of the fp32 z << 32) | triangle index, all ones (-1) where there is none.  The sample frame has the intrinsics
+    (ss fx, ss fy, ss cx, ss cy).  out: an int64 buffer of at least n_views H W ss^2 elements to render into."""
+    who = "visibility_buffer"
+    v, f, m = _mesh_args(vertices, triangles, w2c, who)
+    H, W, ss = _check_frame(H, W, ss, who)
+    dev, n, count = v.device, len(m), len(m) * H * W * ss * ss
+    if out is None:
+        vis = torch.empty(count, dtype=torch.int64, device=dev)
+    else:
+        if not torch.is_tensor(out) or out.device != dev or out.dtype != torch.int64 or not out.is_contiguous() or out.numel() < count:
+            raise RuntimeError(f"{who}: `out` must be a contiguous int64 tensor of at least {count} elements on {dev}")
+        vis = out.reshape(-1)[:count]
+    ws = workspace_for("gs2m_meshview_workspace_bytes", dev, len(f), n)
+    N.launch("gs2m_meshview_visibility", dev, len(v), _ptr(v), len(f), _ptr(f), n, _ptr(m), float(fx), float(fy), float(cx), float(cy),
+             W, H, ss, float(near), float(far), _ptr(ws), _ptr(vis))
+    return vis.view(n, H * ss, W * ss)
+
+
+def shade_views(vertices, triangles, w2c, fx, fy, cx, cy, H, W, ss=2, shading="flat", colors=None, base=BASE, ambient=AMBIENT,
+                diffuse=DIFFUSE, srgb=True, view_batch=None, return_aux=False, near=NEAR, far=FAR):
+    """Shaded RGBA views of the mesh: (n_views, H, W, 4) uint8 on the device, straight alpha = the covered share of the pixel's
+    ss x ss samples.  shading: "flat" (the face normal) or "smooth" (vertex normals interpolated).  colors: (V, 3) vertex colours
+    in [0, 1] as the albedo instead of `base`.  The views go through the rasterizer `view_batch` at a time (default: as many as
+    keep the visibility buffer under 512 MiB) into one reused buffer.  return_aux: also depth (n, H, W) float32 and tri_id
+    (n, H, W) int32 of each pixel's centre sample, 0 and -1 where it is empty."""
+    who = "shade_views"
+    v, f, m = _mesh_args(vertices, triangles, w2c, who)
+    H, W, ss = _check_frame(H, W, ss, who)
+    if shading not in ("flat", "smooth"):
+        raise RuntimeError(f"{who}: `shading` must be 'flat' or 'smooth', got {shading!r}")
+    col = None if colors is None else _on_device(colors, "colors", who, torch.float32, (3,))
+    if col is not None and len(col) != len(v):
+        raise RuntimeError(f"{who}: {len(col)} colours for {len(v)} vertices")
+    base = [float(x) for x in base]
+    if len(base) != 3:
+        raise RuntimeError(f"{who}: `base` must hold three values")
+    dev, n = v.device, len(m)
+    normals = vertex_normals(v, f)[0] if shading == "smooth" else None
+    per_view = 8 * H * W * ss * ss
+    batch = int(view_batch) if view_batch else max(1, VIS_BUDGET // max(per_view, 1))
+    batch = max(1, min(batch, max(n, 1)))
+    rgba = torch.empty((n, H, W, 4), dtype=torch.uint8, device=dev)
+    depth = torch.empty((n, H, W), dtype=torch.float32, device=dev) if return_aux else None
+    tri_id = torch.empty((n, H, W), dtype=torch.int32, device=dev) if return_aux else None
+    buf = torch.empty(batch * H * W * ss * ss, dtype=torch.int64, device=dev)
+    for k in range(0, max(n, 1), batch):  # (with no view one call still checks the arguments and the indices)
+        part = m[k:k + batch]
+        vis = visibility_buffer(v, f, part, fx, fy, cx, cy, H, W, ss, near, far, out=buf)
+        N.launch("gs2m_meshview_shade", dev, len(v), _ptr(v), len(f), _ptr(f), len(part), _ptr(part), float(fx), float(fy), float(cx),
+                 float(cy), W, H, ss, _ptr(vis), _ptr(normals), _ptr(col), base[0], base[1], base[2], float(ambient), float(diffuse),
+                 1 if srgb else 0, _ptr(rgba[k:k + batch]), None if depth is None else _ptr(depth[k:k + batch]),
+                 None if tri_id is None else _ptr(tri_id[k:k + batch]))
+    return (rgba, depth, tri_id) if return_aux else rgba
+
+
+def turntable(w2c, frames=FRAMES, shift=(0.0, 0.0, 0.0)):
+    """The rocking animation of vis_dtu.py's export_anim as cameras: the mesh, moved by `shift`, turns about its x axis by
+    0.4 sin(2 pi f / frames) and then about its y axis by 0.6 sin(4 pi f / frames) (Euler XYZ); composed into the camera:
+    w2c @ T(shift) @ Ry @ Rx.  w2c: (4, 4) world-to-camera.  -> (frames, 4, 4) float64 numpy."""
+    w = np.asarray(torch.as_tensor(w2c).detach().cpu().numpy() if torch.is_tensor(w2c) else w2c, np.float64).reshape(4, 4)
+    T = np.eye(4)
+    T[:3, 3] = np.asarray(shift, np.float64)
+    out = np.empty((int(frames), 4, 4), np.float64)
+    for k in range(int(frames)):
+        ax, ay = 0.4 * math.sin(2.0 * math.pi * k / frames), 0.6 * math.sin(4.0 * math.pi * k / frames)
+        Rx, Ry = np.eye(4), np.eye(4)
+        Rx[1:3, 1:3] = [[math.cos(ax), -math.sin(ax)], [math.sin(ax), math.cos(ax)]]
+        Ry[0, 0], Ry[0, 2], Ry[2, 0], Ry[2, 2] = math.cos(ay), math.sin(ay), -math.sin(ay), math.cos(ay)
+        out[k] = w @ T @ Ry @ Rx
+    return out
+
+
+# ---- files -------------------------------------------------------------------------------------------------------------------
+
+def read_cameras_json(path):
+    """MODEL/cameras.json, the reference's camera_to_JSON records -> a list of dict(name, width, height, fx, fy, cx, cy, w2c):
+    `rotation` and `position` are the camera-to-world pose (OpenCV convention), the principal point is the frame's centre."""
+    with open(str(path)) as f:
+        records = json.load(f)
+    views = []
+    for r in records:
+        c2w = np.eye(4)
+        c2w[:3, :3], c2w[:3, 3] = np.asarray(r["rotation"], np.float64).reshape(3, 3), np.asarray(r["position"], np.float64).reshape(3)
+        w, h = int(r["width"]), int(r["height"])
+        views.append(dict(name=str(r["img_name"]), width=w, height=h, fx=float(r["fx"]), fy=float(r["fy"]), cx=0.5 * w, cy=0.5 * h,
+                          w2c=np.linalg.inv(c2w)))
+    return views
+
+
+def read_colmap_views(folder):
+    """SCENE/sparse/0 through the readers gs2m_train.load_colmap_dataset is built on (images sorted by name; no image is opened)
+    -> the same list as read_cameras_json."""
+    import gs2m_colmap as C
+    sparse = os.path.join(str(folder), "sparse", "0")
+    intr = C.read_intrinsics_binary(os.path.join(sparse, "cameras.bin"))
+    infos = sorted(C.colmap_cameras(C.read_extrinsics_binary(os.path.join(sparse, "images.bin")), intr), key=lambda c: c.image_name)
+    views = []
+    for info in infos:
+        w2c = np.eye(4)
+        w2c[:3, :3], w2c[:3, 3] = np.asarray(info.R, np.float64).T, np.asarray(info.T, np.float64)
+        views.append(dict(name=str(info.image_name), width=int(info.width), height=int(info.height), fx=float(info.Fx), fy=float(info.Fy),
+                          cx=0.5 * info.width, cy=0.5 * info.height, w2c=w2c))
+    return views
+
+
+def scaled(view, n):
+    """-r N: the frame at (w // N, h // N), the intrinsics scaled by the same two ratios"""
+    w, h = view["width"] // n, view["height"] // n
+    sx, sy = w / view["width"], h / view["height"]
+    return dict(view, width=w, height=h, fx=view["fx"] * sx, fy=view["fy"] * sy, cx=view["cx"] * sx, cy=view["cy"] * sy)
+
+
+def _save_png(image, path):
+    from gs2m_render import _save
+    _save(image, path)
+
+
+def write_gif(frames, path, fps=FPS):
+    """(n, H, W, 4) uint8 numpy -> a looping GIF as vis_dtu.py's convert_gif makes it: pixels of alpha 0 are transparent, the
+    others opaque; one adaptive palette of 255 colours from the first frame, whose black entry (else entry 0) is the transparent
+    index; every frame replaces the one before (disposal 2)."""
+    from PIL import Image
+    rgb = [Image.fromarray(np.where(f[..., 3:] == 0, 0, f[..., :3]).astype(np.uint8), "RGB") for f in frames]
+    source = rgb[0].convert("P", palette=Image.ADAPTIVE, colors=255)
+    pal = source.getpalette()
+    black = [k for k in range(len(pal) // 3) if pal[3 * k:3 * k + 3] == [0, 0, 0]]
+    index = black[0] if black else 0
+    out = []
+    for im, f in zip(rgb, frames):
+        q = im.quantize(palette=source)
+        q.paste(index, mask=Image.fromarray(np.where(f[..., 3] == 0, 255, 0).astype(np.uint8), "L"))
+        out.append(q)
+    out[0].save(str(path), save_all=True, append_images=out[1:], optimize=True, duration=int(1000 / fps), loop=0, transparency=index, disposal=2)
+
+
+def write_webp(frames, path, fps=FPS):
+    """an animated WebP of the RGBA frames where the installed Pillow can write one -> whether it was written"""
+    from PIL import Image, features
+    if not features.check("webp"):
+        return False
+    ims = [Image.fromarray(f, "RGBA") for f in frames]
+    ims[0].save(str(path), save_all=True, append_images=ims[1:], format="WEBP", duration=int(1000 / fps), loop=0)
+    return True
+
+
+def view_files(a):
+    """The command line's work.  -> dict(out_dir, views: the PNGs written, still, frames, gif, webp)."""
+    import gs2m_mesh as M
+    dev = _dev(None)
+    mesh = M.read_mesh(a.ply_path)
+    v = torch.as_tensor(np.asarray(mesh.vertices, np.float64)).to(dev)
+    f = torch.as_tensor(np.asarray(mesh.triangles, np.int32)).to(dev)
+    col = None
+    if a.colour == "vertex":
+        if mesh.vertex_colors is None:
+            raise RuntimeError(f"{a.ply_path}: --colour vertex needs a mesh with vertex colours")
+        col = torch.as_tensor(np.asarray(mesh.vertex_colors, np.float32).reshape(-1, 3)).to(dev)
+    views = read_cameras_json(a.cameras) if a.cameras else read_colmap_views(a.source_path)
+    if not views:
+        raise RuntimeError("no camera to render from")
+    out_dir = a.out_dir or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(a.ply_path))), "visual")
+    os.makedirs(out_dir, exist_ok=True)
+    result = dict(out_dir=out_dir, views=[], still=None, frames=[], gif=None, webp=None)
+
+    def shade(w2c, k, H, W):
+        return shade_views(v, f, torch.as_tensor(np.ascontiguousarray(w2c)).to(dev), k["fx"], k["fy"], k["cx"], k["cy"], H, W, ss=a.ss,
+                           shading=a.shading, colors=col)
+
+    if a.rendering:
+        os.makedirs(os.path.join(out_dir, "views"), exist_ok=True)
+        chosen = [scaled(x, a.resolution) for x in (views if a.render_view_idx < 0 else [views[a.render_view_idx]])]
+        groups = {}
+        for x in chosen:  # one batched call per frame size and intrinsics
+            groups.setdefault((x["height"], x["width"], x["fx"], x["fy"], x["cx"], x["cy"]), []).append(x)
+        for (H, W, *_), members in groups.items():
+            images = shade(np.stack([x["w2c"] for x in members]), members[0], H, W)
+            for x, image in zip(members, images):
+                path = os.path.join(out_dir, "views", x["name"].split(".")[0] + ".png")
+                _save_png(image, path)
+                result["views"].append(path)
+    if a.still or a.animation:
+        # a 600 x 600 frame, the first view's focal lengths scaled to it as the frame of the first view is
+        first, ref = views[0], views[min(a.view_idx, len(views) - 1)]
+        k = dict(fx=first["fx"] * STILL_SIZE / first["width"], fy=first["fy"] * STILL_SIZE / first["height"], cx=0.5 * STILL_SIZE, cy=0.5 * STILL_SIZE)
+        T = np.eye(4)
+        T[:3, 3] = a.shift
+        if a.still:
+            result["still"] = os.path.join(out_dir, "still.png")
+            _save_png(shade((ref["w2c"] @ T)[None], k, STILL_SIZE, STILL_SIZE)[0], result["still"])
+        if a.animation:
+            os.makedirs(os.path.join(out_dir, "frames"), exist_ok=True)
+            images = shade(turntable(ref["w2c"], a.frames, a.shift), k, STILL_SIZE, STILL_SIZE)
+            for n, image in enumerate(images):
+                result["frames"].append(os.path.join(out_dir, "frames", f"{n:03d}.png"))
+                _save_png(image, result["frames"][-1])
+            host = images.cpu().numpy()
+            result["gif"] = os.path.join(out_dir, "anim.gif")
+            write_gif(host, result["gif"])
+            webp = os.path.join(out_dir, "anim.webp")
+            result["webp"] = webp if write_webp(host, webp) else None
+    return result
+
+
+def parser():
+    ap = argparse.ArgumentParser(description="Shaded views and turntable frames of a mesh (scripts/vis_dtu.py, scripts/vis_shiny.py)")
+    ap.add_argument("--ply-path", required=True, help="the mesh (binary PLY), e.g. MODEL/train/ours_30000/mesh/tsdf_post.ply")
+    src = ap.add_mutually_exclusive_group(required=True)
+    src.add_argument("--cameras", default="", help="MODEL/cameras.json")
+    src.add_argument("--source-path", "-s", default="", help="a COLMAP-format dataset")
+    ap.add_argument("--resolution", "-r", type=int, default=1, help="--rendering at (w // N, h // N)")
+    ap.add_argument("--rendering", action="store_true", help="views/<stem>.png from every camera")
+    ap.add_argument("--render_view_idx", type=int, default=-1, help="--rendering from this camera alone")
+    ap.add_argument("--still", action="store_true", help="still.png, 600 x 600, from the camera --view-idx")
+    ap.add_argument("--animation", action="store_true", help="frames/, anim.gif and anim.webp: the mesh rocking in front of --view-idx")
+    ap.add_argument("--view-idx", type=int, default=VIEW_IDX)
+    ap.add_argument("--frames", type=int, default=FRAMES, help=argparse.SUPPRESS)  # for the tests
+    ap.add_argument("--shift", type=float, nargs=3, default=(0.0, 0.0, 0.0), metavar=("X", "Y", "Z"), help="moves the mesh (still, animation)")
+    ap.add_argument("--shading", choices=("flat", "smooth"), default="flat")
+    ap.add_argument("--colour", choices=("grey", "vertex"), default="grey")
+    ap.add_argument("--ss", type=int, default=2, help="samples per pixel and axis, 1 .. 4")
+    ap.add_argument("--out-dir", default="", help="default: visual/ beside the mesh's directory")
+    return ap
+
+
+def main(argv=None):
+    a = parser().parse_args(argv)
+    r = view_files(a)
+    print(f"[>] {len(r['views'])} views, {'a still, ' if r['still'] else ''}{len(r['frames'])} frames -> {r['out_dir']}")
+    return r
+
+
+if __name__ == "__main__":
+    main()

@@ -207,6 +207,12 @@ SIGNATURES = {
     "gs2m_image_resize_workspace_bytes": (i, [i, i, i, i, i, p]),
     "gs2m_image_resize_u8": (i, [i, i, i, p, i, i, p, p, p, p, s]),
     "gs2m_image_unpack": (i, [i, i, i, p, p, p, p, p, p, s]),
+    # include/gs2m_meshview.h
+    "gs2m_meshview_workspace_bytes": (i, [ll, i, p]),
+    "gs2m_meshview_visibility": (i, [ll, p, ll, p, i, p, d, d, d, d, i, i, i, d, d, p, p, s]),
+    "gs2m_meshview_normals_workspace_bytes": (i, [p]),
+    "gs2m_meshview_normals": (i, [ll, p, ll, p, p, p, p, s]),
+    "gs2m_meshview_shade": (i, [ll, p, ll, p, i, p, d, d, d, d, i, i, i, p, p, p, d, d, d, d, d, i, p, p, p, s]),
 }
 del p, i, f, d, ll, ull, A, s
 EXPORTS = tuple(SIGNATURES)

@@ -50,7 +50,7 @@ def rasterize(v, f, w2c, depth, a):
     ws = workspace_for("gs2m_meshdepth_workspace_bytes", v.device, len(f), len(w2c))
     N.launch("gs2m_meshdepth_render", v.device, len(v), v.data_ptr(), len(f), f.data_ptr(), len(w2c), w2c.data_ptr(), K.TNT_FX, K.TNT_FY,
              K.TNT_CX, K.TNT_CY, a.width, a.height, K.NEAR, K.FAR, ws.data_ptr(), depth.data_ptr())
-    # the workspace's layout (csrc/mesh_depth.hip, carve_depth): the flag, then the views' two counters, each array padded to 256 bytes
+    # the workspace's layout (csrc/mesh_raster.h, carve_raster): the flag, then the views' two counters, each array padded to 256 bytes
     counts = ws[256:256 + 8 * len(w2c)].view(torch.int32).reshape(-1, 2).sum(0).tolist()
     return counts
 

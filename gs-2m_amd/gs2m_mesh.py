@@ -467,12 +467,14 @@ def read_mesh(file):
 
 # ---- command line: render.py --extract_mesh for a saved model ---------------------------------------------------------
 
-def render_views(gaussians, views, render_dir, device="cuda"):
+def render_views(gaussians, views, render_dir, device="cuda", png="host"):
     """Depth and the SH colour of every view with this repository's render(); the colours are saved as render_dir/<stem>.png
-    as render.py saves them (torchvision.utils.save_image rounding).  -> (N, H, W) depths on the device."""
-    from PIL import Image
+    as render.py saves them (torchvision.utils.save_image rounding; `png`: "host" through Pillow, "device" through gs2m_png).
+    -> (N, H, W) depths on the device."""
     from gaussian_renderer import render
     from gs2m_scene import PipelineParams
+    from gs2m_png import Writer
+    writer = Writer(png)
     os.makedirs(render_dir, exist_ok=True)
     bg = torch.zeros(3, device=device)
     depths = []
@@ -482,8 +484,9 @@ def render_views(gaussians, views, render_dir, device="cuda"):
                 view.image_name = f"{k:05d}.png"
             out = render(view, gaussians, PipelineParams(), bg, material_stage=True)  # as render.py: the depth map needs the G-buffer
             depths.append(out["depth_map"].squeeze(0).float().clone())
-            img = out["render"].clamp(0.0, 1.0).mul(255).add_(0.5).clamp_(0, 255).permute(1, 2, 0).to(torch.uint8).cpu().numpy()
-            Image.fromarray(img).save(os.path.join(render_dir, view.image_name.rsplit(".", 1)[0] + ".png"))
+            img = out["render"].clamp(0.0, 1.0).mul(255).add_(0.5).clamp_(0, 255).permute(1, 2, 0).to(torch.uint8).contiguous()
+            writer.put(img, os.path.join(render_dir, view.image_name.rsplit(".", 1)[0] + ".png"))
+            writer.flush()
     return torch.stack(depths)
 
 

@@ -169,11 +169,6 @@ def scaled(view, n):
     return dict(view, width=w, height=h, fx=view["fx"] * sx, fy=view["fy"] * sy, cx=view["cx"] * sx, cy=view["cy"] * sy)
 
 
-def _save_png(image, path):
-    from gs2m_render import _save
-    _save(image, path)
-
-
 def write_gif(frames, path, fps=FPS):
     """(n, H, W, 4) uint8 numpy -> a looping GIF as vis_dtu.py's convert_gif makes it: pixels of alpha 0 are transparent, the
     others opaque; one adaptive palette of 255 colours from the first frame, whose black entry (else entry 0) is the transparent
@@ -220,6 +215,8 @@ def view_files(a):
     out_dir = a.out_dir or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(a.ply_path))), "visual")
     os.makedirs(out_dir, exist_ok=True)
     result = dict(out_dir=out_dir, views=[], still=None, frames=[], gif=None, webp=None)
+    from gs2m_png import Writer
+    writer = Writer("device" if getattr(a, "device_png", False) else "host")  # the PNGs; the GIF and the WebP stay on Pillow
 
     def shade(w2c, k, H, W):
         return shade_views(v, f, torch.as_tensor(np.ascontiguousarray(w2c)).to(dev), k["fx"], k["fy"], k["cx"], k["cy"], H, W, ss=a.ss,
@@ -235,8 +232,9 @@ def view_files(a):
             images = shade(np.stack([x["w2c"] for x in members]), members[0], H, W)
             for x, image in zip(members, images):
                 path = os.path.join(out_dir, "views", x["name"].split(".")[0] + ".png")
-                _save_png(image, path)
+                writer.put(image, path)
                 result["views"].append(path)
+            writer.flush()
     if a.still or a.animation:
         # a 600 x 600 frame, the first view's focal lengths scaled to it as the frame of the first view is
         first, ref = views[0], views[min(a.view_idx, len(views) - 1)]
@@ -245,13 +243,15 @@ def view_files(a):
         T[:3, 3] = a.shift
         if a.still:
             result["still"] = os.path.join(out_dir, "still.png")
-            _save_png(shade((ref["w2c"] @ T)[None], k, STILL_SIZE, STILL_SIZE)[0], result["still"])
+            writer.put(shade((ref["w2c"] @ T)[None], k, STILL_SIZE, STILL_SIZE)[0], result["still"])
+            writer.flush()
         if a.animation:
             os.makedirs(os.path.join(out_dir, "frames"), exist_ok=True)
             images = shade(turntable(ref["w2c"], a.frames, a.shift), k, STILL_SIZE, STILL_SIZE)
             for n, image in enumerate(images):
                 result["frames"].append(os.path.join(out_dir, "frames", f"{n:03d}.png"))
-                _save_png(image, result["frames"][-1])
+                writer.put(image, result["frames"][-1])
+            writer.flush()
             host = images.cpu().numpy()
             result["gif"] = os.path.join(out_dir, "anim.gif")
             write_gif(host, result["gif"])
@@ -278,6 +278,8 @@ def parser():
     ap.add_argument("--colour", choices=("grey", "vertex"), default="grey")
     ap.add_argument("--ss", type=int, default=2, help="samples per pixel and axis, 1 .. 4")
     ap.add_argument("--out-dir", default="", help="default: visual/ beside the mesh's directory")
+    from gs2m_png import add_png_argument
+    add_png_argument(ap)
     return ap
 
 

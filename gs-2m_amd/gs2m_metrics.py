@@ -169,15 +169,16 @@ def quantise(image):
     return image.clamp(0.0, 1.0).mul(255).add_(0.5).clamp_(0, 255).permute(1, 2, 0).to(torch.uint8).contiguous()
 
 
-def score_views(gaussians, views, background, out_dir=None, white_background=False):
+def score_views(gaussians, views, background, out_dir=None, white_background=False, png="host"):
     """Renders every view with this repository's render() and scores the 8-bit colour against the view's 8-bit ground truth
     (`view.gt_image`, (3+, H, W) float; render.py:77-79: clamped, `background` where `view.alpha_mask` <= 0.5 when
     `white_background`) on the device.  `out_dir`: also write out_dir/render/<stem>.png and out_dir/gt/<stem>.png, render.py's
-    layout.  -> {"names", "psnr", "ssim"}: the stems and two float64 host tensors, one value per view."""
+    layout (`png`: "host" through Pillow, "device" through gs2m_png).  -> {"names", "psnr", "ssim"}: the stems and two float64 host tensors, one value per view."""
     from gaussian_renderer import render
     from gs2m_scene import PipelineParams
+    from gs2m_png import Writer
+    writer = Writer(png)
     if out_dir is not None:
-        from PIL import Image
         for sub in ("render", "gt"):
             os.makedirs(os.path.join(out_dir, sub), exist_ok=True)
     names, sse, sums, counts = [], [], [], []
@@ -197,8 +198,9 @@ def score_views(gaussians, views, background, out_dir=None, white_background=Fal
             e, s = image_sums(img[None], gt[None])
             names.append(stem); sse.append(e); sums.append(s); counts.append(img.numel())
             if out_dir is not None:
-                Image.fromarray(img.cpu().numpy()).save(os.path.join(out_dir, "render", stem + ".png"))
-                Image.fromarray(gt.cpu().numpy()).save(os.path.join(out_dir, "gt", stem + ".png"))
+                writer.put(img, os.path.join(out_dir, "render", stem + ".png"))
+                writer.put(gt, os.path.join(out_dir, "gt", stem + ".png"))
+                writer.flush()
     if not names:
         return {"names": [], "psnr": torch.empty(0, dtype=torch.float64), "ssim": torch.empty(0, dtype=torch.float64)}
     counts = torch.tensor(counts, dtype=torch.float64)

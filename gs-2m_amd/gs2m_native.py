@@ -213,6 +213,10 @@ SIGNATURES = {
     "gs2m_meshview_normals_workspace_bytes": (i, [p]),
     "gs2m_meshview_normals": (i, [ll, p, ll, p, p, p, p, s]),
     "gs2m_meshview_shade": (i, [ll, p, ll, p, i, p, d, d, d, d, i, i, i, p, p, p, d, d, d, d, d, i, p, p, p, s]),
+    # include/gs2m_png.h
+    "gs2m_png_plan": (i, [i, i, i, i, p, p, p, p]),
+    "gs2m_png_filter": (i, [i, i, i, i, p, p, s]),
+    "gs2m_png_encode": (i, [i, i, i, i, p, p, ll, p, ll, p, s]),
 }
 del p, i, f, d, ll, ull, A, s
 EXPORTS = tuple(SIGNATURES)

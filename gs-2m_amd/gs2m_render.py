@@ -157,11 +157,6 @@ def pack_image(src, layout="chw", quant="round", alpha=None, mask=None, backgrou
 
 # ---- render.py:35-151 -------------------------------------------------------------------------------------------------------
 
-def _save(array, path):
-    from PIL import Image
-    Image.fromarray(array.cpu().numpy()).save(path)  # (H, W, 3) -> RGB, (H, W, 4) -> RGBA
-
-
 def update_points(point_file, key, count):
     """render.py:59-67: the JSON object at `point_file` with `key` set to the number of Gaussians."""
     points = {}
@@ -175,7 +170,7 @@ def update_points(point_file, key, count):
 
 
 def render_views_to_disk(gaussians, views, out_dir, background, white_background=False, normal_world=False, normal_sobel=False,
-                         light=None, metallic=False, gamma=False, mask_gt=False, points_file=None):
+                         light=None, metallic=False, gamma=False, mask_gt=False, points_file=None, png="host"):
     """render.py:35-151 for one split: renders every view with this repository's render() and writes
 
         out_dir/{render, gt, normal, depth}/<stem>.png
@@ -189,10 +184,14 @@ def render_views_to_disk(gaussians, views, out_dir, background, white_background
     save_depth_map.  `normal_sobel`: the normal image shows the normals estimated from depth; `gamma`: diffuse and specular go
     through linear_to_srgb.  `points_file` (default: points.json two levels above out_dir, i.e. in the model directory) gets
     the number of Gaussians under out_dir's name.  `view.image_name` gives the stem (default: the view's index, five digits).
+    `png`: "host" writes the files through Pillow; "device" encodes them with gs2m_png, a view's RGB images in one call and its
+    RGBA images in another (the same pixels, not the same file bytes).
     -> (N, H, W) float32 depths on the device, what `gs2m_mesh.fuse_depths` takes."""
     import torch.nn.functional as F
     from gaussian_renderer import render
     from gs2m_scene import PipelineParams
+    from gs2m_png import Writer
+    writer = Writer(png)
     out_dir = str(out_dir)
     subs = ["render", "gt", "normal", "depth"] + (["albedo", "roughness", "metallic", "diffuse", "specular"] if light is not None else [])
     for sub in subs:
@@ -206,7 +205,8 @@ def render_views_to_disk(gaussians, views, out_dir, background, white_background
         if light is not None:
             from pbr import pbr_render
             light.cubemap.build_mips()
-            _save(pack_image(light.cubemap.export_envmap(return_img=True).contiguous(), "hwc"), os.path.join(out_dir, "envmap.png"))
+            writer.put(pack_image(light.cubemap.export_envmap(return_img=True).contiguous(), "hwc"), os.path.join(out_dir, "envmap.png"))
+            writer.flush()
         for k, view in enumerate(views):
             if getattr(view, "image_name", None) is None:
                 view.image_name = f"{k:05d}.png"
@@ -223,7 +223,7 @@ def render_views_to_disk(gaussians, views, out_dir, background, white_background
                          blend_metallic=metallic)
 
             def put(sub, image):
-                _save(image, os.path.join(out_dir, sub, stem + ".png"))
+                writer.put(image, os.path.join(out_dir, sub, stem + ".png"))
 
             def put_map(sub, src, layout="chw", **kw):  # render.py:140-151
                 put(sub, pack_image(src, layout, quant, alpha=alpha if white_background else None, **kw))
@@ -237,6 +237,7 @@ def render_views_to_disk(gaussians, views, out_dir, background, white_background
             depths.append(depth.clone())
             if light is None:
                 put("render", pack_image(pkg["render"].contiguous()))
+                writer.flush()
                 continue
             rays = getattr(view, "_render_rays", None)
             if rays is None:
@@ -255,6 +256,7 @@ def render_views_to_disk(gaussians, views, out_dir, background, white_background
             put_map("metallic", pbr["metallic_map"].reshape(1, h, w).contiguous())
             put_map("diffuse", pbr["diffuse_rgb"].reshape(h, w, 3).contiguous(), "hwc", srgb=gamma)
             put_map("specular", pbr["specular_rgb"].reshape(h, w, 3).contiguous(), "hwc", srgb=gamma)
+            writer.flush()
     if not depths:
         return torch.empty((0, 0, 0), dtype=torch.float32, device=background.device)
     return torch.stack(depths)
@@ -296,6 +298,8 @@ def parse_args(argv=None):
     ap.add_argument("--normal_sobel", action="store_true", help="Use normal estimated from depths")
     from gs2m_ingest import add_ingest_arguments
     add_ingest_arguments(ap)  # COLMAP datasets: the views' alpha masks from --masks or the images' alpha channel
+    from gs2m_png import add_png_argument
+    add_png_argument(ap)
     a = ap.parse_args(argv)
     if a.dtu + a.tnt + a.blender > 1:
         ap.error("--dtu, --tnt and --blender are presets: choose one")
@@ -338,7 +342,7 @@ def render_split(a, split, model, cams, gts, extent, background, bounds=None):
             cam.image_name = f"{k:05d}.png"
     out_dir = os.path.join(a.model_path, split, f"{a.label}_{a.iteration}")
     depths = render_views_to_disk(model, cams, out_dir, background, a.white_background, a.normal_world, a.normal_sobel,
-                                  points_file=os.path.join(a.model_path, "points.json"))
+                                  points_file=os.path.join(a.model_path, "points.json"), png="device" if a.device_png else "host")
     print(f"[>] {len(cams)} views -> {out_dir}")
     if not a.extract_mesh:
         return

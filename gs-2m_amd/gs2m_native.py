@@ -217,6 +217,15 @@ SIGNATURES = {
     "gs2m_png_plan": (i, [i, i, i, i, p, p, p, p]),
     "gs2m_png_filter": (i, [i, i, i, i, p, p, s]),
     "gs2m_png_encode": (i, [i, i, i, i, p, p, ll, p, ll, p, s]),
+    # include/gs2m_lpips.h
+    "gs2m_lpips_pack_conv": (i, [i, i, p, p, p, s]),
+    "gs2m_lpips_pack_weights": (i, [p, p, p, p, s]),
+    "gs2m_lpips_workspace_bytes": (i, [i, i, i, p]),
+    "gs2m_lpips": (i, [i, i, i, p, p, p, p, ll, p, p, s]),
+    "gs2m_lpips_conv3x3": (i, [i, i, i, i, i, p, p, p, s]),
+    "gs2m_lpips_maxpool2x2": (i, [i, i, i, i, p, p, s]),
+    "gs2m_lpips_tap_workspace_bytes": (i, [i, i, i, p]),
+    "gs2m_lpips_tap_distance": (i, [i, i, i, i, p, p, p, p, ll, p, s]),
 }
 del p, i, f, d, ll, ull, A, s
 EXPORTS = tuple(SIGNATURES)

@@ -226,6 +226,11 @@ SIGNATURES = {
     "gs2m_lpips_maxpool2x2": (i, [i, i, i, i, p, p, s]),
     "gs2m_lpips_tap_workspace_bytes": (i, [i, i, i, p]),
     "gs2m_lpips_tap_distance": (i, [i, i, i, i, p, p, p, p, ll, p, s]),
+    # include/gs2m_envmap.h
+    "gs2m_hdr_scan": (i, [p, ll, i, i, p]),
+    "gs2m_hdr_decode": (i, [p, ll, i, i, p, p, s]),
+    "gs2m_hdr_encode": (i, [i, i, p, p, s]),
+    "gs2m_latlong_to_cubemap": (i, [i, i, p, i, i, f, f, p, s]),
 }
 del p, i, f, d, ll, ull, A, s
 EXPORTS = tuple(SIGNATURES)

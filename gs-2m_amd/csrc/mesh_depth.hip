@@ -7,6 +7,7 @@
 #include <math.h>
 #include "eval_common.h"
 #include "mesh_raster.h"
+#include "vertex_project.h"
 #include "../../include/gs2m_visibility.h"
 
 using namespace mesh_raster;
@@ -28,22 +29,12 @@ __global__ void __launch_bounds__(256) votes_kernel(long long n, const double* _
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const double p[3] = {verts[3 * i], verts[3 * i + 1], verts[3 * i + 2]};
-    const double w1 = (double)(q.W - 1), h1 = (double)(q.H - 1);
     int count = 0;
     for (int v = 0; v < n_views; v++) {
-        double c[3];
-        to_camera(w2c + 16 * (size_t)v, p, c);
-        const double z = c[2] + 1e-8;
-        const double x = (q.fx * c[0] + q.cx * c[2]) / z, y = (q.fy * c[1] + q.cy * c[2]) / z;
-        if (!(x >= 0.0 && x <= w1 && y >= 0.0 && y <= h1 && z > 0.0)) continue;  // NaN fails
-        const int x0 = (int)floor(x), y0 = (int)floor(y);  // within the frame
-        const double tx = x - (double)x0, ty = y - (double)y0;
-        const float* D = depth + (size_t)v * q.W * q.H + (size_t)y0 * q.W + x0;
-        const bool right = x0 + 1 < q.W, below = y0 + 1 < q.H;
-        const double d00 = (double)D[0], d01 = right ? (double)D[1] : 0.0;
-        const double d10 = below ? (double)D[q.W] : 0.0, d11 = right && below ? (double)D[q.W + 1] : 0.0;
-        const double d = ((d00 * ((1.0 - tx) * (1.0 - ty)) + d01 * (tx * (1.0 - ty))) + d10 * ((1.0 - tx) * ty)) + d11 * (tx * ty);
-        count += d > 0.0 ? (z < d + eps ? 1 : 0) : 1;
+        VertexTaps t;
+        if (!project_vertex(w2c + 16 * (size_t)v, p, q, t)) continue;
+        const double d = bilinear_taps(depth + (size_t)v * q.W * q.H, q.W, t);
+        count += in_front(t.z, d, eps) ? 1 : 0;
     }
     votes[i] = (accumulate ? votes[i] : 0) + count;
 }

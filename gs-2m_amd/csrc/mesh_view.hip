@@ -9,6 +9,9 @@
 // indices and vertices (84 bytes; neighbours mostly share the triangle, so the loads hit the cache), recomputes the barycentrics
 // at the sample's ray, shades, and at the end writes the four bytes.  Keys are not trusted: a triangle index or a vertex index
 // out of range makes the sample empty.  All fp64, as written.
+// G-buffer: a thread per sample runs the same per-sample code as the shade (sample_surface) and writes the world-space
+// normal and view direction and the interpolated vertex attributes, rounded once to fp32, for a shading done elsewhere; Resolve RGB:
+// a thread per output pixel applies the Resolve paragraph to such shaded samples.
 #include <math.h>
 #include "eval_common.h"
 #include "mesh_raster.h"
@@ -70,6 +73,53 @@ __device__ __forceinline__ double encode(double x, int srgb) {
     return x <= 0.0031308 ? 12.92 * x : 1.055 * pow(x, 1.0 / 2.4) - 0.055;
 }
 
+// The Shade paragraph up to the normal, for sample (i, j) of the sample frame q with key `key`: the triangle's vertex indices, the
+// sample's ray, the barycentrics and N in camera space (smooth where `normals` is given and usable, else flat).  false: the
+// sample is empty, or its key names a triangle or a vertex out of range.
+__device__ __forceinline__ bool sample_surface(long long nv, const double* __restrict__ verts, long long nt, const int* __restrict__ tris,
+                                               const double* __restrict__ M, const Frame& q, const double* __restrict__ normals, u64 key,
+                                               int i, int j, int* id, double* r, double* l, double* N) {
+    if (key == EMPTY_KEY) return false;
+    const long long t = (long long)(key & 0xFFFFFFFFull);
+    if (t >= nt) return false;
+    id[0] = tris[3 * t], id[1] = tris[3 * t + 1], id[2] = tris[3 * t + 2];
+    if (id[0] < 0 || id[1] < 0 || id[2] < 0 || id[0] >= nv || id[1] >= nv || id[2] >= nv) return false;
+    double P[9], a[3], b[3], c[3], x[3];
+    load_triangle(verts, tris, t, P);
+    to_camera(M, P, a);
+    to_camera(M, P + 3, b);
+    to_camera(M, P + 6, c);
+    pixel_ray(q, i, j, r);
+    cross3(b, c, x);
+    const double e0 = dot3(x, r);
+    cross3(c, a, x);
+    const double e1 = dot3(x, r);
+    cross3(a, b, x);
+    const double e2 = dot3(x, r);
+    const double s = (e0 + e1) + e2;
+    l[0] = e0 / s, l[1] = e1 / s, l[2] = e2 / s;
+    const double ab[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, ac[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
+    cross3(ab, ac, N);
+    if (normals) {
+        double S[3];
+        bool ok = true;
+        double C3[3][3];
+#pragma unroll
+        for (int w = 0; w < 3; w++) {
+            const double* nw = normals + 3 * (size_t)id[w];
+            const double n0 = nw[0], n1 = nw[1], n2 = nw[2];
+            ok = ok && !(n0 == 0.0 && n1 == 0.0 && n2 == 0.0);
+#pragma unroll
+            for (int d = 0; d < 3; d++) C3[w][d] = (M[4 * d] * n0 + M[4 * d + 1] * n1) + M[4 * d + 2] * n2;
+        }
+#pragma unroll
+        for (int d = 0; d < 3; d++) S[d] = (l[0] * C3[0][d] + l[1] * C3[1][d]) + l[2] * C3[2][d];
+        ok = ok && isfinite(S[0]) && isfinite(S[1]) && isfinite(S[2]) && !(S[0] == 0.0 && S[1] == 0.0 && S[2] == 0.0);
+        if (ok) N[0] = S[0], N[1] = S[1], N[2] = S[2];
+    }
+    return true;
+}
+
 // q: the SAMPLE frame; W, H: the output frame
 __global__ void __launch_bounds__(256) shade_kernel(long long nv, const double* __restrict__ verts, long long nt,
                                                     const int* __restrict__ tris, const double* __restrict__ w2c, Frame q, int W, int H,
@@ -89,48 +139,10 @@ __global__ void __launch_bounds__(256) shade_kernel(long long nv, const double* 
     for (int k = 0; k < ss * ss; k++) {
         const int i = px * ss + k % ss, j = py * ss + k / ss;
         const u64 key = keys[(size_t)j * q.W + i];
-        if (key == EMPTY_KEY) continue;
-        const long long t = (long long)(key & 0xFFFFFFFFull);
-        if (t >= nt) continue;
-        const int id[3] = {tris[3 * t], tris[3 * t + 1], tris[3 * t + 2]};
-        if (id[0] < 0 || id[1] < 0 || id[2] < 0 || id[0] >= nv || id[1] >= nv || id[2] >= nv) continue;
-        double P[9], a[3], b[3], c[3], r[3], x[3];
-        load_triangle(verts, tris, t, P);
-        to_camera(M, P, a);
-        to_camera(M, P + 3, b);
-        to_camera(M, P + 6, c);
-        pixel_ray(q, i, j, r);
-        cross3(b, c, x);
-        const double e0 = dot3(x, r);
-        cross3(c, a, x);
-        const double e1 = dot3(x, r);
-        cross3(a, b, x);
-        const double e2 = dot3(x, r);
-        const double s = (e0 + e1) + e2;
-        const double l0 = e0 / s, l1 = e1 / s, l2 = e2 / s;
-        const double ab[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, ac[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
-        double N[3];
-        cross3(ab, ac, N);
-        if (sh.normals) {
-            double S[3];
-            bool ok = true;
-#pragma unroll
-            for (int w = 0; w < 3; w++) S[w] = 0.0;
-            const double l[3] = {l0, l1, l2};
-            double C3[3][3];
-#pragma unroll
-            for (int w = 0; w < 3; w++) {
-                const double* nw = sh.normals + 3 * (size_t)id[w];
-                const double n0 = nw[0], n1 = nw[1], n2 = nw[2];
-                ok = ok && !(n0 == 0.0 && n1 == 0.0 && n2 == 0.0);
-#pragma unroll
-                for (int d = 0; d < 3; d++) C3[w][d] = (M[4 * d] * n0 + M[4 * d + 1] * n1) + M[4 * d + 2] * n2;
-            }
-#pragma unroll
-            for (int d = 0; d < 3; d++) S[d] = (l[0] * C3[0][d] + l[1] * C3[1][d]) + l[2] * C3[2][d];
-            ok = ok && isfinite(S[0]) && isfinite(S[1]) && isfinite(S[2]) && !(S[0] == 0.0 && S[1] == 0.0 && S[2] == 0.0);
-            if (ok) N[0] = S[0], N[1] = S[1], N[2] = S[2];
-        }
+        int id[3];
+        double r[3], l[3], N[3];
+        if (!sample_surface(nv, verts, nt, tris, M, q, sh.normals, key, i, j, id, r, l, N)) continue;
+        const double l0 = l[0], l1 = l[1], l2 = l[2];
         const double cosv = fabs(dot3(N, r)) / sqrt(dot3(N, N) * dot3(r, r));
         const double light = sh.ambient + sh.diffuse * cosv;
 #pragma unroll
@@ -142,7 +154,7 @@ __global__ void __launch_bounds__(256) shade_kernel(long long nv, const double* 
             sum[d] = sum[d] + fmin(fmax(alb * light, 0.0), 1.0);
         }
         m++;
-        if (k == (ss / 2) * (ss + 1)) zc = __uint_as_float((unsigned)(key >> 32)), tc = (int)t;
+        if (k == (ss / 2) * (ss + 1)) zc = __uint_as_float((unsigned)(key >> 32)), tc = (int)(key & 0xFFFFFFFFull);
     }
     const size_t o = (size_t)v * W * H + (size_t)pix;
     uchar4 out = make_uchar4(0, 0, 0, 0);
@@ -155,6 +167,101 @@ __global__ void __launch_bounds__(256) shade_kernel(long long nv, const double* 
     reinterpret_cast<uchar4*>(rgba)[o] = out;
     if (depth) depth[o] = zc;
     if (tri_id) tri_id[o] = tc;
+}
+
+// ---- G-buffer and resolve of shaded samples ----
+
+struct GBuffer {
+    float *normal, *view_dir, *albedo, *roughness, *metallic;
+    unsigned char* coverage;
+};
+
+// through the transposed rotation rows of the view: camera space to world space
+__device__ __forceinline__ void to_world_dir(const double* __restrict__ M, const double* c, double* o) {
+#pragma unroll
+    for (int k = 0; k < 3; k++) o[k] = (M[k] * c[0] + M[4 + k] * c[1]) + M[8 + k] * c[2];
+}
+
+// a thread per sample of the SAMPLE frame q; every output of an empty sample is 0
+__global__ void __launch_bounds__(256) gbuffer_kernel(long long nv, const double* __restrict__ verts, long long nt,
+                                                      const int* __restrict__ tris, const double* __restrict__ w2c, Frame q,
+                                                      const u64* __restrict__ vis, const double* __restrict__ normals,
+                                                      const float* __restrict__ albedo, const float* __restrict__ roughness,
+                                                      const float* __restrict__ metallic, GBuffer g) {
+    const int v = blockIdx.y;
+    const long long pix = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long frame = (long long)q.W * q.H;
+    if (pix >= frame) return;
+    const int i = (int)(pix % q.W), j = (int)(pix / q.W);
+    const double* M = w2c + 16 * (size_t)v;
+    const size_t o = (size_t)v * frame + (size_t)pix;
+    int id[3];
+    double r[3], l[3], N[3];
+    float out[11];
+#pragma unroll
+    for (int k = 0; k < 11; k++) out[k] = 0.f;
+    const bool hit = sample_surface(nv, verts, nt, tris, M, q, normals, vis[o], i, j, id, r, l, N);
+    if (hit) {
+        double Nw[3], Vw[3];
+        const double back[3] = {-r[0], -r[1], -r[2]};
+        if (dot3(N, r) > 0.0) N[0] = -N[0], N[1] = -N[1], N[2] = -N[2];  // towards the eye
+        to_world_dir(M, N, Nw);
+        to_world_dir(M, back, Vw);
+        const double nl = sqrt(dot3(Nw, Nw)), vl = sqrt(dot3(Vw, Vw));
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            out[k] = (float)(Nw[k] / nl);
+            out[3 + k] = (float)(Vw[k] / vl);
+            out[6 + k] = (float)((l[0] * (double)albedo[3 * (size_t)id[0] + k] + l[1] * (double)albedo[3 * (size_t)id[1] + k]) +
+                                 l[2] * (double)albedo[3 * (size_t)id[2] + k]);
+        }
+        out[9] = (float)((l[0] * (double)roughness[id[0]] + l[1] * (double)roughness[id[1]]) + l[2] * (double)roughness[id[2]]);
+        out[10] = (float)((l[0] * (double)metallic[id[0]] + l[1] * (double)metallic[id[1]]) + l[2] * (double)metallic[id[2]]);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; k++) g.normal[3 * o + k] = out[k], g.view_dir[3 * o + k] = out[3 + k], g.albedo[3 * o + k] = out[6 + k];
+    g.roughness[o] = out[9];
+    g.metallic[o] = out[10];
+    g.coverage[o] = hit ? 1 : 0;
+}
+
+// a thread per output pixel: the Resolve paragraph on per-sample linear RGB
+__global__ void __launch_bounds__(256) resolve_rgb_kernel(int W, int H, int ss, const float* __restrict__ rgb,
+                                                          const unsigned char* __restrict__ coverage, int srgb,
+                                                          const float* __restrict__ background, unsigned char* __restrict__ rgba) {
+    const int v = blockIdx.y;
+    const long long pix = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (pix >= (long long)W * H) return;
+    const int px = (int)(pix % W), py = (int)(pix / W);
+    const int Ws = W * ss;
+    const size_t base = (size_t)v * Ws * ((size_t)H * ss);
+    double sum[3] = {0.0, 0.0, 0.0};
+    int m = 0;
+    for (int k = 0; k < ss * ss; k++) {
+        const size_t s = base + (size_t)(py * ss + k / ss) * Ws + (px * ss + k % ss);
+        if (!coverage[s]) continue;
+#pragma unroll
+        for (int d = 0; d < 3; d++) sum[d] = sum[d] + fmin(fmax((double)rgb[3 * s + d], 0.0), 1.0);
+        m++;
+    }
+    const size_t o = (size_t)v * W * H + (size_t)pix;
+    double enc[3] = {0.0, 0.0, 0.0};
+    if (m > 0) {
+#pragma unroll
+        for (int d = 0; d < 3; d++) enc[d] = encode(sum[d] / (double)m, srgb);
+    }
+    const double a = (double)m / (double)(ss * ss);
+    uchar4 out = make_uchar4(0, 0, 0, 0);
+    if (background) {
+        unsigned char by[3];
+#pragma unroll
+        for (int d = 0; d < 3; d++) by[d] = (unsigned char)floor(255.0 * (a * enc[d] + (1.0 - a) * fmin(fmax((double)background[3 * o + d], 0.0), 1.0)) + 0.5);
+        out = make_uchar4(by[0], by[1], by[2], 255);
+    } else if (m > 0) {
+        out = make_uchar4((unsigned char)floor(255.0 * enc[0] + 0.5), (unsigned char)floor(255.0 * enc[1] + 0.5),
+                          (unsigned char)floor(255.0 * enc[2] + 0.5), (unsigned char)floor(255.0 * a + 0.5));
+    }
+    reinterpret_cast<uchar4*>(rgba)[o] = out;
 }
 
 bool view_frame_ok(int n_views, int W, int H, int ss, double fx, double fy, double cx, double cy) {
@@ -226,6 +333,34 @@ int gs2m_meshview_shade(long long n_verts, const double* verts, long long n_tris
     const Shade sh{normals, colors, {base_r, base_g, base_b}, ambient, diffuse, srgb ? 1 : 0, ss};
     shade_kernel<<<dim3(blocks_of((long long)W * H), (unsigned)n_views), 256, 0, (hipStream_t)stream>>>(
         n_verts, verts, n_tris, tris, w2c, q, W, H, (const u64*)vis, sh, rgba, depth, tri_id);
+    return gs2m_status(hipGetLastError());
+}
+
+int gs2m_meshview_gbuffer(long long n_verts, const double* verts, long long n_tris, const int* tris, int n_views, const double* w2c,
+                          double fx, double fy, double cx, double cy, int W, int H, int ss, const unsigned long long* vis,
+                          const double* normals, const float* albedo, const float* roughness, const float* metallic,
+                          float* out_normal, float* out_view_dir, float* out_albedo, float* out_roughness, float* out_metallic,
+                          unsigned char* coverage, void* stream) {
+    if (n_verts < 0 || n_tris < 0 || !view_frame_ok(n_views, W, H, ss, fx, fy, cx, cy)) return GS2M_ERR_INVALID_ARG;
+    if (n_views > 0 && (!w2c || !vis || !out_normal || !out_view_dir || !out_albedo || !out_roughness || !out_metallic || !coverage))
+        return GS2M_ERR_INVALID_ARG;
+    if (n_tris > 0 && (!tris || (n_verts > 0 && (!verts || !albedo || !roughness || !metallic)))) return GS2M_ERR_INVALID_ARG;
+    if (n_tris > 0x7FFFFFFFll || n_verts > 0x7FFFFFFFll) return GS2M_ERR_UNSUPPORTED;
+    if (n_views == 0) return GS2M_OK;
+    const Frame q{ss * fx, ss * fy, ss * cx, ss * cy, 0.0, 0.0, W * ss, H * ss};
+    const GBuffer g{out_normal, out_view_dir, out_albedo, out_roughness, out_metallic, coverage};
+    gbuffer_kernel<<<dim3(blocks_of((long long)q.W * q.H), (unsigned)n_views), 256, 0, (hipStream_t)stream>>>(
+        n_verts, verts, n_tris, tris, w2c, q, (const u64*)vis, normals, albedo, roughness, metallic, g);
+    return gs2m_status(hipGetLastError());
+}
+
+int gs2m_meshview_resolve_rgb(int n_views, int W, int H, int ss, const float* rgb, const unsigned char* coverage, int srgb,
+                              const float* background, unsigned char* rgba, void* stream) {
+    if (!view_frame_ok(n_views, W, H, ss, 1.0, 1.0, 0.0, 0.0)) return GS2M_ERR_INVALID_ARG;
+    if (n_views > 0 && (!rgb || !coverage || !rgba)) return GS2M_ERR_INVALID_ARG;
+    if (n_views == 0) return GS2M_OK;
+    resolve_rgb_kernel<<<dim3(blocks_of((long long)W * H), (unsigned)n_views), 256, 0, (hipStream_t)stream>>>(
+        W, H, ss, rgb, coverage, srgb ? 1 : 0, background, rgba);
     return gs2m_status(hipGetLastError());
 }
 

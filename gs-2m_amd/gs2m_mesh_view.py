@@ -7,6 +7,8 @@ encoded as straight-alpha sRGB bytes.  Everything is fp64 on device tensors owne
 
     python gs-2m_amd/gs2m_mesh_view.py --ply-path M.ply --cameras MODEL/cameras.json --rendering --still --animation
     python gs-2m_amd/gs2m_mesh_view.py --ply-path M.ply -s SCENE -r 2 --rendering --shading smooth --colour vertex
+    python gs-2m_amd/gs2m_mesh_view.py --ply-path MATERIAL.ply -s SCENE --rendering --colour pbr --envmap studio.hdr [--background env]
+(the last: a material mesh of gs2m_mesh_bake.py under an environment map)
 write views/<stem>.png, still.png, frames/000.png .. 119.png, anim.gif and anim.webp under --out-dir (default: visual/ beside the
 mesh's directory).
 """
@@ -110,6 +112,102 @@ def shade_views(vertices, triangles, w2c, fx, fy, cx, cy, H, W, ss=2, shading="f
                  1 if srgb else 0, _ptr(rgba[k:k + batch]), None if depth is None else _ptr(depth[k:k + batch]),
                  None if tri_id is None else _ptr(tri_id[k:k + batch]))
     return (rgba, depth, tri_id) if return_aux else rgba
+
+
+def mesh_gbuffer(vertices, triangles, w2c, fx, fy, cx, cy, H, W, vis, albedo, roughness, metallic, ss=1, normals=None):
+    """The G-buffer of the samples of `vis` (visibility_buffer of the same mesh, views, frame and ss): dict(normal, view_dir,
+    albedo: (n, H ss, W ss, 3) float32; roughness, metallic: (n, H ss, W ss, 1) float32; coverage: (n, H ss, W ss) uint8), on the
+    device.  normal and view_dir (surface to eye) are unit vectors in world space, the normal facing the eye; albedo (V, 3),
+    roughness (V,) and metallic (V,) are float32 vertex arrays interpolated by the sample's barycentrics.  normals: (V, 3) fp64
+    vertex normals for smooth shading, None for flat.  An empty sample is 0 throughout."""
+    who = "mesh_gbuffer"
+    v, f, m = _mesh_args(vertices, triangles, w2c, who)
+    H, W, ss = _check_frame(H, W, ss, who)
+    dev, n = v.device, len(m)
+    a = _on_device(albedo, "albedo", who, torch.float32, (3,))
+    r = _on_device(roughness, "roughness", who, torch.float32, ())
+    k = _on_device(metallic, "metallic", who, torch.float32, ())
+    if not len(a) == len(r) == len(k) == len(v):
+        raise RuntimeError(f"{who}: {len(a)} albedo, {len(r)} roughness and {len(k)} metallic values for {len(v)} vertices")
+    if not torch.is_tensor(vis) or vis.device != dev or vis.dtype != torch.int64 or not vis.is_contiguous() or vis.numel() != n * H * W * ss * ss:
+        raise RuntimeError(f"{who}: `vis` must be the contiguous int64 visibility buffer of {n} views of {W * ss} x {H * ss} samples on {dev}")
+    nrm = None if normals is None else _on_device(normals, "normals", who, torch.float64, (3,))
+    shape = (n, H * ss, W * ss)
+    g = {name: torch.empty(shape + (c,), dtype=torch.float32, device=dev)
+         for name, c in (("normal", 3), ("view_dir", 3), ("albedo", 3), ("roughness", 1), ("metallic", 1))}
+    g["coverage"] = torch.empty(shape, dtype=torch.uint8, device=dev)
+    N.launch("gs2m_meshview_gbuffer", dev, len(v), _ptr(v), len(f), _ptr(f), n, _ptr(m), float(fx), float(fy), float(cx), float(cy), W, H, ss,
+             _ptr(vis), _ptr(nrm), _ptr(a), _ptr(r), _ptr(k), _ptr(g["normal"]), _ptr(g["view_dir"]), _ptr(g["albedo"]), _ptr(g["roughness"]),
+             _ptr(g["metallic"]), _ptr(g["coverage"]))
+    return g
+
+
+def resolve_rgb(rgb, coverage, ss, srgb=False, background=None):
+    """Per-sample linear RGB (n, H ss, W ss, 3) float32 and coverage bytes (n, H ss, W ss) -> (n, H, W, 4) uint8: the mean over a
+    pixel's covered samples, optionally sRGB-encoded, straight alpha = the covered share.  background: (n, H, W, 3) float32 in the
+    output's encoding, composited under the alpha; the alpha byte is then 255."""
+    who = "resolve_rgb"
+    rgb = N.f32(rgb, "rgb", who=who)
+    if rgb.dim() != 4 or rgb.shape[3] != 3 or int(ss) < 1 or rgb.shape[1] % int(ss) or rgb.shape[2] % int(ss):
+        raise RuntimeError(f"{who}: `rgb` must have shape (n, H ss, W ss, 3) with ss = {ss}, got {tuple(rgb.shape)}")
+    n, H, W = int(rgb.shape[0]), int(rgb.shape[1]) // int(ss), int(rgb.shape[2]) // int(ss)
+    H, W, ss = _check_frame(H, W, ss, who)
+    if not torch.is_tensor(coverage) or coverage.device != rgb.device or coverage.dtype != torch.uint8 or coverage.numel() * 3 != rgb.numel():
+        raise RuntimeError(f"{who}: `coverage` must be a uint8 tensor of shape {tuple(rgb.shape[:3])} on {rgb.device}")
+    bg = None if background is None else N.f32(background, "background", (n, H, W, 3), who=who)
+    out = torch.empty((n, H, W, 4), dtype=torch.uint8, device=rgb.device)
+    N.launch("gs2m_meshview_resolve_rgb", rgb.device, n, W, H, ss, _ptr(rgb), _ptr(coverage.contiguous()), 1 if srgb else 0, _ptr(bg), _ptr(out))
+    return out
+
+
+def pixel_view_dirs(w2c, fx, fy, cx, cy, H, W):
+    """The unit directions surface -> eye along the rays through the pixel centres, in world space: (n, H, W, 3) float32, what
+    gs2m_relight.environment_behind takes."""
+    m = torch.as_tensor(w2c).to(torch.float64).reshape(-1, 4, 4)
+    j, i = torch.meshgrid(torch.arange(H, dtype=torch.float64, device=m.device), torch.arange(W, dtype=torch.float64, device=m.device), indexing="ij")
+    r = torch.stack([(i + 0.5 - cx) / fx, (j + 0.5 - cy) / fy, torch.ones_like(i)], dim=-1)
+    world = torch.einsum("nck,hwc->nhwk", m[:, :3, :3], r)
+    return (-world / world.norm(dim=-1, keepdim=True)).to(torch.float32)
+
+
+def shade_views_pbr(vertices, triangles, w2c, fx, fy, cx, cy, H, W, light, albedo, roughness, metallic, ss=2, shading="smooth",
+                    gamma=False, background="none", view_batch=None, near=NEAR, far=FAR):
+    """Views of a material mesh under an environment light: (n_views, H, W, 4) uint8 on the device.  light: anything with
+    `.cubemap` (a CubemapLight) and `.brdf_lut`, e.g. gs2m_envmap.EnvLight; albedo (V, 3), roughness (V,), metallic (V,): float32
+    vertex attributes.  Per batch of views: the visibility buffer, the G-buffer of its samples, the project's fused split-sum
+    shading (pbr_shading_fused) on every sample, and the resolve over ss x ss samples; gamma: sRGB-encode the resolved colour.
+    background "none": straight alpha = the covered share of the pixel; "env": the environment along the pixel's ray
+    (gs2m_relight.environment_behind) under the alpha, which is then 255."""
+    from pbr import pbr_shading_fused
+    who = "shade_views_pbr"
+    v, f, m = _mesh_args(vertices, triangles, w2c, who)
+    H, W, ss = _check_frame(H, W, ss, who)
+    if shading not in ("flat", "smooth"):
+        raise RuntimeError(f"{who}: `shading` must be 'flat' or 'smooth', got {shading!r}")
+    if background not in ("none", "env"):
+        raise RuntimeError(f"{who}: `background` must be 'none' or 'env', got {background!r}")
+    dev, n = v.device, len(m)
+    normals = vertex_normals(v, f)[0] if shading == "smooth" else None
+    per_view = (8 + 4 * 14 + 1) * H * W * ss * ss  # the keys, the G-buffer and the shaded samples
+    batch = int(view_batch) if view_batch else max(1, VIS_BUDGET // max(per_view, 1))
+    batch = max(1, min(batch, max(n, 1)))
+    rgba = torch.empty((n, H, W, 4), dtype=torch.uint8, device=dev)
+    buf = torch.empty(batch * H * W * ss * ss, dtype=torch.int64, device=dev)
+    with torch.no_grad():
+        light.cubemap.build_mips()
+        for k in range(0, n, batch):
+            part = m[k:k + batch]
+            vis = visibility_buffer(v, f, part, fx, fy, cx, cy, H, W, ss, near, far, out=buf)
+            g = mesh_gbuffer(v, f, part, fx, fy, cx, cy, H, W, vis.reshape(-1), albedo, roughness, metallic, ss, normals)
+            rgb = pbr_shading_fused(light.cubemap, g["normal"], g["view_dir"], g["albedo"], g["roughness"], metallic=g["metallic"],
+                                    brdf_lut=light.brdf_lut, gamma=False)["render_rgb"]
+            bg = None
+            if background == "env":
+                from gs2m_relight import environment_behind
+                dirs = pixel_view_dirs(part, fx, fy, cx, cy, H, W)
+                bg = torch.stack([environment_behind(light, d, gamma) for d in dirs]).contiguous()
+            rgba[k:k + batch] = resolve_rgb(rgb.reshape(len(part), H * ss, W * ss, 3), g["coverage"], ss, gamma, bg)
+    return rgba
 
 
 def turntable(w2c, frames=FRAMES, shift=(0.0, 0.0, 0.0)):
@@ -218,7 +316,25 @@ def view_files(a):
     from gs2m_png import Writer
     writer = Writer("device" if getattr(a, "device_png", False) else "host")  # the PNGs; the GIF and the WebP stay on Pillow
 
+    material = light = None
+    if a.colour == "pbr":
+        import gs2m_relight as RL
+        from gs2m_envmap import EnvLight
+        from gs2m_mesh_bake import read_material_mesh
+        if not a.envmap:
+            raise RuntimeError("--colour pbr needs --envmap FILE.hdr")
+        try:
+            mm = read_material_mesh(a.ply_path)
+        except ValueError as e:
+            raise RuntimeError(f"--colour pbr needs a material mesh (gs2m_mesh_bake.py writes one): {e}") from None
+        material = [torch.as_tensor(mm[k]).to(dev) for k in ("albedo", "roughness", "metallic")]
+        light = EnvLight.from_hdr(a.envmap, a.env_res, a.env_samples, math.radians(a.env_rotation), a.exposure, device=dev)
+        RL._check(light, "env", "normal")  # the light's size, as the relighting checks it
+
     def shade(w2c, k, H, W):
+        if material is not None:
+            return shade_views_pbr(v, f, torch.as_tensor(np.ascontiguousarray(w2c)).to(dev), k["fx"], k["fy"], k["cx"], k["cy"], H, W, light,
+                                   *material, ss=a.ss, shading=a.shading, gamma=a.gamma, background=a.background)
         return shade_views(v, f, torch.as_tensor(np.ascontiguousarray(w2c)).to(dev), k["fx"], k["fy"], k["cx"], k["cy"], H, W, ss=a.ss,
                            shading=a.shading, colors=col)
 
@@ -275,7 +391,15 @@ def parser():
     ap.add_argument("--frames", type=int, default=FRAMES, help=argparse.SUPPRESS)  # for the tests
     ap.add_argument("--shift", type=float, nargs=3, default=(0.0, 0.0, 0.0), metavar=("X", "Y", "Z"), help="moves the mesh (still, animation)")
     ap.add_argument("--shading", choices=("flat", "smooth"), default="flat")
-    ap.add_argument("--colour", choices=("grey", "vertex"), default="grey")
+    ap.add_argument("--colour", choices=("grey", "vertex", "pbr"), default="grey",
+                    help="pbr: a material mesh (gs2m_mesh_bake.py) shaded under --envmap; the options below belong to it")
+    ap.add_argument("--envmap", default="", help="lat-long Radiance file (.hdr), as gs2m_relight.py takes it")
+    ap.add_argument("--env-res", type=int, default=512, help="cube-map resolution: a power of two >= 64")
+    ap.add_argument("--env-samples", type=int, default=None, help="S x S taps per texel, 1 .. 16")
+    ap.add_argument("--env-rotation", type=float, default=0.0, help="degrees about +y")
+    ap.add_argument("--exposure", type=float, default=0.0, help="stops: the radiance is scaled by 2^EV")
+    ap.add_argument("--gamma", action="store_true", help="sRGB-encode the shaded colour")
+    ap.add_argument("--background", choices=("none", "env"), default="none", help="env: the environment along the view ray behind the mesh")
     ap.add_argument("--ss", type=int, default=2, help="samples per pixel and axis, 1 .. 4")
     ap.add_argument("--out-dir", default="", help="default: visual/ beside the mesh's directory")
     from gs2m_png import add_png_argument

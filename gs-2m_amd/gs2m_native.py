@@ -213,6 +213,11 @@ SIGNATURES = {
     "gs2m_meshview_normals_workspace_bytes": (i, [p]),
     "gs2m_meshview_normals": (i, [ll, p, ll, p, p, p, p, s]),
     "gs2m_meshview_shade": (i, [ll, p, ll, p, i, p, d, d, d, d, i, i, i, p, p, p, d, d, d, d, d, i, p, p, p, s]),
+    "gs2m_meshview_gbuffer": (i, [ll, p, ll, p, i, p, d, d, d, d, i, i, i, p, p, p, p, p, p, p, p, p, p, p, s]),
+    "gs2m_meshview_resolve_rgb": (i, [i, i, i, i, p, p, i, p, p, s]),
+    # include/gs2m_meshbake.h
+    "gs2m_meshbake_accumulate": (i, [ll, p, p, i, p, d, d, d, d, i, i, p, i, p, p, d, i, p, p, s]),
+    "gs2m_meshbake_resolve": (i, [ll, i, p, p, d, p, p, p, s]),
     # include/gs2m_png.h
     "gs2m_png_plan": (i, [i, i, i, i, p, p, p, p]),
     "gs2m_png_filter": (i, [i, i, i, i, p, p, s]),

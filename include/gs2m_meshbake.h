@@ -1,0 +1,55 @@
+/* gs2m_meshbake.h -- C ABI of the per-vertex attribute bake (mesh_bake.hip), part of libgs2m_raster.so.
+ *
+ * The per-view material maps of a trained model (albedo, roughness, metallic: any C <= 8 planes) are carried onto the vertices of
+ * the reconstructed mesh: every vertex is projected into every view, the views that see it are sampled bilinearly and averaged
+ * with a weight that favours head-on views; DESIGN.md §20 writes the contract down.  Everything is fp64 and evaluated as written
+ * (-ffp-contract=off).  Vertices and normals are (n, 3) fp64, a view is a DEVICE double 4 x 4 world-to-camera matrix, row major,
+ * OpenCV convention; fx, fy, cx, cy are the pinhole intrinsics of every view of the call; images are float32, row major.
+ *
+ *   Project, test  per vertex p and view: the camera-space point, z, u, v, `inside`, the depth sample d and `front` are those of
+ *                  the Votes paragraph of gs2m_visibility.h (its z = z0 + 1e-8 included), d read from `depth`: the mesh's own
+ *                  z-buffer, gs2m_meshdepth_render's image for the same views and frame.
+ *   Taps           x0 = floor(u), y0 = floor(v), tx = u - x0, ty = v - y0; the four taps (y0, x0), (y0, x0 + 1), (y0 + 1, x0),
+ *                  (y0 + 1, x0 + 1) have the weights (1 - tx) (1 - ty), tx (1 - ty), (1 - tx) ty, tx ty.  A neighbour outside
+ *                  the frame has weight 0 and is not read.
+ *   Mask           with `mask`, the view is skipped unless every tap of non-zero weight has mask >= 0.5.
+ *   Weight         without `normals`, w = 1.  With them, N = the vertex's normal, o = the camera centre,
+ *                  o_k = -((M[0][k] M[0][3] + M[1][k] M[1][3]) + M[2][k] M[2][3]), e = o - p,
+ *                  w = max(0, dot(N, e) / sqrt(dot(N, N) dot(e, e))), dot(a, b) = (a0 b0 + a1 b1) + a2 b2;
+ *                  N zero or not finite gives w = 0.
+ *   Sample         a_c = ((A[y0][x0] ((1 - tx) (1 - ty)) + A[y0][x0 + 1] (tx (1 - ty))) + A[y0 + 1][x0] ((1 - tx) ty))
+ *                  + A[y0 + 1][x0 + 1] (tx ty), A = maps[view][c], the fp32 taps widened to double.
+ *   Accumulate     when the view is inside, front, unmasked and w > 0: sums[p][c] = sums[p][c] + w a_c for every c, then
+ *                  weights[p] = weights[p] + w.  With accumulate == 0 both start from 0, else from the stored values.  The
+ *                  additions happen one view at a time in view order: one call over the views 0 .. n and two calls over
+ *                  0 .. k and k .. n (the second with accumulate != 0) give the same bits.
+ *   Resolve        seen[p] = weights[p] >= min_weight && weights[p] > 0; out[p][c] = (float)(sums[p][c] / weights[p]) when
+ *                  seen, else fallback[c].
+ *
+ * Every buffer is the caller's.  Return GS2M_OK (0) or a negative GS2M_ERR_* code (gs2m_raster.h).  No float atomics: a vertex
+ * belongs to one thread, results are bitwise reproducible. */
+#ifndef GS2M_MESHBAKE_H
+#define GS2M_MESHBAKE_H
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* verts: double (n_verts, 3); normals: double (n_verts, 3), gs2m_meshview_normals's output, or NULL; w2c: DEVICE double
+ * (n_views, 4, 4); depth: float (n_views, H, W); maps: float (n_views, C, H, W), 1 <= C <= 8; mask: float (n_views, H, W) or NULL;
+ * sums: double (n_verts, C); weights: double (n_verts) (see above).  n_verts == 0 or n_views == 0 is valid: nothing is sampled,
+ * and with accumulate == 0 the two buffers are still set to 0.  GS2M_ERR_INVALID_ARG, without a launch, for C outside 1 .. 8,
+ * W or H < 1, fx or fy == 0, a NaN eps or a missing buffer. */
+int gs2m_meshbake_accumulate(long long n_verts, const double* verts, const double* normals, int n_views, const double* w2c,
+                             double fx, double fy, double cx, double cy, int W, int H, const float* depth, int C, const float* maps,
+                             const float* mask, double eps, int accumulate, double* sums, double* weights, void* stream);
+
+/* out: float (n_verts, C); seen: unsigned char (n_verts), 1 or 0; fallback: C HOST floats (see above). */
+int gs2m_meshbake_resolve(long long n_verts, int C, const double* sums, const double* weights, double min_weight,
+                          const float* fallback, float* out, unsigned char* seen, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif

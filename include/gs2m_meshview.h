@@ -27,6 +27,14 @@
  *                  1.055 pow(x, 1 / 2.4) - 0.055; colour byte floor(255 enc + 0.5), alpha byte floor(255 m / ss^2 + 0.5).
  *                  Colour is straight, not premultiplied.  depth and tri_id come from sample (ss / 2) (ss + 1) of the block:
  *                  the fp32 z and the triangle index, 0 and -1 where it is empty.
+ *   G-buffer       per sample, with r, l_k and N (flat or smooth) of the Shade paragraph: N is negated when dot(N, r) > 0, so
+ *                  that it faces the eye; Nw_k = (M[0][k] N0 + M[1][k] N1) + M[2][k] N2 takes it to world space and
+ *                  normal = Nw / sqrt(dot(Nw, Nw)); the view direction, surface to eye, is the same of -r.  albedo_k, roughness
+ *                  and metallic are (l0 Xa + l1 Xb) + l2 Xc of the float vertex arrays widened to double.  Every value is
+ *                  rounded once to fp32; coverage is 1.  An empty sample has coverage 0 and every value 0.
+ *   Resolve RGB    the Resolve paragraph on samples shaded elsewhere: lin_k = min(max(rgb_k, 0), 1) of the sample's float RGB
+ *                  widened to double, covered = its coverage byte is not 0.  With a background, (0, 0, 0) for enc where m == 0,
+ *                  a = m / ss^2, the colour byte is floor(255 (a enc_k + (1 - a) min(max(bg_k, 0), 1)) + 0.5) and alpha is 255.
  *
  * Every buffer is the caller's; workspace sizes come from the *_workspace_bytes functions.  Return GS2M_OK (0) or a negative
  * GS2M_ERR_* code (gs2m_raster.h).  No float atomics: results are bitwise reproducible. */
@@ -64,6 +72,23 @@ int gs2m_meshview_shade(long long n_verts, const double* verts, long long n_tris
                         double fx, double fy, double cx, double cy, int W, int H, int ss, const unsigned long long* vis,
                         const double* normals, const float* colors, double base_r, double base_g, double base_b, double ambient,
                         double diffuse, int srgb, unsigned char* rgba, float* depth, int* tri_id, void* stream);
+
+/* The G-buffer of the samples (see above) from `vis`, as gs2m_meshview_shade reads it: out_normal, out_view_dir, out_albedo:
+ * float (n_views, H ss, W ss, 3); out_roughness, out_metallic: float (n_views, H ss, W ss); coverage: unsigned char
+ * (n_views, H ss, W ss).  normals: double (n_verts, 3) for smooth normals, NULL for flat.  albedo: float (n_verts, 3), roughness
+ * and metallic: float (n_verts).  Keys are not trusted: one whose triangle index is not below n_tris, or whose triangle names a
+ * vertex outside [0, n_verts), is an empty sample. */
+int gs2m_meshview_gbuffer(long long n_verts, const double* verts, long long n_tris, const int* tris, int n_views, const double* w2c,
+                          double fx, double fy, double cx, double cy, int W, int H, int ss, const unsigned long long* vis,
+                          const double* normals, const float* albedo, const float* roughness, const float* metallic,
+                          float* out_normal, float* out_view_dir, float* out_albedo, float* out_roughness, float* out_metallic,
+                          unsigned char* coverage, void* stream);
+
+/* rgba: unsigned char (n_views, H, W, 4) from rgb: float (n_views, H ss, W ss, 3), the samples' linear colour, and coverage:
+ * unsigned char (n_views, H ss, W ss) (see above).  background: float (n_views, H, W, 3) composited under the alpha, in the
+ * encoding of the output, or NULL. */
+int gs2m_meshview_resolve_rgb(int n_views, int W, int H, int ss, const float* rgb, const unsigned char* coverage, int srgb,
+                              const float* background, unsigned char* rgba, void* stream);
 
 #ifdef __cplusplus
 }

@@ -105,6 +105,28 @@ static inline Grid carve_grid(char* base, long long n) {
     g.bytes = c.off;
     return g;
 }
+// ---- the workspace of gs2m_mesh_compact (mesh_post.hip) ----
+// mesh_simplify.hip reads `av` after the call: av[v] is the new id of vertex v where av[v + 1] != av[v] (v survived).
+struct CompactWs {
+    unsigned char* used;  // V
+    u64* av;              // V + 1
+    u64* at;              // F + 1
+    u64* bsum;            // scan blocks of the longer of the two + 1
+    int* err;
+    size_t bytes;
+};
+static inline CompactWs carve_compact(char* base, long long nv, long long nt) {
+    Carver c{base, 0};
+    CompactWs w;
+    w.used = c.take<unsigned char>((size_t)(nv > 0 ? nv : 1));
+    w.av = c.take<u64>((size_t)nv + 1);
+    w.at = c.take<u64>((size_t)nt + 1);
+    w.bsum = c.take<u64>(gs2m_scan_blocks(nv > nt ? nv : nt) + 1);
+    w.err = c.take<int>(2);
+    w.bytes = c.off;
+    return w;
+}
+
 // a triangle's vertex indices against the vertex count; err[0] = 1 tells the host of one out of range
 __device__ __forceinline__ bool tri_in_range(int a, int b, int c, long long nv, int* __restrict__ err) {
     if (a < 0 || b < 0 || c < 0 || a >= nv || b >= nv || c >= nv) {

@@ -259,26 +259,6 @@ __global__ void __launch_bounds__(256) gather_triangles_kernel(long long nt, con
     }
 }
 
-struct CompactWs {
-    unsigned char* used;  // V
-    u64* av;              // V + 1
-    u64* at;              // F + 1
-    u64* bsum;            // scan blocks of the longer of the two + 1
-    int* err;
-    size_t bytes;
-};
-CompactWs carve_compact(char* base, long long nv, long long nt) {
-    Carver c{base, 0};
-    CompactWs w;
-    w.used = c.take<unsigned char>((size_t)(nv > 0 ? nv : 1));
-    w.av = c.take<u64>((size_t)nv + 1);
-    w.at = c.take<u64>((size_t)nt + 1);
-    w.bsum = c.take<u64>(gs2m_scan_blocks(nv > nt ? nv : nt) + 1);
-    w.err = c.take<int>(2);
-    w.bytes = c.off;
-    return w;
-}
-
 int bits_holding(long long vmax) {  // bits that hold 0 .. vmax
     int b = 1;
     while (b < 32 && (1ll << b) <= vmax) b++;

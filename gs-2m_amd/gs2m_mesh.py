@@ -9,7 +9,8 @@ the memory is torch tensors owned here (the library allocates nothing).  The blo
 box fixed at creation: `fuse_depths` derives it from the depth maps (or `bounds`).
 
     python gs-2m_amd/gs2m_mesh.py --ply point_cloud.ply -s SCENE -o OUT [--dtu | --tnt [--scene NAME]]
-writes OUT/tsdf_mesh.ply, OUT/tsdf_post.ply and OUT/config.json as render.py --extract_mesh does.
+writes OUT/tsdf_mesh.ply, OUT/tsdf_post.ply and OUT/config.json as render.py --extract_mesh does; with --simplify-cell X or
+--simplify-triangles N also OUT/tsdf_simplified.ply (`simplify_mesh_gpu`: csrc/mesh_simplify.hip).
 """
 import argparse
 import ctypes as C
@@ -390,6 +391,121 @@ def post_process_mesh_gpu(mesh, cluster_to_keep=1, device="cuda"):
     return out if isinstance(mesh, DeviceMesh) else out.cpu()
 
 
+# ---- simplification (csrc/mesh_simplify.hip, include/gs2m_simplify.h) ---------------------------------------------------
+
+SIMPLIFY_STAGES = ("keys_sorts", "quadrics", "placement", "remap_dedupe", "compaction")
+LADDER = 8  # rungs per octave of the target-count search
+
+
+def simplify_count_gpu(vertices, triangles, cell):
+    """(surviving vertices, emitted triangles) of the contract at `cell`, without placement: the probe of the search."""
+    dev, V, F = vertices.device, len(vertices), len(triangles)
+    if V == 0 or F == 0:
+        return 0, 0
+    ws = workspace_for("gs2m_simplify_workspace_bytes", dev, V, F, 0)
+    tot = (C.c_longlong * 2)()
+    N.launch("gs2m_simplify_count", dev, V, F, _ptr(vertices), _ptr(triangles), float(cell), _ptr(ws), tot)
+    return int(tot[0]), int(tot[1])
+
+
+def simplify_base_cell(vertices, triangles):
+    """The first rung of the ladder: the shortest non-degenerate edge of the first 4096 triangles (fp64 lengths of the fp32
+    corners), a pure function of the input; 1.0 when they have none."""
+    t = triangles[:4096].long()
+    if len(t) == 0:
+        return 1.0
+    p = vertices.double()[t]  # (n, 3 corners, 3)
+    e = torch.cat([p[:, 1] - p[:, 0], p[:, 2] - p[:, 1], p[:, 0] - p[:, 2]]).norm(dim=1)
+    e = e[(e > 0) & torch.isfinite(e)]
+    return float(e.min()) if len(e) else 1.0
+
+
+def simplify_target_cell(vertices, triangles, target_triangles, max_rungs=8 * 40):
+    """The cell of the ladder cell_k = base * 2^(k / 8) (base: simplify_base_cell) that bisection with gs2m_simplify_count
+    settles on: its result has at most `target_triangles` triangles and rung k - 1 has more.  -> (cell, k)."""
+    base, n = simplify_base_cell(vertices, triangles), int(target_triangles)
+    count = lambda k: simplify_count_gpu(vertices, triangles, base * 2.0 ** (k / LADDER))[1]
+    lo, hi = -1, LADDER  # invariant: count(lo) > n (rung -1 stands for the input itself), count(hi) <= n
+    while count(hi) > n:
+        lo, hi = hi, hi * 2
+        if hi > max_rungs:
+            raise RuntimeError(f"simplify_mesh_gpu: no cell up to base * 2^{max_rungs // LADDER} reaches {n} triangles")
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        if mid >= 0 and count(mid) <= n:
+            hi = mid
+        else:
+            lo = mid
+    return base * 2.0 ** (hi / LADDER), hi
+
+
+def simplify_mesh_gpu(mesh, cell=None, target_triangles=None, attributes=None, weights=None, device="cuda", extras=False):
+    """Vertex clustering with quadric placement on the device (include/gs2m_simplify.h has the contract).  A DeviceMesh is
+    processed where it is and a DeviceMesh comes back; a TriangleMesh goes to `device` and comes back as a TriangleMesh.  The
+    vertex colours are carried as three channels; `attributes` (V, k) are further fp32 channels, `weights` (V,) >= 0 weigh all
+    of them within a cell (None: all ones).  With `extras` (or attributes) the result is (mesh, dict(attributes, weight,
+    vertex_map, cell, input_triangles)): weight is a cell's weight sum (0: no weighted vertex, its values are the plain
+    mean), vertex_map the new id of every input vertex or -1.
+
+    Exactly one of `cell` and `target_triangles`.  target_triangles searches the ladder cell_k = base * 2^(k / 8), base the
+    shortest non-degenerate edge of the first 4096 triangles, by bisection with the count-only entry point.  The count is NOT
+    monotone in the cell (the lattice shifts against the surface), so only two facts are guaranteed: the result has at most
+    target_triangles triangles, and the rung below the chosen one has more.  A target that is not below the input's count
+    returns the mesh unchanged (cell = None in the extras)."""
+    who = "simplify_mesh_gpu"
+    if (cell is None) == (target_triangles is None):
+        raise ValueError(f"{who}: give exactly one of `cell` and `target_triangles`")
+    if cell is not None and not (math.isfinite(float(cell)) and float(cell) > 0):
+        raise ValueError(f"{who}: `cell` must be finite and positive, got {cell}")
+    if target_triangles is not None and int(target_triangles) < 0:
+        raise ValueError(f"{who}: `target_triangles` must not be negative")
+    dm = _post_device(mesh, device, who)
+    dev, V, F = dm.device, len(dm.vertices), len(dm.triangles)
+    with N.device_guard(dev):
+        att = None if attributes is None else torch.as_tensor(attributes).to(dev, torch.float32).reshape(V, -1)
+        w = None if weights is None else torch.as_tensor(weights).to(dev, torch.float32).reshape(-1).contiguous()
+        if w is not None and len(w) != V:
+            raise ValueError(f"{who}: {len(w)} weights for {V} vertices")
+        k = 0 if att is None else att.shape[1]
+        unchanged = target_triangles is not None and int(target_triangles) >= F
+        if unchanged:
+            out, oa = dm, att
+            ow = torch.ones(V, device=dev) if w is None else w
+            vmap = torch.arange(V, dtype=torch.int32, device=dev)
+        else:
+            if cell is None:
+                cell, _ = simplify_target_cell(dm.vertices, dm.triangles, target_triangles)
+            cell = float(cell)
+            chan = dm.vertex_colors if att is None else torch.cat([dm.vertex_colors, att], dim=1).contiguous()
+            nch = 3 + k
+            ov, oc, ot = torch.empty_like(dm.vertices), torch.empty_like(chan), torch.empty_like(dm.triangles)
+            ow = torch.empty(V, dtype=torch.float32, device=dev)
+            vmap = torch.full((V,), -1, dtype=torch.int32, device=dev)
+            tot = (C.c_longlong * 2)()
+            if V and F:
+                ws = workspace_for("gs2m_simplify_workspace_bytes", dev, V, F, nch)
+                N.launch("gs2m_simplify", dev, V, F, _ptr(dm.vertices), _ptr(dm.triangles), nch, _ptr(chan), _ptr(w), cell, _ptr(ws),
+                         _ptr(ov), _ptr(oc), _ptr(ow), _ptr(ot), _ptr(vmap), tot)
+            nv, nt = int(tot[0]), int(tot[1])
+            out = DeviceMesh(ov[:nv].clone(), ot[:nt].clone(), oc[:nv, :3].clone())  # clones: the input-sized buffers go
+            oa, ow = (None if att is None else oc[:nv, 3:].clone()), ow[:nv].clone()
+    res = out if isinstance(mesh, DeviceMesh) else out.cpu()
+    if not (extras or attributes is not None):
+        return res
+    return res, {"attributes": oa, "weight": ow, "vertex_map": vmap, "cell": None if unchanged else cell, "input_triangles": F}
+
+
+def simplify_stage_times(on=None):
+    """on = True / False: switch the per-stage timing of gs2m_simplify (a stream synchronisation at every stage boundary);
+    None: -> {stage: ms} of the last call."""
+    if on is not None:
+        N.check(N.lib().gs2m_simplify_set_timing(int(bool(on))), "gs2m_simplify_set_timing")
+        return None
+    ms = (C.c_float * 5)()
+    N.check(N.lib().gs2m_simplify_stage_ms(ms), "gs2m_simplify_stage_ms")
+    return {n: float(ms[k]) for k, n in enumerate(SIMPLIFY_STAGES)}
+
+
 _PLY_VERTEX = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
 _PLY_FACE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
 
@@ -491,11 +607,14 @@ def render_views(gaussians, views, render_dir, device="cuda", png="host"):
 
 
 def extract_mesh(gaussians, views, cameras_extent, out_dir, max_depth=-1.0, voxel_size=-1.0, sdf_trunc=-1.0, num_clusters=1,
-                 bounds=None, device="cuda", host_post=False):
+                 bounds=None, device="cuda", host_post=False, simplify_cell=None, simplify_triangles=None):
     """render.py's --extract_mesh path: render, fuse, extract, post-process; writes out_dir/{config.json, tsdf_mesh.ply,
     tsdf_post.ply}.  The mesh stays on the device from extraction through post_process_mesh_gpu; `host_post`: read it back
     and run the host post_process_mesh instead (the same two files, byte for byte).  -> (raw mesh, post-processed mesh),
-    host TriangleMesh both."""
+    host TriangleMesh both.  `simplify_cell` / `simplify_triangles` (one of them): simplify_mesh_gpu runs on the post-processed mesh,
+    out_dir/tsdf_simplified.ply is written too and config.json records the cell and both triangle counts."""
+    if simplify_cell is not None and simplify_triangles is not None:
+        raise ValueError("extract_mesh: give one of `simplify_cell` and `simplify_triangles`")
     os.makedirs(out_dir, exist_ok=True)
     max_depth = max_depth if max_depth > 0 else 2.0 * cameras_extent
     voxel_size = voxel_size if voxel_size > 0 else max_depth / 1024.0
@@ -508,17 +627,45 @@ def extract_mesh(gaussians, views, cameras_extent, out_dir, max_depth=-1.0, voxe
     if host_post:
         mesh = vol.extract_triangle_mesh()
         post = post_process_mesh(mesh, num_clusters)
+        post_device = None
     else:
         on_device = vol.extract_triangle_mesh(to_host=False)
-        mesh, post = on_device.cpu(), post_process_mesh_gpu(on_device, num_clusters).cpu()
+        post_device = post_process_mesh_gpu(on_device, num_clusters)
+        mesh, post = on_device.cpu(), post_device.cpu()
     write_mesh(os.path.join(out_dir, "tsdf_mesh.ply"), mesh)
     write_mesh(os.path.join(out_dir, "tsdf_post.ply"), post)
+    if simplify_cell is not None or simplify_triangles is not None:
+        simple, info = simplify_mesh_gpu(post_device if post_device is not None else DeviceMesh.from_mesh(post, device),
+                                         cell=simplify_cell, target_triangles=simplify_triangles, extras=True)
+        write_mesh(os.path.join(out_dir, "tsdf_simplified.ply"), simple)
+        with open(os.path.join(out_dir, "config.json"), "w") as f:
+            json.dump({"max_depth": max_depth, "voxel_size": voxel_size, "sdf_trunc": sdf_trunc, "simplify_cell": info["cell"],
+                       "simplify_input_triangles": len(post.triangles), "simplify_output_triangles": len(simple.triangles)}, f, indent=4)
+        print(f"[>] simplified at cell {info['cell']}: {len(simple.vertices)} vertices / {len(simple.triangles)} triangles")
     print(f"[>] {len(mesh.vertices)} vertices / {len(mesh.triangles)} triangles raw, {len(post.vertices)} / {len(post.triangles)} "
           f"post-processed; {vol.n_blocks} blocks, {vol.ignored_points} points outside the domain -> {out_dir}")
     return mesh, post
 
 
 TNT_360_SCENES = ("barn", "caterpillar", "ignatius", "truck")
+
+
+def add_simplify_arguments(ap):
+    """--simplify-cell X / --simplify-triangles N.  SUPPRESSed defaults: without the flags the namespace is what it was."""
+    ap.add_argument("--simplify-cell", type=float, default=argparse.SUPPRESS, metavar="X",
+                    help="also write tsdf_simplified.ply: the post-processed mesh clustered on a lattice of edge X (quadric placement)")
+    ap.add_argument("--simplify-triangles", type=int, default=argparse.SUPPRESS, metavar="N",
+                    help="the same with the lattice edge searched for at most N triangles")
+
+
+def simplify_keywords(a, ap=None):
+    """-> extract_mesh's simplify keywords from a parsed namespace ({}: neither flag was given)."""
+    kw = {k: getattr(a, k) for k in ("simplify_cell", "simplify_triangles") if hasattr(a, k)}
+    if len(kw) == 2:
+        if ap is None:
+            raise ValueError("--simplify-cell and --simplify-triangles: choose one")
+        ap.error("--simplify-cell and --simplify-triangles: choose one")
+    return kw
 
 
 def parse_args(argv=None):
@@ -544,7 +691,9 @@ def parse_args(argv=None):
     ap.add_argument("--host-post", action="store_true", help="post-process on the host (numpy / scipy) instead of the device")
     from gs2m_ingest import add_ingest_arguments
     add_ingest_arguments(ap)  # COLMAP datasets: the alpha masks fuse_depths cuts the depths with
+    add_simplify_arguments(ap)
     a = ap.parse_args(argv)
+    simplify_keywords(a, ap)
     if a.dtu and a.tnt:
         ap.error("--dtu and --tnt are two presets: choose one")
     bounds = None
@@ -578,7 +727,7 @@ def main(argv=None):
     model = GaussianModel(a.sh_degree)
     model.load_ply(a.ply)
     extract_mesh(model, cams, extent, a.output, a.max_depth, a.voxel_size, a.sdf_trunc, a.num_clusters, bounds,
-                 host_post=a.host_post)
+                 host_post=a.host_post, **simplify_keywords(a))
 
 
 if __name__ == "__main__":

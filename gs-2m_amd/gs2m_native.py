@@ -149,6 +149,12 @@ SIGNATURES = {
     "gs2m_mesh_cluster_triangles": (i, [ll, ll, p, p, p, p, p, s]),
     "gs2m_mesh_keep_clusters": (i, [ll, p, p, i, p, s]),
     "gs2m_mesh_compact": (i, [ll, ll, p, p, p, p, p, p, p, p, p, s]),
+    # include/gs2m_simplify.h
+    "gs2m_simplify_workspace_bytes": (i, [ll, ll, i, p]),
+    "gs2m_simplify_count": (i, [ll, ll, p, p, d, p, p, s]),
+    "gs2m_simplify": (i, [ll, ll, p, p, i, p, p, d, p, p, p, p, p, p, p, s]),
+    "gs2m_simplify_set_timing": (i, [i]),
+    "gs2m_simplify_stage_ms": (i, [p]),
     # include/gs2m_eval.h
     "gs2m_eval_transform": (i, [ll, p, d, p, p, s]),
     "gs2m_eval_sample_workspace_bytes": (i, [ll, ll, p, p]),

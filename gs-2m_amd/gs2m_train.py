@@ -562,7 +562,10 @@ if __name__ == "__main__":
     ap.add_argument("--c4-fx", type=float, default=None)
     ap.add_argument("--extract-mesh", default=None, metavar="DIR", help="after training: TSDF mesh of the training views into DIR "
                     "(tsdf_mesh.ply, tsdf_post.ply, config.json; gs2m_mesh.extract_mesh with render.py's defaults)")
+    import gs2m_mesh
+    gs2m_mesh.add_simplify_arguments(ap)  # with --extract-mesh: tsdf_simplified.ply as well
     a = ap.parse_args()
+    gs2m_mesh.simplify_keywords(a, ap)
     if a.c4:
         if a.c4_detail is not None:
             C4["detail"] = a.c4_detail
@@ -606,4 +609,4 @@ if __name__ == "__main__":
     if a.extract_mesh:
         import gs2m_mesh
         cams, _, _, _, extent = scene or synthetic_scene(a.true_gaussians, a.views, a.width, a.height)
-        gs2m_mesh.extract_mesh(model, cams, extent, a.extract_mesh)
+        gs2m_mesh.extract_mesh(model, cams, extent, a.extract_mesh, **gs2m_mesh.simplify_keywords(a))

@@ -1,34 +1,32 @@
-// Per-vertex attribute bake: the views' attribute maps averaged onto the mesh's vertices (include/gs2m_meshbake.h; the
-// contract: DESIGN.md §20).
+// Attribute bakes: the views' attribute maps averaged onto the mesh's vertices, or onto the texels of its atlas
+// (include/gs2m_meshbake.h; the contracts: DESIGN.md §20 and §22).
 //
-// Accumulate: a thread per vertex keeps its position, its normal and its C + 1 running sums in registers and walks the views of
-// the call in order; a wave's lanes are 64 neighbouring vertices.  The views' matrices and camera centres are staged in LDS,
-// BAKE_CHUNK at a time, by the whole workgroup (every lane then reads the same words: a broadcast), so no lane re-reads a matrix
-// from memory.  Projection, inside test, taps and the depth sample are vertex_project.h's, the ones the votes use.  A view costs a
-// vertex the four depth taps, and only where it passes them the mask's and the C x 4 attribute taps.  The kernel is instantiated
-// per C so that the sums are registers.  Every tap lies within [0, W - 1] x [0, H - 1]: x0, y0 come from a passed inside test and
-// the neighbours are read only where they exist.  One thread owns a vertex: no atomics, and the order of the additions is the
-// order of the views.
-// Resolve: a thread per vertex.
+// Accumulate: a thread per point -- a vertex, or a texel's point on its triangle -- keeps its position, its normal and its C + 1
+// running sums in registers and walks the views of the call in order (bake_views.h: the views staged in LDS, the projection and
+// the taps of vertex_project.h); a wave's lanes are 64 neighbouring vertices, or 64 texels of a row, which within a cell are
+// neighbours on the surface, so their taps share lines.  The kernels are instantiated per C so that the sums are registers.
+// One thread owns a point: no atomics, and the order of the additions is the order of the views.
+// Resolve: a thread per point.  An unseen texel reads its triangle's per-vertex attributes at the chart's barycentrics
+// (atlas_layout.h), recomputed from the triangle's cell rather than stored per texel.
+// Pack: a thread per texel, two 8-bit images.
 #include <math.h>
 #include "eval_common.h"
 #include "mesh_raster.h"
-#include "vertex_project.h"
+#include "bake_views.h"
+#include "atlas_layout.h"
+#include "srgb_encode.h"
 #include "../../include/gs2m_meshbake.h"
 
 using namespace mesh_raster;
 
 namespace {
 
-constexpr int BAKE_CHUNK = 64;   // views staged in LDS at a time
-constexpr int BAKE_ROW = 16;     // doubles per staged view: the matrix's three rows, the camera centre, one pad
 constexpr int BAKE_CMAX = 8;
 
 template <int C>
 __global__ void __launch_bounds__(256) bake_kernel(long long n, const double* __restrict__ verts, const double* __restrict__ normals,
-                                                   int n_views, const double* __restrict__ w2c, Frame q, const float* __restrict__ depth,
-                                                   const float* __restrict__ maps, const float* __restrict__ mask, double eps,
-                                                   int accumulate, double* __restrict__ sums, double* __restrict__ weights) {
+                                                   BakeViews views, int accumulate, double* __restrict__ sums,
+                                                   double* __restrict__ weights) {
     __shared__ double s_m[BAKE_CHUNK][BAKE_ROW];
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     const bool live = i < n;
@@ -41,7 +39,7 @@ __global__ void __launch_bounds__(256) bake_kernel(long long n, const double* __
 #pragma unroll
             for (int k = 0; k < 3; k++) N[k] = normals[3 * i + k];
             nn = dot3(N, N);
-            lit = isfinite(N[0]) && isfinite(N[1]) && isfinite(N[2]) && !(N[0] == 0.0 && N[1] == 0.0 && N[2] == 0.0);
+            lit = normal_ok(N);
         }
     }
     double acc[C], wsum = 0.0;
@@ -52,48 +50,44 @@ __global__ void __launch_bounds__(256) bake_kernel(long long n, const double* __
         for (int c = 0; c < C; c++) acc[c] = sums[(size_t)i * C + c];
         wsum = weights[i];
     }
-    const size_t frame = (size_t)q.W * q.H;
-    for (int v0 = 0; v0 < n_views; v0 += BAKE_CHUNK) {
-        const int nv = min(BAKE_CHUNK, n_views - v0);
-        __syncthreads();
-        for (int k = threadIdx.x; k < nv * BAKE_ROW; k += 256) {
-            const int v = k / BAKE_ROW, e = k % BAKE_ROW;
-            const double* M = w2c + 16 * (size_t)(v0 + v);
-            double x = 0.0;
-            if (e < 12) x = M[e];
-            else if (e < 15) x = -((M[e - 12] * M[3] + M[4 + e - 12] * M[7]) + M[8 + e - 12] * M[11]);
-            s_m[v][e] = x;
-        }
-        __syncthreads();
-        if (!lit) continue;
-        for (int v = 0; v < nv; v++) {
-            const double* M = s_m[v];
-            double w = 1.0;
-            if (normals) {
-                const double e[3] = {M[12] - p[0], M[13] - p[1], M[14] - p[2]};
-                w = fmax(0.0, dot3(N, e) / sqrt(nn * dot3(e, e)));
-            }
-            if (!(w > 0.0)) continue;  // NaN fails
-            VertexTaps t;
-            if (!project_vertex(M, p, q, t)) continue;
-            const size_t view = (size_t)(v0 + v);
-            if (!in_front(t.z, bilinear_taps(depth + view * frame, q.W, t), eps)) continue;
-            if (mask) {
-                const float* K = mask + view * frame + (size_t)t.y0 * q.W + t.x0;
-                const double ax = 1.0 - t.tx, ay = 1.0 - t.ty;
-                bool ok = true;
-                if (ax * ay != 0.0) ok = ok && K[0] >= 0.5f;
-                if (t.right && t.tx * ay != 0.0) ok = ok && K[1] >= 0.5f;
-                if (t.below && ax * t.ty != 0.0) ok = ok && K[q.W] >= 0.5f;
-                if (t.right && t.below && t.tx * t.ty != 0.0) ok = ok && K[q.W + 1] >= 0.5f;
-                if (!ok) continue;
-            }
-            const float* A = maps + view * C * frame;
+    bake_views<C>(views, lit, p, normals != nullptr, N, nn, s_m, acc, wsum);
+    if (live) {
 #pragma unroll
-            for (int c = 0; c < C; c++) acc[c] = acc[c] + w * bilinear_taps(A + c * frame, q.W, t);
-            wsum = wsum + w;
+        for (int c = 0; c < C; c++) sums[(size_t)i * C + c] = acc[c];
+        weights[i] = wsum;
+    }
+}
+
+// The texel bake: as bake_kernel, but a texel without an owner has no point -- it walks no view and its sums are 0.
+template <int C>
+__global__ void __launch_bounds__(256) texbake_kernel(long long n, const double* __restrict__ points, const double* __restrict__ normals,
+                                                      const int* __restrict__ owner, BakeViews views, int accumulate,
+                                                      double* __restrict__ sums, double* __restrict__ weights) {
+    __shared__ double s_m[BAKE_CHUNK][BAKE_ROW];
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const bool live = i < n;
+    const bool owned = live && owner[i] >= 0;
+    double p[3] = {0.0, 0.0, 0.0}, N[3] = {0.0, 0.0, 0.0}, nn = 0.0;
+    bool lit = owned;
+    if (owned) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) p[k] = points[3 * i + k];
+        if (normals) {
+#pragma unroll
+            for (int k = 0; k < 3; k++) N[k] = normals[3 * i + k];
+            nn = dot3(N, N);
+            lit = normal_ok(N);
         }
     }
+    double acc[C], wsum = 0.0;
+#pragma unroll
+    for (int c = 0; c < C; c++) acc[c] = 0.0;
+    if (owned && accumulate) {
+#pragma unroll
+        for (int c = 0; c < C; c++) acc[c] = sums[(size_t)i * C + c];
+        wsum = weights[i];
+    }
+    bake_views<C>(views, lit, p, normals != nullptr, N, nn, s_m, acc, wsum);
     if (live) {
 #pragma unroll
         for (int c = 0; c < C; c++) sums[(size_t)i * C + c] = acc[c];
@@ -116,11 +110,70 @@ __global__ void __launch_bounds__(256) bake_resolve_kernel(long long n, int C, c
     seen[i] = ok ? 1 : 0;
 }
 
-template <int C>
-void bake_launch(long long n, const double* verts, const double* normals, int n_views, const double* w2c, const Frame& q,
-                 const float* depth, const float* maps, const float* mask, double eps, int accumulate, double* sums, double* weights,
-                 hipStream_t s) {
-    bake_kernel<C><<<blocks_of(n), 256, 0, s>>>(n, verts, normals, n_views, w2c, q, depth, maps, mask, eps, accumulate, sums, weights);
+// texel i of the call is texel (i % width, row0 + i / width) of the atlas
+__global__ void __launch_bounds__(256) texbake_resolve_kernel(long long n, int C, int width, int row0, const double* __restrict__ sums,
+                                                              const double* __restrict__ weights, double min_weight, Fallback fb,
+                                                              const int* __restrict__ owner, long long nt, const int* __restrict__ tris,
+                                                              const int* __restrict__ cells, long long nv, const float* __restrict__ attrs,
+                                                              float* __restrict__ out, unsigned char* __restrict__ seen) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int t = owner[i];
+    const double w = t >= 0 ? weights[i] : 0.0;
+    const bool ok = w >= min_weight && w > 0.0;
+    seen[i] = ok ? 1 : 0;
+    if (ok) {
+        for (int c = 0; c < C; c++) out[(size_t)i * C + c] = (float)(sums[(size_t)i * C + c] / w);
+        return;
+    }
+    bool from_vertices = false;
+    double l[3] = {0.0, 0.0, 0.0};
+    int id[3] = {0, 0, 0};
+    if (attrs && t >= 0 && t < nt) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) id[k] = tris[3 * (size_t)t + k];
+        const int* cell = cells + 4 * (size_t)t;
+        const int side = cell[2], half = cell[3];
+        const int li = (int)(i % width) - cell[0], lj = row0 + (int)(i / width) - cell[1];
+        from_vertices = id[0] >= 0 && id[1] >= 0 && id[2] >= 0 && id[0] < nv && id[1] < nv && id[2] < nv && side >= 8 && side <= 256 &&
+                        (half == 0 || half == 1) && li >= 0 && lj >= 0 && li < side && lj < side;
+        if (from_vertices) atlas_bary(side, half, li, lj, l);
+    }
+    for (int c = 0; c < C; c++) {
+        float x = fb.v[c];
+        if (from_vertices)
+            x = (float)((l[0] * (double)attrs[(size_t)id[0] * C + c] + l[1] * (double)attrs[(size_t)id[1] * C + c]) +
+                        l[2] * (double)attrs[(size_t)id[2] * C + c]);
+        out[(size_t)i * C + c] = x;
+    }
+}
+
+__device__ __forceinline__ unsigned char to_byte(double x) {  // NaN -> 0
+    const double c = x > 0.0 ? (x < 1.0 ? x : 1.0) : 0.0;
+    return (unsigned char)floor(255.0 * c + 0.5);
+}
+
+__global__ void __launch_bounds__(256) texture_pack_kernel(long long n, int C, const float* __restrict__ values, int srgb,
+                                                           unsigned char* __restrict__ base, unsigned char* __restrict__ orm) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float* v = values + (size_t)i * C;
+    for (int d = 0; d < 3; d++) {
+        const double x = (double)v[d], c = x > 0.0 ? (x < 1.0 ? x : 1.0) : 0.0;
+        base[3 * (size_t)i + d] = (unsigned char)floor(255.0 * encode(c, srgb) + 0.5);
+    }
+    if (orm) {
+        orm[3 * (size_t)i] = 255;
+        orm[3 * (size_t)i + 1] = to_byte((double)v[3]);
+        orm[3 * (size_t)i + 2] = to_byte((double)v[4]);
+    }
+}
+
+int views_status(int n_views, double fx, double fy, double cx, double cy, int W, int H, const double* w2c, const float* depth, int C,
+                 const float* maps, double eps) {
+    if (C < 1 || C > BAKE_CMAX || !frame_ok(n_views, W, H, fx, fy, cx, cy) || eps != eps) return GS2M_ERR_INVALID_ARG;
+    if (n_views > 0 && (!w2c || !depth || !maps)) return GS2M_ERR_INVALID_ARG;
+    return GS2M_OK;
 }
 
 }  // namespace
@@ -130,16 +183,15 @@ extern "C" {
 int gs2m_meshbake_accumulate(long long n_verts, const double* verts, const double* normals, int n_views, const double* w2c,
                              double fx, double fy, double cx, double cy, int W, int H, const float* depth, int C, const float* maps,
                              const float* mask, double eps, int accumulate, double* sums, double* weights, void* stream) {
-    if (n_verts < 0 || C < 1 || C > BAKE_CMAX || !frame_ok(n_views, W, H, fx, fy, cx, cy) || eps != eps) return GS2M_ERR_INVALID_ARG;
+    if (n_verts < 0 || views_status(n_views, fx, fy, cx, cy, W, H, w2c, depth, C, maps, eps) != GS2M_OK) return GS2M_ERR_INVALID_ARG;
     if (n_verts > 0 && (!verts || !sums || !weights)) return GS2M_ERR_INVALID_ARG;
-    if (n_views > 0 && (!w2c || !depth || !maps)) return GS2M_ERR_INVALID_ARG;
     if (n_verts == 0) return GS2M_OK;
     if (n_verts > MAX_LAUNCH) return GS2M_ERR_UNSUPPORTED;
     if ((long long)n_views * C * W * H > MAX_LAUNCH) return GS2M_ERR_UNSUPPORTED;
-    const Frame q{fx, fy, cx, cy, 0.0, 0.0, W, H};
+    const BakeViews views{n_views, w2c, Frame{fx, fy, cx, cy, 0.0, 0.0, W, H}, depth, maps, mask, eps};
     hipStream_t s = (hipStream_t)stream;
 #define BAKE_CASE(c) \
-    case c: bake_launch<c>(n_verts, verts, normals, n_views, w2c, q, depth, maps, mask, eps, accumulate, sums, weights, s); break;
+    case c: bake_kernel<c><<<blocks_of(n_verts), 256, 0, s>>>(n_verts, verts, normals, views, accumulate, sums, weights); break;
     switch (C) {
         BAKE_CASE(1) BAKE_CASE(2) BAKE_CASE(3) BAKE_CASE(4) BAKE_CASE(5) BAKE_CASE(6) BAKE_CASE(7) BAKE_CASE(8)
     }
@@ -156,6 +208,53 @@ int gs2m_meshbake_resolve(long long n_verts, int C, const double* sums, const do
     Fallback fb{};
     for (int c = 0; c < C; c++) fb.v[c] = fallback[c];
     bake_resolve_kernel<<<blocks_of(n_verts), 256, 0, (hipStream_t)stream>>>(n_verts, C, sums, weights, min_weight, fb, out, seen);
+    return gs2m_status(hipGetLastError());
+}
+
+int gs2m_texbake_accumulate(long long n_texels, const double* points, const double* normals, const int* owner, int n_views,
+                            const double* w2c, double fx, double fy, double cx, double cy, int W, int H, const float* depth, int C,
+                            const float* maps, const float* mask, double eps, int accumulate, double* sums, double* weights,
+                            void* stream) {
+    if (n_texels < 0 || views_status(n_views, fx, fy, cx, cy, W, H, w2c, depth, C, maps, eps) != GS2M_OK) return GS2M_ERR_INVALID_ARG;
+    if (n_texels > 0 && (!points || !owner || !sums || !weights)) return GS2M_ERR_INVALID_ARG;
+    if (n_texels == 0) return GS2M_OK;
+    if (n_texels > MAX_LAUNCH) return GS2M_ERR_UNSUPPORTED;
+    if ((long long)n_views * C * W * H > MAX_LAUNCH) return GS2M_ERR_UNSUPPORTED;
+    const BakeViews views{n_views, w2c, Frame{fx, fy, cx, cy, 0.0, 0.0, W, H}, depth, maps, mask, eps};
+    hipStream_t s = (hipStream_t)stream;
+#define BAKE_CASE(c) \
+    case c: texbake_kernel<c><<<blocks_of(n_texels), 256, 0, s>>>(n_texels, points, normals, owner, views, accumulate, sums, weights); break;
+    switch (C) {
+        BAKE_CASE(1) BAKE_CASE(2) BAKE_CASE(3) BAKE_CASE(4) BAKE_CASE(5) BAKE_CASE(6) BAKE_CASE(7) BAKE_CASE(8)
+    }
+#undef BAKE_CASE
+    return gs2m_status(hipGetLastError());
+}
+
+int gs2m_texbake_resolve(long long n_texels, int C, int width, int row0, const double* sums, const double* weights, double min_weight,
+                         const float* fallback, const int* owner, long long n_triangles, const int* triangles, const int* cells,
+                         long long n_verts, const float* attributes, float* out, unsigned char* seen, void* stream) {
+    if (n_texels < 0 || C < 1 || C > BAKE_CMAX || min_weight != min_weight || !fallback || width < 1 || row0 < 0 || n_triangles < 0 ||
+        n_verts < 0)
+        return GS2M_ERR_INVALID_ARG;
+    if (n_texels > 0 && (!sums || !weights || !owner || !out || !seen)) return GS2M_ERR_INVALID_ARG;
+    if (attributes && (!triangles || !cells)) return GS2M_ERR_INVALID_ARG;
+    if (n_texels == 0) return GS2M_OK;
+    if (n_texels > MAX_LAUNCH || (n_texels + width - 1) / width + row0 > 0x7FFFFFFFll) return GS2M_ERR_UNSUPPORTED;
+    Fallback fb{};
+    for (int c = 0; c < C; c++) fb.v[c] = fallback[c];
+    texbake_resolve_kernel<<<blocks_of(n_texels), 256, 0, (hipStream_t)stream>>>(n_texels, C, width, row0, sums, weights, min_weight, fb, owner,
+                                                                                 n_triangles, triangles, cells, n_verts, attributes, out, seen);
+    return gs2m_status(hipGetLastError());
+}
+
+int gs2m_texture_pack(long long n_texels, int C, const float* values, int srgb, unsigned char* base_color, unsigned char* orm,
+                      void* stream) {
+    if (n_texels < 0 || (C != 3 && C != 5) || (C == 3 && orm) || (C == 5 && n_texels > 0 && !orm)) return GS2M_ERR_INVALID_ARG;
+    if (n_texels > 0 && (!values || !base_color)) return GS2M_ERR_INVALID_ARG;
+    if (n_texels == 0) return GS2M_OK;
+    if (n_texels > MAX_LAUNCH) return GS2M_ERR_UNSUPPORTED;
+    texture_pack_kernel<<<blocks_of(n_texels), 256, 0, (hipStream_t)stream>>>(n_texels, C, values, srgb ? 1 : 0, base_color, orm);
     return gs2m_status(hipGetLastError());
 }
 

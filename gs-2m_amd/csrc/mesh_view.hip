@@ -15,6 +15,7 @@
 #include <math.h>
 #include "eval_common.h"
 #include "mesh_raster.h"
+#include "srgb_encode.h"
 #include "../../include/gs2m_meshview.h"
 
 using namespace mesh_raster;
@@ -67,11 +68,6 @@ struct Shade {
     double base[3], ambient, diffuse;
     int srgb, ss;
 };
-
-__device__ __forceinline__ double encode(double x, int srgb) {
-    if (!srgb) return x;
-    return x <= 0.0031308 ? 12.92 * x : 1.055 * pow(x, 1.0 / 2.4) - 0.055;
-}
 
 // The Shade paragraph up to the normal, for sample (i, j) of the sample frame q with key `key`: the triangle's vertex indices, the
 // sample's ray, the barycentrics and N in camera space (smooth where `normals` is given and usable, else flat).  false: the

@@ -1,0 +1,13 @@
+// The display transfer of the 8-bit outputs, shared by mesh_view.hip (the shaded views) and mesh_bake.hip (the base-colour
+// texture): one copy of the sRGB encode.  fp64, as written.
+#pragma once
+#include <math.h>
+
+namespace mesh_raster {
+
+__device__ __forceinline__ double encode(double x, int srgb) {
+    if (!srgb) return x;
+    return x <= 0.0031308 ? 12.92 * x : 1.055 * pow(x, 1.0 / 2.4) - 0.055;
+}
+
+}  // namespace mesh_raster

@@ -10,7 +10,8 @@ box fixed at creation: `fuse_depths` derives it from the depth maps (or `bounds`
 
     python gs-2m_amd/gs2m_mesh.py --ply point_cloud.ply -s SCENE -o OUT [--dtu | --tnt [--scene NAME]]
 writes OUT/tsdf_mesh.ply, OUT/tsdf_post.ply and OUT/config.json as render.py --extract_mesh does; with --simplify-cell X or
---simplify-triangles N also OUT/tsdf_simplified.ply (`simplify_mesh_gpu`: csrc/mesh_simplify.hip).
+--simplify-triangles N also OUT/tsdf_simplified.ply (`simplify_mesh_gpu`: csrc/mesh_simplify.hip); with --texture-size N also
+OUT/tsdf_textured.glb, that mesh (else tsdf_post.ply) with a baked texture atlas (gs2m_mesh_texture.py).
 """
 import argparse
 import ctypes as C
@@ -658,6 +659,12 @@ def add_simplify_arguments(ap):
                     help="the same with the lattice edge searched for at most N triangles")
 
 
+def add_texture_arguments(ap):
+    """--texture-size N.  SUPPRESSed default: without the flag the namespace is what it was (and gs2m_mesh_texture is not imported)."""
+    ap.add_argument("--texture-size", type=int, default=argparse.SUPPRESS, metavar="N",
+                    help="also write tsdf_textured.glb: the simplified (else the post-processed) mesh with an atlas at most N texels wide")
+
+
 def simplify_keywords(a, ap=None):
     """-> extract_mesh's simplify keywords from a parsed namespace ({}: neither flag was given)."""
     kw = {k: getattr(a, k) for k in ("simplify_cell", "simplify_triangles") if hasattr(a, k)}
@@ -692,6 +699,7 @@ def parse_args(argv=None):
     from gs2m_ingest import add_ingest_arguments
     add_ingest_arguments(ap)  # COLMAP datasets: the alpha masks fuse_depths cuts the depths with
     add_simplify_arguments(ap)
+    add_texture_arguments(ap)
     a = ap.parse_args(argv)
     simplify_keywords(a, ap)
     if a.dtu and a.tnt:
@@ -728,6 +736,11 @@ def main(argv=None):
     model.load_ply(a.ply)
     extract_mesh(model, cams, extent, a.output, a.max_depth, a.voxel_size, a.sdf_trunc, a.num_clusters, bounds,
                  host_post=a.host_post, **simplify_keywords(a))
+    if hasattr(a, "texture_size"):  # the textured asset, from the simplified mesh when this run wrote one
+        from gs2m_mesh_texture import texture_mesh
+        source = "tsdf_simplified.ply" if simplify_keywords(a) else "tsdf_post.ply"
+        texture_mesh(model, cams, read_mesh(os.path.join(a.output, source)), os.path.join(a.output, "tsdf_textured.glb"),
+                     texture_size=a.texture_size)
 
 
 if __name__ == "__main__":

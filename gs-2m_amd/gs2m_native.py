@@ -224,6 +224,14 @@ SIGNATURES = {
     # include/gs2m_meshbake.h
     "gs2m_meshbake_accumulate": (i, [ll, p, p, i, p, d, d, d, d, i, i, p, i, p, p, d, i, p, p, s]),
     "gs2m_meshbake_resolve": (i, [ll, i, p, p, d, p, p, p, s]),
+    "gs2m_texbake_accumulate": (i, [ll, p, p, p, i, p, d, d, d, d, i, i, p, i, p, p, d, i, p, p, s]),
+    "gs2m_texbake_resolve": (i, [ll, i, i, i, p, p, d, p, p, ll, p, p, ll, p, p, p, s]),
+    "gs2m_texture_pack": (i, [ll, i, p, i, p, p, s]),
+    # include/gs2m_atlas.h
+    "gs2m_atlas_workspace_bytes": (i, [ll, p]),
+    "gs2m_atlas_count": (i, [ll, ll, p, p, d, p, p, p, s]),
+    "gs2m_atlas_build": (i, [ll, ll, p, p, d, p, p, p, p, p, p, p, s]),
+    "gs2m_atlas_texels": (i, [ll, p, p, ll, p, p, p, i, i, i, i, p, p, p, p, s]),
     # include/gs2m_png.h
     "gs2m_png_plan": (i, [i, i, i, i, p, p, p, p]),
     "gs2m_png_filter": (i, [i, i, i, i, p, p, s]),

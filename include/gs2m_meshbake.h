@@ -48,6 +48,40 @@ int gs2m_meshbake_accumulate(long long n_verts, const double* verts, const doubl
 int gs2m_meshbake_resolve(long long n_verts, int C, const double* sums, const double* weights, double min_weight,
                           const float* fallback, float* out, unsigned char* seen, void* stream);
 
+/* ---- the texel bake: the same views averaged onto the texels of a triangle atlas (gs2m_atlas.h) ----
+ *
+ *   Accumulate     a texel is a point: points, normals (n_texels, 3) and owner (n_texels) are gs2m_atlas_texels's output (any
+ *                  run of whole rows of it).  A texel with owner < 0 walks no view; its sums and weight are set to 0.  For
+ *                  every other texel the Project .. Accumulate paragraphs above apply word for word with p = its point and
+ *                  N = its normal (both kernels run the same code: csrc/bake_views.h), `accumulate` included.
+ *   Resolve        seen[p] = owner[p] >= 0 && weights[p] >= min_weight && weights[p] > 0; out[p][c] =
+ *                  (float)(sums[p][c] / weights[p]) when seen.  An owned texel that is not seen takes, with `attributes`
+ *                  (float (n_verts, C): the vertex bake's output, or the vertex colours), (float)((l0 Xa + l1 Xb) + l2 Xc),
+ *                  X the attribute rows of its triangle's corners widened to double and l the texel's barycentrics of the
+ *                  Texel paragraph of gs2m_atlas.h, recomputed from cells[owner]; without `attributes`, or where its owner,
+ *                  cell or corners are out of range, fallback[c].  An empty texel takes fallback[c].
+ *   Pack           x = the fp32 value widened, clamped to [0, 1] (NaN -> 0).  base_color[p][d] = floor(255 enc(x_d) + 0.5),
+ *                  d < 3, enc the sRGB encode of gs2m_meshview.h when srgb != 0, else the identity.  With C == 5 also
+ *                  orm[p] = (255, floor(255 x_3 + 0.5), floor(255 x_4 + 0.5)): occlusion unused, roughness in G, metallic in
+ *                  B, glTF's metallicRoughnessTexture layout.  C == 3 (a plain colour bake) takes orm == NULL. */
+
+/* As gs2m_meshbake_accumulate; points, normals: double (n_texels, 3), normals may be NULL; owner: int (n_texels). */
+int gs2m_texbake_accumulate(long long n_texels, const double* points, const double* normals, const int* owner, int n_views,
+                            const double* w2c, double fx, double fy, double cx, double cy, int W, int H, const float* depth, int C,
+                            const float* maps, const float* mask, double eps, int accumulate, double* sums, double* weights,
+                            void* stream);
+
+/* The n_texels texels from row `row0` on of an atlas `width` wide (whole rows, but for the last).  triangles (n_triangles, 3),
+ * cells (n_triangles, 4) as gs2m_atlas_build wrote them and attributes (n_verts, C) are read only for unseen owned texels;
+ * attributes may be NULL.  out: float (n_texels, C); seen: unsigned char (n_texels); fallback: C HOST floats. */
+int gs2m_texbake_resolve(long long n_texels, int C, int width, int row0, const double* sums, const double* weights, double min_weight,
+                         const float* fallback, const int* owner, long long n_triangles, const int* triangles, const int* cells,
+                         long long n_verts, const float* attributes, float* out, unsigned char* seen, void* stream);
+
+/* values: float (n_texels, C), C = 3 or 5; base_color, orm: unsigned char (n_texels, 3) (see Pack). */
+int gs2m_texture_pack(long long n_texels, int C, const float* values, int srgb, unsigned char* base_color, unsigned char* orm,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -231,6 +231,12 @@ inline bool ssim_dims_ok(int B, int CH, int H, int W) {
 
 }  // namespace
 
+extern "C" int gs2m_ssim_strip_rows(int B, int CH, int H, int W) {
+    if (B < 0 || CH < 0 || H < 0 || W < 0) return GS2M_ERR_INVALID_ARG;
+    if (!ssim_dims_ok(B, CH, H, W)) return GS2M_ERR_UNSUPPORTED;  // an empty frame too: it launches nothing, so it has no strips
+    return ssim_rows(B, CH, H, W);
+}
+
 extern "C" int gs2m_ssim_forward(int B, int CH, int H, int W, float C1, float C2, const float* img1, const float* img2,
                                  float* ssim_map, float* dm_dmu1, float* dm_dsigma1_sq, float* dm_dsigma12, void* stream) {
     if (B == 0 || CH == 0 || H == 0 || W == 0) return GS2M_OK;

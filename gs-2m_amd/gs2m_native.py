@@ -118,6 +118,7 @@ SIGNATURES = {
     "gs2m_ssim_forward": (i, [i, i, i, i, f, f, p, p, p, p, p, p, s]),
     "gs2m_ssim_backward": (i, [i, i, i, i, p, p, p, p, p, p, p, s]),
     "gs2m_ssim_backward_uniform": (i, [i, i, i, i, p, p, p, f, f, p, p, p, p, s]),
+    "gs2m_ssim_strip_rows": (i, [i, i, i, i]),
     # include/gs2m_loss.h
     "gs2m_loss_workspace_bytes": (i, []),
     "gs2m_edge_gradient": (i, [i, i, p, p, p, p, s]),

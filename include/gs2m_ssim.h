@@ -33,6 +33,12 @@ int gs2m_ssim_backward_uniform(int B, int CH, int H, int W, const float* img1, c
                                float mul, float div, const float* dm_dmu1, const float* dm_dsigma1_sq,
                                const float* dm_dsigma12, float* dL_dimg1, void* stream);
 
+/* Host only, launches nothing: the output rows per strip (one wave walks one 64-column strip) that the three calls
+ * above use on a (B, CH, H, W) frame, 12 .. 45; GS2M_ERR_INVALID_ARG for a negative dimension, GS2M_ERR_UNSUPPORTED
+ * for a frame the calls above refuse (B * CH > 65535, (H + 11) / 12 > 65535) or launch nothing for (a dimension of
+ * 0).  For tests that have to know which strip height they cover. */
+int gs2m_ssim_strip_rows(int B, int CH, int H, int W);
+
 #ifdef __cplusplus
 }
 #endif

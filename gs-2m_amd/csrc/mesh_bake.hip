@@ -9,12 +9,15 @@
 // Resolve: a thread per point.  An unseen texel reads its triangle's per-vertex attributes at the chart's barycentrics
 // (atlas_layout.h), recomputed from the triangle's cell rather than stored per texel.
 // Pack: a thread per texel, two 8-bit images.
+// Normals: a thread per texel builds the tangent frame of its triangle at its interpolated normal (tangent_frame.h) and encodes
+// the baked world normal in it.
 #include <math.h>
 #include "eval_common.h"
 #include "mesh_raster.h"
 #include "bake_views.h"
 #include "atlas_layout.h"
 #include "srgb_encode.h"
+#include "tangent_frame.h"
 #include "../../include/gs2m_meshbake.h"
 
 using namespace mesh_raster;
@@ -169,6 +172,40 @@ __global__ void __launch_bounds__(256) texture_pack_kernel(long long n, int C, c
     }
 }
 
+// values: the resolved planes of the texel, the normal's three from `offset` on
+__global__ void __launch_bounds__(256) texture_normals_kernel(long long n, const int* __restrict__ owner, const double* __restrict__ tnormals,
+                                                              long long nt, const int* __restrict__ tris, const float* __restrict__ uvs,
+                                                              long long nv, const double* __restrict__ verts, int C, int offset,
+                                                              const float* __restrict__ values, unsigned char* __restrict__ normal_map,
+                                                              double* __restrict__ tangent) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double m[3] = {0.0, 0.0, 1.0};
+    const int t = owner[i];
+    if (t >= 0 && t < nt) {
+        const int id[3] = {tris[3 * (size_t)t], tris[3 * (size_t)t + 1], tris[3 * (size_t)t + 2]};
+        if (id[0] >= 0 && id[1] >= 0 && id[2] >= 0 && id[0] < nv && id[1] < nv && id[2] < nv) {
+            double P[9], uv[6], N[3], w[3];
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+#pragma unroll
+                for (int d = 0; d < 3; d++) P[3 * k + d] = verts[3 * (size_t)id[k] + d];
+                uv[2 * k] = (double)uvs[6 * (size_t)t + 2 * k], uv[2 * k + 1] = (double)uvs[6 * (size_t)t + 2 * k + 1];
+                N[k] = tnormals[3 * (size_t)i + k];
+                w[k] = (double)values[(size_t)i * C + offset + k];
+            }
+            TangentFrame F;
+            tangent_frame(P, P + 3, P + 6, uv, N, &F);
+            tangent_encode(F, w, m);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        normal_map[3 * (size_t)i + k] = tangent_byte(m[k]);
+        if (tangent) tangent[3 * (size_t)i + k] = m[k];
+    }
+}
+
 int views_status(int n_views, double fx, double fy, double cx, double cy, int W, int H, const double* w2c, const float* depth, int C,
                  const float* maps, double eps) {
     if (C < 1 || C > BAKE_CMAX || !frame_ok(n_views, W, H, fx, fy, cx, cy) || eps != eps) return GS2M_ERR_INVALID_ARG;
@@ -255,6 +292,19 @@ int gs2m_texture_pack(long long n_texels, int C, const float* values, int srgb, 
     if (n_texels == 0) return GS2M_OK;
     if (n_texels > MAX_LAUNCH) return GS2M_ERR_UNSUPPORTED;
     texture_pack_kernel<<<blocks_of(n_texels), 256, 0, (hipStream_t)stream>>>(n_texels, C, values, srgb ? 1 : 0, base_color, orm);
+    return gs2m_status(hipGetLastError());
+}
+
+int gs2m_texture_normals(long long n_texels, const int* owner, const double* tnormals, long long n_triangles, const int* triangles,
+                         const float* uvs, long long n_verts, const double* vertices, int C, int offset, const float* values,
+                         unsigned char* normal_map, double* tangent, void* stream) {
+    if (n_texels < 0 || n_triangles < 0 || n_verts < 0 || C < 3 || C > BAKE_CMAX || offset < 0 || offset > C - 3) return GS2M_ERR_INVALID_ARG;
+    if (n_texels > 0 && (!owner || !tnormals || !values || !normal_map)) return GS2M_ERR_INVALID_ARG;
+    if (n_triangles > 0 && (!triangles || !uvs || (n_verts > 0 && !vertices))) return GS2M_ERR_INVALID_ARG;
+    if (n_texels == 0) return GS2M_OK;
+    if (n_texels > MAX_LAUNCH) return GS2M_ERR_UNSUPPORTED;
+    texture_normals_kernel<<<blocks_of(n_texels), 256, 0, (hipStream_t)stream>>>(n_texels, owner, tnormals, n_triangles, triangles, uvs, n_verts,
+                                                                                 vertices, C, offset, values, normal_map, tangent);
     return gs2m_status(hipGetLastError());
 }
 

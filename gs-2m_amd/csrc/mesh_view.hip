@@ -12,10 +12,15 @@
 // G-buffer: a thread per sample runs the same per-sample code as the shade (sample_surface) and writes the world-space
 // normal and view direction and the interpolated vertex attributes, rounded once to fp32, for a shading done elsewhere; Resolve RGB:
 // a thread per output pixel applies the Resolve paragraph to such shaded samples.
+// Textured G-buffer: the same thread per sample interpolates the triangle's UVs instead of vertex attributes and
+// reads the 8-bit textures bilinearly, the bytes decoded through a 256-entry table in LDS (one pow per entry and block instead of
+// twelve per sample); the normal map is decoded in the tangent frame of tangent_frame.h at the sample's world-space normal.
 #include <math.h>
 #include "eval_common.h"
 #include "mesh_raster.h"
 #include "srgb_encode.h"
+#include "tangent_frame.h"
+#include "../../include/gs2m_atlas.h"
 #include "../../include/gs2m_meshview.h"
 
 using namespace mesh_raster;
@@ -221,6 +226,104 @@ __global__ void __launch_bounds__(256) gbuffer_kernel(long long nv, const double
     g.coverage[o] = hit ? 1 : 0;
 }
 
+struct Textures {
+    const float* uvs;  // (n_tris, 3, 2)
+    const unsigned char *base, *orm, *normal;  // (th, tw, 3); orm and normal may be null
+    int tw, th, srgb;
+};
+
+// the first tap's index along an axis of n texels for the coordinate x = u n - 0.5, kept within [-1, n] (a NaN goes to -1)
+// before it becomes an int, and the fraction from the tap's own floor
+__device__ __forceinline__ int tap_floor(double x, int n, double* t) {
+    const double f = floor(x);
+    *t = x - f;
+    return (int)(f >= -1.0 ? (f <= (double)n ? f : (double)n) : -1.0);
+}
+__device__ __forceinline__ int clamp_tap(int i, int n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }
+
+// a thread per sample of the SAMPLE frame q, as gbuffer_kernel; lut[b]: base-colour byte b decoded
+__global__ void __launch_bounds__(256) gbuffer_textured_kernel(long long nv, const double* __restrict__ verts, long long nt,
+                                                               const int* __restrict__ tris, const double* __restrict__ w2c, Frame q,
+                                                               const u64* __restrict__ vis, const double* __restrict__ normals, Textures tx,
+                                                               GBuffer g) {
+    __shared__ double lut[256];
+    lut[threadIdx.x] = decode((double)threadIdx.x / 255.0, tx.srgb);
+    __syncthreads();
+    const int v = blockIdx.y;
+    const long long pix = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long frame = (long long)q.W * q.H;
+    if (pix >= frame) return;
+    const int i = (int)(pix % q.W), j = (int)(pix / q.W);
+    const double* M = w2c + 16 * (size_t)v;
+    const size_t o = (size_t)v * frame + (size_t)pix;
+    int id[3];
+    double r[3], l[3], N[3];
+    float out[11];
+#pragma unroll
+    for (int k = 0; k < 11; k++) out[k] = 0.f;
+    const bool hit = sample_surface(nv, verts, nt, tris, M, q, normals, vis[o], i, j, id, r, l, N);
+    if (hit) {
+        const long long t = (long long)(vis[o] & 0xFFFFFFFFull);
+        double uv[6];
+#pragma unroll
+        for (int k = 0; k < 6; k++) uv[k] = (double)tx.uvs[6 * (size_t)t + k];
+        const double u = (l[0] * uv[0] + l[1] * uv[2]) + l[2] * uv[4], w = (l[0] * uv[1] + l[1] * uv[3]) + l[2] * uv[5];
+        double fx, fy;
+        const int x0 = tap_floor(u * (double)tx.tw - 0.5, tx.tw, &fx), y0 = tap_floor(w * (double)tx.th - 0.5, tx.th, &fy);
+        const double wt[4] = {(1.0 - fx) * (1.0 - fy), fx * (1.0 - fy), (1.0 - fx) * fy, fx * fy};
+        size_t tap[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) tap[k] = 3 * ((size_t)clamp_tap(y0 + k / 2, tx.th) * tx.tw + clamp_tap(x0 + k % 2, tx.tw));
+        double Nw[3], Vw[3], n[3];
+        const double back[3] = {-r[0], -r[1], -r[2]};
+        to_world_dir(M, back, Vw);
+        if (tx.normal) {
+            double P[9], m[3], rw[3];
+            load_triangle(verts, tris, t, P);
+            to_world_dir(M, N, Nw);  // before the flip: the frame is the surface's, not the view's
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                double b[4];
+#pragma unroll
+                for (int c = 0; c < 4; c++) b[c] = (double)tx.normal[tap[c] + k] / 255.0 * 2.0 - 1.0;
+                m[k] = ((b[0] * wt[0] + b[1] * wt[1]) + b[2] * wt[2]) + b[3] * wt[3];
+            }
+            TangentFrame F;
+            tangent_frame(P, P + 3, P + 6, uv, Nw, &F);
+            tangent_decode(F, m, n);
+            to_world_dir(M, r, rw);
+            if (dot3(n, rw) > 0.0) n[0] = -n[0], n[1] = -n[1], n[2] = -n[2];
+        } else {
+            if (dot3(N, r) > 0.0) N[0] = -N[0], N[1] = -N[1], N[2] = -N[2];  // towards the eye
+            to_world_dir(M, N, Nw);
+            const double nl = sqrt(dot3(Nw, Nw));
+#pragma unroll
+            for (int k = 0; k < 3; k++) n[k] = Nw[k] / nl;
+        }
+        const double vl = sqrt(dot3(Vw, Vw));
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            out[k] = (float)n[k];
+            out[3 + k] = (float)(Vw[k] / vl);
+            out[6 + k] = (float)(((lut[tx.base[tap[0] + k]] * wt[0] + lut[tx.base[tap[1] + k]] * wt[1]) + lut[tx.base[tap[2] + k]] * wt[2]) +
+                                 lut[tx.base[tap[3] + k]] * wt[3]);
+        }
+        out[9] = 1.f;
+        if (tx.orm) {
+#pragma unroll
+            for (int k = 1; k < 3; k++)
+                out[8 + k] = (float)((((double)tx.orm[tap[0] + k] / 255.0 * wt[0] + (double)tx.orm[tap[1] + k] / 255.0 * wt[1]) +
+                                      (double)tx.orm[tap[2] + k] / 255.0 * wt[2]) +
+                                     (double)tx.orm[tap[3] + k] / 255.0 * wt[3]);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; k++) g.normal[3 * o + k] = out[k], g.view_dir[3 * o + k] = out[3 + k], g.albedo[3 * o + k] = out[6 + k];
+    g.roughness[o] = out[9];
+    g.metallic[o] = out[10];
+    g.coverage[o] = hit ? 1 : 0;
+}
+
 // a thread per output pixel: the Resolve paragraph on per-sample linear RGB
 __global__ void __launch_bounds__(256) resolve_rgb_kernel(int W, int H, int ss, const float* __restrict__ rgb,
                                                           const unsigned char* __restrict__ coverage, int srgb,
@@ -347,6 +450,26 @@ int gs2m_meshview_gbuffer(long long n_verts, const double* verts, long long n_tr
     const GBuffer g{out_normal, out_view_dir, out_albedo, out_roughness, out_metallic, coverage};
     gbuffer_kernel<<<dim3(blocks_of((long long)q.W * q.H), (unsigned)n_views), 256, 0, (hipStream_t)stream>>>(
         n_verts, verts, n_tris, tris, w2c, q, (const u64*)vis, normals, albedo, roughness, metallic, g);
+    return gs2m_status(hipGetLastError());
+}
+
+int gs2m_meshview_gbuffer_textured(long long n_verts, const double* verts, long long n_tris, const int* tris, const float* uvs, int n_views,
+                                   const double* w2c, double fx, double fy, double cx, double cy, int W, int H, int ss,
+                                   const unsigned long long* vis, const double* normals, int tw, int th, const unsigned char* base_color,
+                                   int srgb, const unsigned char* orm, const unsigned char* normal_map, float* out_normal,
+                                   float* out_view_dir, float* out_albedo, float* out_roughness, float* out_metallic,
+                                   unsigned char* coverage, void* stream) {
+    if (n_verts < 0 || n_tris < 0 || !view_frame_ok(n_views, W, H, ss, fx, fy, cx, cy) || tw < 1 || th < 1) return GS2M_ERR_INVALID_ARG;
+    if (n_views > 0 && (!w2c || !vis || !out_normal || !out_view_dir || !out_albedo || !out_roughness || !out_metallic || !coverage))
+        return GS2M_ERR_INVALID_ARG;
+    if (n_tris > 0 && (!tris || !uvs || !base_color || (n_verts > 0 && !verts))) return GS2M_ERR_INVALID_ARG;
+    if (n_tris > 0x7FFFFFFFll || n_verts > 0x7FFFFFFFll || tw > GS2M_ATLAS_MAX_WIDTH || th > GS2M_ATLAS_MAX_WIDTH) return GS2M_ERR_UNSUPPORTED;
+    if (n_views == 0) return GS2M_OK;
+    const Frame q{ss * fx, ss * fy, ss * cx, ss * cy, 0.0, 0.0, W * ss, H * ss};
+    const GBuffer g{out_normal, out_view_dir, out_albedo, out_roughness, out_metallic, coverage};
+    const Textures tx{uvs, base_color, orm, normal_map, tw, th, srgb ? 1 : 0};
+    gbuffer_textured_kernel<<<dim3(blocks_of((long long)q.W * q.H), (unsigned)n_views), 256, 0, (hipStream_t)stream>>>(
+        n_verts, verts, n_tris, tris, w2c, q, (const u64*)vis, normals, tx, g);
     return gs2m_status(hipGetLastError());
 }
 

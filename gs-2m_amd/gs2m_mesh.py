@@ -11,7 +11,8 @@ box fixed at creation: `fuse_depths` derives it from the depth maps (or `bounds`
     python gs-2m_amd/gs2m_mesh.py --ply point_cloud.ply -s SCENE -o OUT [--dtu | --tnt [--scene NAME]]
 writes OUT/tsdf_mesh.ply, OUT/tsdf_post.ply and OUT/config.json as render.py --extract_mesh does; with --simplify-cell X or
 --simplify-triangles N also OUT/tsdf_simplified.ply (`simplify_mesh_gpu`: csrc/mesh_simplify.hip); with --texture-size N also
-OUT/tsdf_textured.glb, that mesh (else tsdf_post.ply) with a baked texture atlas (gs2m_mesh_texture.py).
+OUT/tsdf_textured.glb, that mesh (else tsdf_post.ply) with a baked texture atlas (gs2m_mesh_texture.py), and with --normal-map
+beside it a tangent-space normal map in that file.
 """
 import argparse
 import ctypes as C
@@ -660,9 +661,12 @@ def add_simplify_arguments(ap):
 
 
 def add_texture_arguments(ap):
-    """--texture-size N.  SUPPRESSed default: without the flag the namespace is what it was (and gs2m_mesh_texture is not imported)."""
+    """--texture-size N [--normal-map].  SUPPRESSed defaults: without the flags the namespace is what it was (and gs2m_mesh_texture
+    is not imported)."""
     ap.add_argument("--texture-size", type=int, default=argparse.SUPPRESS, metavar="N",
                     help="also write tsdf_textured.glb: the simplified (else the post-processed) mesh with an atlas at most N texels wide")
+    ap.add_argument("--normal-map", action="store_true", default=argparse.SUPPRESS,
+                    help="with --texture-size: the views' normals as a tangent-space normal map in tsdf_textured.glb")
 
 
 def simplify_keywords(a, ap=None):
@@ -701,6 +705,8 @@ def parse_args(argv=None):
     add_simplify_arguments(ap)
     add_texture_arguments(ap)
     a = ap.parse_args(argv)
+    if hasattr(a, "normal_map") and not hasattr(a, "texture_size"):
+        ap.error("--normal-map needs --texture-size")
     simplify_keywords(a, ap)
     if a.dtu and a.tnt:
         ap.error("--dtu and --tnt are two presets: choose one")
@@ -740,7 +746,7 @@ def main(argv=None):
         from gs2m_mesh_texture import texture_mesh
         source = "tsdf_simplified.ply" if simplify_keywords(a) else "tsdf_post.ply"
         texture_mesh(model, cams, read_mesh(os.path.join(a.output, source)), os.path.join(a.output, "tsdf_textured.glb"),
-                     texture_size=a.texture_size)
+                     texture_size=a.texture_size, **({"normal_map": True} if hasattr(a, "normal_map") else {}))
 
 
 if __name__ == "__main__":

@@ -107,11 +107,20 @@ def bake_vertex_attributes(vertices, triangles, w2c, fx, fy, cx, cy, maps, mask=
     return baker.finish(min_weight, fallback)
 
 
-def material_maps(gaussians, view, metallic=False):
+def unit_normal_planes(normal_map):
+    """A render's world-space normal_map (3, H, W) normalised per pixel, zero where its length is zero or not finite: the three
+    planes a normal-map bake appends to a view's maps."""
+    n = normal_map.to(torch.float32)
+    length = n.norm(dim=0, keepdim=True)
+    return torch.where((length > 0) & torch.isfinite(length), n / length, torch.zeros_like(n))
+
+
+def material_maps(gaussians, view, metallic=False, normal=False):
     """One view's five material planes and its mask, as gs2m_render.py stores them before the 8-bit packing: the clamped albedo,
     and the roughness and metallic shading_inputs_fused hands to the shading (with `metallic` the model's blended metallic map,
     else the estimate from the roughness that gs2m_render.py stores under metallic/).
-    -> (maps (5, H, W) float32, mask (H, W) float32) on the device."""
+    normal: three more planes, unit_normal_planes of the render's normal_map (gs2m_mesh_texture.bake_textures(normal_map=True)).
+    -> (maps (5 or 8, H, W) float32, mask (H, W) float32) on the device."""
     from gaussian_renderer import render
     from gs2m_scene import PipelineParams
     from pbr import shading_inputs_fused
@@ -121,10 +130,12 @@ def material_maps(gaussians, view, metallic=False):
         h, w = pkg["normal_map"].shape[-2:]
         _, albedo, rough, metal = shading_inputs_fused(pkg["normal_map"], pkg["albedo_map"], pkg["roughness_map"], pkg["alpha_map"],
                                                        pkg["metallic_map"] if metallic else None, 0.04, 1.0)
-        maps = torch.empty((5, h, w), dtype=torch.float32, device=dev)
+        maps = torch.empty((8 if normal else 5, h, w), dtype=torch.float32, device=dev)
         maps[0:3] = pkg["albedo_map"].clamp(0.0, 1.0)
         maps[3] = rough.reshape(h, w)
         maps[4] = metal.reshape(h, w)
+        if normal:
+            maps[5:8] = unit_normal_planes(pkg["normal_map"])
         return maps, pkg["normal_mask"].to(torch.float32).reshape(h, w)
 
 

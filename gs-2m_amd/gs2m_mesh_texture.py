@@ -9,7 +9,10 @@ written with the unwelded mesh as one .glb (`export_glb`, `write_glb`; `read_glb
 files runs on device tensors owned here; there is no CPU path.
 
     python gs-2m_amd/gs2m_mesh_texture.py --ply point_cloud.ply -s SCENE --mesh tsdf_simplified.ply -o asset.glb \\
-        (--texture-size N | --density D) [--metallic] [--rgb] [--linear] [--device-png] [--textures-dir DIR]
+        (--texture-size N | --density D) [--metallic] [--rgb] [--linear] [--normal-map] [--device-png] [--textures-dir DIR]
+
+With --normal-map the views' world-space normals are baked beside the materials and encoded per texel in the tangent frame of its
+triangle (`pack_normal_map`; csrc/tangent_frame.h): the .glb then carries a TANGENT accessor and a normalTexture.
 """
 import argparse
 import ctypes as C
@@ -222,25 +225,39 @@ def bake_texel_attributes(atlas, w2c, fx, fy, cx, cy, maps, mask=None, eps=EPS, 
     return baker.finish(min_weight, fallback, attributes)
 
 
-def rgb_maps(gaussians, view):
-    """One view's plain render and its foreground (alpha >= 0.5) -> (maps (3, H, W) float32, mask (H, W) float32)"""
+def rgb_maps(gaussians, view, normal=False):
+    """One view's plain render and its foreground (alpha >= 0.5) -> (maps (3, H, W) float32, mask (H, W) float32); normal: three
+    more planes, gs2m_mesh_bake.unit_normal_planes of the render's normal_map"""
     from gaussian_renderer import render
     from gs2m_scene import PipelineParams
     dev = gaussians.get_xyz.device
     with torch.no_grad():
         pkg = render(view, gaussians, PipelineParams(), torch.zeros(3, device=dev))
         rgb = pkg["render"].clamp(0.0, 1.0).to(torch.float32)
+        if normal:
+            from gs2m_mesh_bake import unit_normal_planes
+            rgb = torch.cat([rgb, unit_normal_planes(pkg["normal_map"])])
         return rgb.contiguous(), (pkg["alpha_map"].reshape(rgb.shape[-2:]) >= 0.5).to(torch.float32)
 
 
 def bake_textures(gaussians, views, mesh, atlas, metallic=False, rgb=False, eps=EPS, use_normals=True, view_batch=None,
-                  min_weight=MIN_WEIGHT, fallback=None, attributes=None, near=NEAR, far=FAR):
+                  min_weight=MIN_WEIGHT, fallback=None, attributes=None, near=NEAR, far=FAR, normal_map=False):
     """The model's albedo, roughness and metallic (gs2m_mesh_bake.material_maps), or with rgb=True its plain render, in the texels
     of `atlas` (build_atlas(mesh, ...)).  Views are baked in runs of up to `view_batch` that share size and intrinsics, with the
     principal-point shift of bake_materials.  Texels no view reached take `attributes` (V, C) interpolated, else `fallback`.
-    -> (values (H, W, 5 or 3) float32, seen (H, W) bool, weights (H, W) float64)"""
+    normal_map: three more planes, the views' unit world-space normals averaged like the others (for pack_normal_map; the mean is
+    not unit); `attributes` and `fallback` keep their 5 or 3 columns and are padded with zeros there, so that a texel no view
+    reached carries a zero normal and encodes flat.
+    -> (values (H, W, 5 or 3, + 3 with normal_map) float32, seen (H, W) bool, weights (H, W) float64)"""
     from gs2m_mesh_bake import material_maps
-    channels = 3 if rgb else 5
+    materials = 3 if rgb else 5
+    channels = materials + (3 if normal_map else 0)
+    fallback = list(FALLBACK[:materials] if fallback is None else fallback)
+    if normal_map:
+        fallback = fallback + [0.0, 0.0, 0.0]
+        if attributes is not None:
+            att = N.f32(attributes, "attributes", (len(atlas.vertices), materials), who="bake_textures")
+            attributes = torch.cat([att, torch.zeros((len(att), 3), dtype=torch.float32, device=att.device)], 1).contiguous()
     baker = TextureBaker(atlas, channels, eps, use_normals, near, far)
     batch = max(1, int(view_batch or VIEW_BATCH))
     run, key = [], None
@@ -256,16 +273,22 @@ def bake_textures(gaussians, views, mesh, atlas, metallic=False, rgb=False, eps=
         if k != key or len(run) == batch:
             flush()
             key = k
-        maps, mask = rgb_maps(gaussians, view) if rgb else material_maps(gaussians, view, metallic)
+        if normal_map:
+            maps, mask = rgb_maps(gaussians, view, True) if rgb else material_maps(gaussians, view, metallic, True)
+        else:
+            maps, mask = rgb_maps(gaussians, view) if rgb else material_maps(gaussians, view, metallic)
         run.append((view.world_view_transform.transpose(0, 1).to(torch.float64), maps, mask))
     flush()
-    return baker.finish(min_weight, FALLBACK[:channels] if fallback is None else fallback, attributes)
+    return baker.finish(min_weight, fallback, attributes)
 
 
 def pack_textures(values, srgb=True):
     """values (H, W, 5) or (H, W, 3) float32 -> (base colour (H, W, 3) uint8, sRGB-encoded unless srgb=False; ORM (H, W, 3) uint8:
-    255, roughness, metallic -- None for three channels)"""
+    255, roughness, metallic -- None for three channels).  The three normal planes of a bake with normal_map=True (6 or 8 channels)
+    are left to pack_normal_map."""
     x = N.f32(values, "values", who="pack_textures")
+    if x.dim() == 3 and x.shape[2] in (6, 8):  # a bake with normal planes: they are pack_normal_map's
+        x = x[..., :x.shape[2] - 3].contiguous()
     if x.dim() != 3 or x.shape[2] not in (3, 5):
         raise RuntimeError(f"pack_textures: `values` must have shape (H, W, 3) or (H, W, 5), got {tuple(x.shape)}")
     H, W, ch = x.shape
@@ -273,6 +296,36 @@ def pack_textures(values, srgb=True):
     orm = torch.empty((H, W, 3), dtype=torch.uint8, device=x.device) if ch == 5 else None
     N.launch("gs2m_texture_pack", x.device, H * W, ch, _ptr(x), int(bool(srgb)), _ptr(base), _ptr(orm))
     return base, orm
+
+
+def texel_normals(atlas):
+    """The texels' interpolated normals as the bake sees them (TextureBaker with use_normals) -> (owner (H, W) int32, normals
+    (H, W, 3) float64)"""
+    vn = None
+    if len(atlas.triangles):
+        from gs2m_mesh_view import vertex_normals
+        vn = vertex_normals(atlas.vertices, atlas.triangles)[0]
+    owner, _, _, tn = atlas_texels(atlas, vn)
+    return owner, tn
+
+
+def pack_normal_map(atlas, values, offset=None, return_tangent=False):
+    """values (H, W, C) float32 of a bake of `atlas` whose planes offset .. offset + 2 (default: the last three) hold the baked
+    world-space normal -> the tangent-space normal map (H, W, 3) uint8 (include/gs2m_meshbake.h, the Normals paragraph: each
+    texel's frame is built at its interpolated vertex normal); return_tangent: also the (H, W, 3) float64 values before packing."""
+    who = "pack_normal_map"
+    x = N.f32(values, "values", who=who)
+    if x.dim() != 3 or not 3 <= x.shape[2] <= MAX_CHANNELS or tuple(x.shape[:2]) != (atlas.height, atlas.width):
+        raise RuntimeError(f"{who}: `values` must have shape ({atlas.height}, {atlas.width}, 3 .. {MAX_CHANNELS}), got {tuple(x.shape)}")
+    ch = int(x.shape[2])
+    offset = ch - 3 if offset is None else int(offset)
+    owner, tn = texel_normals(atlas)
+    dev = x.device
+    out = torch.empty((atlas.height, atlas.width, 3), dtype=torch.uint8, device=dev)
+    tangent = torch.empty((atlas.height, atlas.width, 3), dtype=torch.float64, device=dev) if return_tangent else None
+    N.launch("gs2m_texture_normals", dev, atlas.height * atlas.width, _ptr(owner), _ptr(tn), len(atlas.triangles), _ptr(atlas.triangles),
+             _ptr(atlas.uvs), len(atlas.vertices), _ptr(atlas.vertices), ch, offset, _ptr(x), _ptr(out), _ptr(tangent))
+    return (out, tangent) if return_tangent else out
 
 
 # ---- glTF 2.0 binary -------------------------------------------------------------------------------------------------------
@@ -285,10 +338,12 @@ def _pad(b, fill):
     return b + fill * (-len(b) % 4)
 
 
-def write_glb(file, positions, normals, uvs, indices, images):
+def write_glb(file, positions, normals, uvs, indices, images, tangents=None, normal_image=None):
     """One mesh, one primitive: positions, normals (n, 3) and uvs (n, 2) float32, indices (m,) uint32, images = the PNG files
     (bytes) of the base-colour texture and, optionally, of the metallic-roughness texture, embedded as buffer views.  Buffer
-    views and chunks are aligned to 4 bytes; POSITION carries min / max.  -> the bytes written."""
+    views and chunks are aligned to 4 bytes; POSITION carries min / max.  tangents (n, 4) float32 and normal_image (a PNG file),
+    both or neither: the TANGENT accessor (xyz and the handedness w) and the material's normalTexture; they come after everything
+    else in the buffer, and without them the file is byte for byte what it was before they existed.  -> the bytes written."""
     pos = np.ascontiguousarray(positions, "<f4").reshape(-1, 3)
     nrm = np.ascontiguousarray(normals, "<f4").reshape(-1, 3)
     uv = np.ascontiguousarray(uvs, "<f4").reshape(-1, 2)
@@ -298,11 +353,18 @@ def write_glb(file, positions, normals, uvs, indices, images):
         raise ValueError("write_glb: n positions, normals and uvs (n > 0), 3 m indices and one or two images")
     if int(idx.max()) >= len(pos):
         raise ValueError("write_glb: an index names no vertex")
+    if (tangents is None) != (normal_image is None):
+        raise ValueError("write_glb: `tangents` and `normal_image` come together")
     blobs = [pos.tobytes(), nrm.tobytes(), uv.tobytes(), idx.tobytes()] + images
+    if tangents is not None:
+        tan = np.ascontiguousarray(tangents, "<f4").reshape(-1, 4)
+        if len(tan) != len(pos):
+            raise ValueError("write_glb: one tangent per vertex")
+        blobs += [tan.tobytes(), bytes(normal_image)]
     views, body = [], b""
     for k, b in enumerate(blobs):
         view = {"buffer": 0, "byteOffset": len(body), "byteLength": len(b)}
-        if k < 4:
+        if k < 4 or (tangents is not None and k == len(blobs) - 2):
             view["target"] = _ELEMENT_BUFFER if k == 3 else _ARRAY_BUFFER
         views.append(view)
         body = _pad(body + b, b"\0")
@@ -326,6 +388,13 @@ def write_glb(file, positions, normals, uvs, indices, images):
         "images": [{"bufferView": 4 + k, "mimeType": "image/png"} for k in range(len(images))],
         "accessors": accessors, "bufferViews": views, "buffers": [{"byteLength": len(body)}],
     }
+    if tangents is not None:
+        n = len(images)
+        accessors.append({"bufferView": 4 + n, "componentType": _FLOAT, "count": len(tan), "type": "VEC4"})
+        doc["meshes"][0]["primitives"][0]["attributes"]["TANGENT"] = 4
+        doc["materials"][0]["normalTexture"] = {"index": n}
+        doc["textures"].append({"sampler": 0, "source": n})
+        doc["images"].append({"bufferView": 5 + n, "mimeType": "image/png"})
     text = _pad(json.dumps(doc, separators=(",", ":")).encode("utf-8"), b" ")
     total = 12 + 8 + len(text) + 8 + len(body)
     data = struct.pack("<III", GLB_MAGIC, 2, total) + struct.pack("<II", len(text), GLB_JSON) + text + struct.pack("<II", len(body), GLB_BIN) + body
@@ -336,7 +405,8 @@ def write_glb(file, positions, normals, uvs, indices, images):
 
 def read_glb(file):
     """What write_glb wrote -> dict(positions, normals (n, 3) float32, uvs (n, 2) float32, indices (m,) uint32, images: list of
-    PNG files as bytes, json: the document).  ValueError for anything but a version-2 .glb of one mesh with one primitive."""
+    PNG files as bytes -- the base colour and, where the material has one, the metallic-roughness texture --, tangents (n, 4)
+    float32 or None, normal_image: the normal map's PNG file or None, json: the document).  ValueError for anything but a version-2 .glb of one mesh with one primitive."""
     with open(str(file), "rb") as f:
         data = f.read()
     if len(data) < 20 or struct.unpack_from("<III", data, 0)[:2] != (GLB_MAGIC, 2) or struct.unpack_from("<I", data, 8)[0] != len(data):
@@ -358,15 +428,23 @@ def read_glb(file):
 
     def accessor(k, dtype, cols):
         a = doc["accessors"][k]
-        if a["componentType"] != {"<f4": _FLOAT, "<u4": _UINT}[dtype] or a["type"] != {1: "SCALAR", 2: "VEC2", 3: "VEC3"}[cols]:
+        if a["componentType"] != {"<f4": _FLOAT, "<u4": _UINT}[dtype] or a["type"] != {1: "SCALAR", 2: "VEC2", 3: "VEC3", 4: "VEC4"}[cols]:
             raise ValueError(f"{file}: accessor {k} is not what write_glb writes")
         x = np.frombuffer(view(a["bufferView"]), dtype, a["count"] * cols, a.get("byteOffset", 0))
         return x.reshape(-1, cols) if cols > 1 else x
 
     prim = doc["meshes"][0]["primitives"][0]
     att = prim["attributes"]
+    images = [view(i["bufferView"]) for i in doc.get("images", ())]
+    normal_image = None
+    material = doc.get("materials", [{}])[prim.get("material", 0)]
+    if "normalTexture" in material:
+        source = doc["textures"][material["normalTexture"]["index"]]["source"]
+        normal_image = images[source]
+        images = [b for k, b in enumerate(images) if k != source]
     return dict(positions=accessor(att["POSITION"], "<f4", 3), normals=accessor(att["NORMAL"], "<f4", 3), uvs=accessor(att["TEXCOORD_0"], "<f4", 2),
-                indices=accessor(prim["indices"], "<u4", 1), images=[view(i["bufferView"]) for i in doc.get("images", ())], json=doc)
+                indices=accessor(prim["indices"], "<u4", 1), images=images, tangents=accessor(att["TANGENT"], "<f4", 4) if "TANGENT" in att else None,
+                normal_image=normal_image, json=doc)
 
 
 def decode_png(data):
@@ -390,10 +468,8 @@ def encode_png(images, device_png=False):
     return out
 
 
-def unwelded(atlas):
-    """The primitive of the export: 3 F vertices, each triangle with corners of its own -> (positions (3F, 3) float32, unit normals
-    (3F, 3) float32: the smooth vertex normals, the face normal where there is none, +z for a zero-area triangle; uvs (3F, 2)
-    float32; indices (3F,) uint32), numpy."""
+def _corner_normals(atlas):
+    """-> (p (F, 3, 3) the corners, n (F, 3, 3) their unit normals as `unwelded` documents them), float64 device tensors"""
     from gs2m_mesh_view import vertex_normals
     f = atlas.triangles.long()
     p = atlas.vertices[f]                                  # (F, 3, 3)
@@ -402,21 +478,56 @@ def unwelded(atlas):
     n = torch.where((vn != 0).any(2, keepdim=True) & torch.isfinite(vn).all(2, keepdim=True), vn, face)
     length = n.norm(dim=2, keepdim=True)
     n = torch.where((length > 0) & torch.isfinite(length), n / length, torch.tensor([0.0, 0.0, 1.0], dtype=n.dtype, device=n.device))
+    return p, n
+
+
+def unwelded(atlas):
+    """The primitive of the export: 3 F vertices, each triangle with corners of its own -> (positions (3F, 3) float32, unit normals
+    (3F, 3) float32: the smooth vertex normals, the face normal where there is none, +z for a zero-area triangle; uvs (3F, 2)
+    float32; indices (3F,) uint32), numpy."""
+    p, n = _corner_normals(atlas)
     return (p.reshape(-1, 3).float().cpu().numpy(), n.reshape(-1, 3).float().cpu().numpy(), atlas.uvs.reshape(-1, 2).cpu().numpy(),
-            np.arange(3 * len(f), dtype=np.uint32))
+            np.arange(3 * len(p), dtype=np.uint32))
 
 
-def export_glb(file, atlas, base_color, orm=None, device_png=False, textures_dir=None):
-    """The mesh of `atlas` with its textures (pack_textures's images) as one .glb; textures_dir: also the two PNG files."""
+def unwelded_tangents(atlas):
+    """The TANGENT accessor of `unwelded`'s vertices: per corner the T of the Tangent frame paragraph (include/gs2m_meshbake.h)
+    of its triangle at that corner's own normal, and the handedness w = -1 -> (3F, 4) float32 numpy.  A corner without a frame (a
+    zero-area triangle) gets (1, 0, 0, -1).  The frame replaces a normal that opposes its face by the face's: there T is
+    perpendicular to the face normal, not to the NORMAL accessor's."""
+    p, n = _corner_normals(atlas)
+    uv = atlas.uvs.to(torch.float64)
+    dot = lambda a, b: ((a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2])[..., None]
+    e1, e2 = p[:, 1] - p[:, 0], p[:, 2] - p[:, 0]
+    d1, d2 = uv[:, 1] - uv[:, 0], uv[:, 2] - uv[:, 0]
+    det = (d1[:, 0] * d2[:, 1] - d2[:, 0] * d1[:, 1])[:, None]
+    du = ((e1 * d2[:, 1:2] - e2 * d1[:, 1:2]) / det)[:, None]            # (F, 1, 3)
+    nf = torch.linalg.cross(e1, e2)
+    uf = (nf / dot(nf, nf).sqrt())[:, None]
+    n = torch.where(dot(n, nf[:, None]) > 0, n, uf.expand(-1, 3, -1))
+    t = du - n * dot(n, du)
+    t = t / dot(t, t).sqrt()
+    ok = torch.isfinite(t).all(2, keepdim=True) & (det != 0)[:, None]
+    t = torch.where(ok, t, torch.tensor([1.0, 0.0, 0.0], dtype=t.dtype, device=t.device))
+    out = torch.cat([t, torch.full_like(t[..., :1], -1.0)], 2)
+    return out.reshape(-1, 4).float().cpu().numpy()
+
+
+def export_glb(file, atlas, base_color, orm=None, device_png=False, textures_dir=None, normal_map=None):
+    """The mesh of `atlas` with its textures (pack_textures's images, and pack_normal_map's as `normal_map`: then with tangents)
+    as one .glb; textures_dir: also the PNG files."""
     if len(atlas.triangles) == 0:
         raise RuntimeError("export_glb: the mesh has no triangle")
-    pngs = encode_png([base_color] + ([orm] if orm is not None else []), device_png)
+    pngs = encode_png([base_color] + ([orm] if orm is not None else []) + ([normal_map] if normal_map is not None else []), device_png)
+    names = ["base_color.png"] + (["metallic_roughness.png"] if orm is not None else []) + (["normal.png"] if normal_map is not None else [])
     if textures_dir:
         os.makedirs(textures_dir, exist_ok=True)
-        for name, b in zip(("base_color.png", "metallic_roughness.png"), pngs):
+        for name, b in zip(names, pngs):
             with open(os.path.join(textures_dir, name), "wb") as f:
                 f.write(b)
-    return write_glb(file, *unwelded(atlas), pngs)
+    if normal_map is None:
+        return write_glb(file, *unwelded(atlas), pngs)
+    return write_glb(file, *unwelded(atlas), pngs[:-1], tangents=unwelded_tangents(atlas), normal_image=pngs[-1])
 
 
 # ---- command line ------------------------------------------------------------------------------------------------------------
@@ -433,7 +544,10 @@ def parser():
     ap.add_argument("--metallic", action="store_true", help="the model's metallic map (default: estimated from the roughness)")
     ap.add_argument("--rgb", action="store_true", help="bake the plain render into a base colour only (a model without materials)")
     ap.add_argument("--linear", action="store_true", help="store the base colour without the sRGB transfer")
-    ap.add_argument("--textures-dir", default=None, metavar="DIR", help="also write base_color.png and metallic_roughness.png there")
+    ap.add_argument("--normal-map", action="store_true",
+                    help="also bake the views' normals into a tangent-space normal map: TANGENT and normalTexture in the .glb")
+    ap.add_argument("--textures-dir", default=None, metavar="DIR",
+                    help="also write base_color.png and metallic_roughness.png (with --normal-map: normal.png) there")
     ap.add_argument("--blender", action="store_true")
     ap.add_argument("--split", choices=("train", "test"), default="train")
     ap.add_argument("--resolution", "-r", type=int, default=1)
@@ -464,11 +578,11 @@ def read_source_mesh(file):
 
 
 def texture_mesh(model, cams, mesh, output, density=None, texture_size=None, metallic=False, rgb=False, linear=False, device_png=False,
-                 textures_dir=None, eps=EPS, min_weight=MIN_WEIGHT, view_batch=None, vertex_values=None):
+                 textures_dir=None, eps=EPS, min_weight=MIN_WEIGHT, view_batch=None, vertex_values=None, normal_map=False):
     """Atlas, bake, pack and export in one call -> dict(out, width, height, density, n_views, n_texels, n_seen).  Texels no view
     reached interpolate `vertex_values` (V, 5): albedo rgb, roughness, metallic, the vertex bake's output; without them the mesh's
     vertex colours, taken as they are for the linear albedo (a PLY says nothing of their transfer), with roughness 1 and metallic 0;
-    a mesh without colours leaves the fallback."""
+    a mesh without colours leaves the fallback.  normal_map: the views' normals too, as a tangent-space normal map."""
     atlas = build_atlas(mesh, density=density, texture_size=texture_size, device=model.get_xyz.device)
     colours = getattr(mesh, "vertex_colors", None)
     attributes = None
@@ -479,9 +593,10 @@ def texture_mesh(model, cams, mesh, output, density=None, texture_size=None, met
         c = torch.as_tensor(np.asarray(colours, np.float32)).to(atlas.vertices.device).reshape(-1, 3)
         attributes = c if rgb else torch.cat([c, torch.tensor(FALLBACK[3:], device=c.device).expand(len(c), 2)], 1).contiguous()
     values, seen, _ = bake_textures(model, cams, mesh, atlas, metallic=metallic, rgb=rgb, eps=eps, view_batch=view_batch,
-                                    min_weight=min_weight, attributes=attributes)
+                                    min_weight=min_weight, attributes=attributes, **({"normal_map": True} if normal_map else {}))
     base, orm = pack_textures(values, srgb=not linear)
-    export_glb(output, atlas, base, orm, device_png=device_png, textures_dir=textures_dir)
+    extra = {"normal_map": pack_normal_map(atlas, values)} if normal_map else {}
+    export_glb(output, atlas, base, orm, device_png=device_png, textures_dir=textures_dir, **extra)
     print(f"[>] {len(cams)} views: atlas {atlas.width} x {atlas.height} at {atlas.density:.6g} texels per unit, "
           f"{int(seen.sum())} of {atlas.width * atlas.height} texels seen -> {output}")
     return {"out": str(output), "width": atlas.width, "height": atlas.height, "density": atlas.density, "n_views": len(cams),
@@ -505,7 +620,7 @@ def main(argv=None):
     mesh, vertex_values = read_source_mesh(a.mesh)
     return texture_mesh(model, cams, mesh, a.output, vertex_values=vertex_values, density=a.density, texture_size=a.texture_size, metallic=a.metallic, rgb=a.rgb,
                         linear=a.linear, device_png=a.device_png, textures_dir=a.textures_dir, eps=a.eps, min_weight=a.min_weight,
-                        view_batch=a.view_batch)
+                        view_batch=a.view_batch, normal_map=a.normal_map)
 
 
 if __name__ == "__main__":

@@ -8,7 +8,11 @@ encoded as straight-alpha sRGB bytes.  Everything is fp64 on device tensors owne
     python gs-2m_amd/gs2m_mesh_view.py --ply-path M.ply --cameras MODEL/cameras.json --rendering --still --animation
     python gs-2m_amd/gs2m_mesh_view.py --ply-path M.ply -s SCENE -r 2 --rendering --shading smooth --colour vertex
     python gs-2m_amd/gs2m_mesh_view.py --ply-path MATERIAL.ply -s SCENE --rendering --colour pbr --envmap studio.hdr [--background env]
-(the last: a material mesh of gs2m_mesh_bake.py under an environment map)
+    python gs-2m_amd/gs2m_mesh_view.py --glb ASSET.glb -s SCENE --rendering --colour texture [--shading smooth]
+    python gs-2m_amd/gs2m_mesh_view.py --glb ASSET.glb -s SCENE --rendering --colour pbr --envmap studio.hdr
+(the third: a material mesh of gs2m_mesh_bake.py under an environment map; the last two: the textured .glb of
+gs2m_mesh_texture.py, its base colour under the headlight or its materials under an environment map, with its normal map where
+it has one)
 write views/<stem>.png, still.png, frames/000.png .. 119.png, anim.gif and anim.webp under --out-dir (default: visual/ beside the
 mesh's directory).
 """
@@ -142,6 +146,65 @@ def mesh_gbuffer(vertices, triangles, w2c, fx, fy, cx, cy, H, W, vis, albedo, ro
     return g
 
 
+def _image(t, name, who, dev, like=None):
+    """a (th, tw, 3) uint8 texture on `dev`, of the size of `like` when given"""
+    if not torch.is_tensor(t) or t.device != dev or t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3 or t.numel() == 0:
+        raise RuntimeError(f"{who}: `{name}` must be a (th, tw, 3) uint8 tensor on {dev}")
+    if like is not None and t.shape != like.shape:
+        raise RuntimeError(f"{who}: `{name}` is {tuple(t.shape)}, the base colour {tuple(like.shape)}")
+    return t.contiguous()
+
+
+def mesh_gbuffer_textured(vertices, triangles, uvs, w2c, fx, fy, cx, cy, H, W, vis, base_color, orm=None, normal_map=None, srgb=True,
+                          ss=1, normals=None):
+    """mesh_gbuffer with the materials read from textures (include/gs2m_meshview.h, the Textured paragraph): uvs (F, 3, 2) float32
+    per triangle corner, v from the top row; base_color, orm, normal_map: (th, tw, 3) uint8 device tensors of one size, orm and
+    normal_map optional (roughness 1 and metallic 0; the geometric normal).  srgb: the base colour is sRGB-encoded and is decoded.
+    normal_map is tangent-space, in the frame gs2m_mesh_texture.pack_normal_map encodes in.  -> the same dict."""
+    who = "mesh_gbuffer_textured"
+    v, f, m = _mesh_args(vertices, triangles, w2c, who)
+    H, W, ss = _check_frame(H, W, ss, who)
+    dev, n = v.device, len(m)
+    uv = N.f32(uvs, "uvs", (len(f), 3, 2), who=who)
+    base = _image(base_color, "base_color", who, dev)
+    o = None if orm is None else _image(orm, "orm", who, dev, base)
+    nm = None if normal_map is None else _image(normal_map, "normal_map", who, dev, base)
+    if not torch.is_tensor(vis) or vis.device != dev or vis.dtype != torch.int64 or not vis.is_contiguous() or vis.numel() != n * H * W * ss * ss:
+        raise RuntimeError(f"{who}: `vis` must be the contiguous int64 visibility buffer of {n} views of {W * ss} x {H * ss} samples on {dev}")
+    nrm = None if normals is None else _on_device(normals, "normals", who, torch.float64, (3,))
+    shape = (n, H * ss, W * ss)
+    g = {name: torch.empty(shape + (c,), dtype=torch.float32, device=dev)
+         for name, c in (("normal", 3), ("view_dir", 3), ("albedo", 3), ("roughness", 1), ("metallic", 1))}
+    g["coverage"] = torch.empty(shape, dtype=torch.uint8, device=dev)
+    N.launch("gs2m_meshview_gbuffer_textured", dev, len(v), _ptr(v), len(f), _ptr(f), _ptr(uv), n, _ptr(m), float(fx), float(fy), float(cx),
+             float(cy), W, H, ss, _ptr(vis), _ptr(nrm), int(base.shape[1]), int(base.shape[0]), _ptr(base), 1 if srgb else 0, _ptr(o), _ptr(nm),
+             _ptr(g["normal"]), _ptr(g["view_dir"]), _ptr(g["albedo"]), _ptr(g["roughness"]), _ptr(g["metallic"]), _ptr(g["coverage"]))
+    return g
+
+
+def shade_views_textured(vertices, triangles, uvs, w2c, fx, fy, cx, cy, H, W, base_color, normal_map=None, texture_srgb=True, ss=2,
+                         normals=None, ambient=AMBIENT, diffuse=DIFFUSE, srgb=True, view_batch=None, near=NEAR, far=FAR):
+    """shade_views for a textured mesh: the headlight Lambert shade, ambient + diffuse |dot(normal, view_dir)|, on the texture's
+    base colour, per sample of the textured G-buffer and resolved by resolve_rgb -> (n_views, H, W, 4) uint8, straight alpha.
+    normals: (V, 3) fp64 vertex normals for smooth shading, None for flat."""
+    who = "shade_views_textured"
+    v, f, m = _mesh_args(vertices, triangles, w2c, who)
+    H, W, ss = _check_frame(H, W, ss, who)
+    dev, n = v.device, len(m)
+    per_view = (8 + 4 * 14 + 1) * H * W * ss * ss
+    batch = int(view_batch) if view_batch else max(1, VIS_BUDGET // max(per_view, 1))
+    batch = max(1, min(batch, max(n, 1)))
+    rgba = torch.empty((n, H, W, 4), dtype=torch.uint8, device=dev)
+    buf = torch.empty(batch * H * W * ss * ss, dtype=torch.int64, device=dev)
+    for k in range(0, n, batch):
+        part = m[k:k + batch]
+        vis = visibility_buffer(v, f, part, fx, fy, cx, cy, H, W, ss, near, far, out=buf)
+        g = mesh_gbuffer_textured(v, f, uvs, part, fx, fy, cx, cy, H, W, vis.reshape(-1), base_color, None, normal_map, texture_srgb, ss, normals)
+        cos = (g["normal"] * g["view_dir"]).sum(-1, keepdim=True).abs()
+        rgba[k:k + batch] = resolve_rgb(g["albedo"] * (float(ambient) + float(diffuse) * cos), g["coverage"], ss, srgb)
+    return rgba
+
+
 def resolve_rgb(rgb, coverage, ss, srgb=False, background=None):
     """Per-sample linear RGB (n, H ss, W ss, 3) float32 and coverage bytes (n, H ss, W ss) -> (n, H, W, 4) uint8: the mean over a
     pixel's covered samples, optionally sRGB-encoded, straight alpha = the covered share.  background: (n, H, W, 3) float32 in the
@@ -171,13 +234,14 @@ def pixel_view_dirs(w2c, fx, fy, cx, cy, H, W):
 
 
 def shade_views_pbr(vertices, triangles, w2c, fx, fy, cx, cy, H, W, light, albedo, roughness, metallic, ss=2, shading="smooth",
-                    gamma=False, background="none", view_batch=None, near=NEAR, far=FAR):
+                    gamma=False, background="none", view_batch=None, near=NEAR, far=FAR, gbuffer=None):
     """Views of a material mesh under an environment light: (n_views, H, W, 4) uint8 on the device.  light: anything with
     `.cubemap` (a CubemapLight) and `.brdf_lut`, e.g. gs2m_envmap.EnvLight; albedo (V, 3), roughness (V,), metallic (V,): float32
     vertex attributes.  Per batch of views: the visibility buffer, the G-buffer of its samples, the project's fused split-sum
     shading (pbr_shading_fused) on every sample, and the resolve over ss x ss samples; gamma: sRGB-encode the resolved colour.
     background "none": straight alpha = the covered share of the pixel; "env": the environment along the pixel's ray
-    (gs2m_relight.environment_behind) under the alpha, which is then 255."""
+    (gs2m_relight.environment_behind) under the alpha, which is then 255.  gbuffer: a function (views, vis, normals) -> the
+    G-buffer dict that takes mesh_gbuffer's place, e.g. around mesh_gbuffer_textured; the three vertex arrays are then unused."""
     from pbr import pbr_shading_fused
     who = "shade_views_pbr"
     v, f, m = _mesh_args(vertices, triangles, w2c, who)
@@ -198,7 +262,10 @@ def shade_views_pbr(vertices, triangles, w2c, fx, fy, cx, cy, H, W, light, albed
         for k in range(0, n, batch):
             part = m[k:k + batch]
             vis = visibility_buffer(v, f, part, fx, fy, cx, cy, H, W, ss, near, far, out=buf)
-            g = mesh_gbuffer(v, f, part, fx, fy, cx, cy, H, W, vis.reshape(-1), albedo, roughness, metallic, ss, normals)
+            if gbuffer is not None:
+                g = gbuffer(part, vis.reshape(-1), normals)
+            else:
+                g = mesh_gbuffer(v, f, part, fx, fy, cx, cy, H, W, vis.reshape(-1), albedo, roughness, metallic, ss, normals)
             rgb = pbr_shading_fused(light.cubemap, g["normal"], g["view_dir"], g["albedo"], g["roughness"], metallic=g["metallic"],
                                     brdf_lut=light.brdf_lut, gamma=False)["render_rgb"]
             bg = None
@@ -295,13 +362,52 @@ def write_webp(frames, path, fps=FPS):
     return True
 
 
+def read_textured_mesh(file, device):
+    """A .glb of gs2m_mesh_texture.write_glb as device tensors -> dict(vertices (V, 3) float64, triangles (F, 3) int32, uvs
+    (F, 3, 2) float32, normals (V, 3) float64: the NORMAL accessor, base_color, orm, normal_map: (th, tw, 3) uint8, the last two
+    None where the file has none).  The PNGs are decoded on the host (gs2m_mesh_texture.decode_png)."""
+    import gs2m_mesh_texture as MT
+    g = MT.read_glb(file)
+    idx = np.asarray(g["indices"], np.int64).reshape(-1, 3)
+
+    def image(data):
+        px = MT.decode_png(data)
+        if px.ndim != 3 or px.shape[2] < 3 or px.dtype != np.uint8:
+            raise ValueError(f"{file}: a texture is not 8-bit RGB")
+        return torch.as_tensor(np.ascontiguousarray(px[..., :3])).to(device)
+
+    images = [image(b) for b in g["images"]]
+    if not images:
+        raise ValueError(f"{file}: no base-colour texture")
+    return dict(vertices=torch.as_tensor(np.asarray(g["positions"], np.float64)).to(device),
+                triangles=torch.as_tensor(idx.astype(np.int32)).to(device),
+                uvs=torch.as_tensor(np.ascontiguousarray(np.asarray(g["uvs"], np.float32)[idx])).to(device),
+                normals=torch.as_tensor(np.asarray(g["normals"], np.float64)).to(device), base_color=images[0],
+                orm=images[1] if len(images) > 1 else None, normal_map=None if g["normal_image"] is None else image(g["normal_image"]))
+
+
 def view_files(a):
     """The command line's work.  -> dict(out_dir, views: the PNGs written, still, frames, gif, webp)."""
     import gs2m_mesh as M
     dev = _dev(None)
-    mesh = M.read_mesh(a.ply_path)
-    v = torch.as_tensor(np.asarray(mesh.vertices, np.float64)).to(dev)
-    f = torch.as_tensor(np.asarray(mesh.triangles, np.int32)).to(dev)
+    glb = getattr(a, "glb", "") or ""
+    if glb:
+        return _view_files(a, dev, None, read_textured_mesh(glb, dev))
+    if a.colour == "texture":
+        raise RuntimeError("--colour texture needs --glb FILE")
+    if not a.ply_path:
+        raise RuntimeError("give the mesh: --ply-path FILE or --glb FILE")
+    return _view_files(a, dev, M.read_mesh(a.ply_path), None)
+
+
+def _view_files(a, dev, mesh, tex):
+    if tex is not None:
+        if a.colour not in ("texture", "pbr"):
+            raise RuntimeError("--glb is drawn with --colour texture or --colour pbr")
+        v, f = tex["vertices"], tex["triangles"]
+    else:
+        v = torch.as_tensor(np.asarray(mesh.vertices, np.float64)).to(dev)
+        f = torch.as_tensor(np.asarray(mesh.triangles, np.int32)).to(dev)
     col = None
     if a.colour == "vertex":
         if mesh.vertex_colors is None:
@@ -310,7 +416,7 @@ def view_files(a):
     views = read_cameras_json(a.cameras) if a.cameras else read_colmap_views(a.source_path)
     if not views:
         raise RuntimeError("no camera to render from")
-    out_dir = a.out_dir or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(a.ply_path))), "visual")
+    out_dir = a.out_dir or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(a.glb if tex is not None else a.ply_path))), "visual")
     os.makedirs(out_dir, exist_ok=True)
     result = dict(out_dir=out_dir, views=[], still=None, frames=[], gif=None, webp=None)
     from gs2m_png import Writer
@@ -323,15 +429,32 @@ def view_files(a):
         from gs2m_mesh_bake import read_material_mesh
         if not a.envmap:
             raise RuntimeError("--colour pbr needs --envmap FILE.hdr")
-        try:
-            mm = read_material_mesh(a.ply_path)
-        except ValueError as e:
-            raise RuntimeError(f"--colour pbr needs a material mesh (gs2m_mesh_bake.py writes one): {e}") from None
-        material = [torch.as_tensor(mm[k]).to(dev) for k in ("albedo", "roughness", "metallic")]
+        if tex is not None:
+            material = [None, None, None]
+        else:
+            try:
+                mm = read_material_mesh(a.ply_path)
+            except ValueError as e:
+                raise RuntimeError(f"--colour pbr needs a material mesh (gs2m_mesh_bake.py writes one): {e}") from None
+            material = [torch.as_tensor(mm[k]).to(dev) for k in ("albedo", "roughness", "metallic")]
         light = EnvLight.from_hdr(a.envmap, a.env_res, a.env_samples, math.radians(a.env_rotation), a.exposure, device=dev)
         RL._check(light, "env", "normal")  # the light's size, as the relighting checks it
 
     def shade(w2c, k, H, W):
+        if tex is not None:
+            m = torch.as_tensor(np.ascontiguousarray(w2c)).to(dev)
+            vn = tex["normals"] if a.shading == "smooth" else None
+            srgb_tex = not getattr(a, "linear_texture", False)
+            if material is None:
+                return shade_views_textured(v, f, tex["uvs"], m, k["fx"], k["fy"], k["cx"], k["cy"], H, W, tex["base_color"], tex["normal_map"],
+                                            srgb_tex, ss=a.ss, normals=vn)
+
+            def gbuffer(part, vis, _):
+                return mesh_gbuffer_textured(v, f, tex["uvs"], part, k["fx"], k["fy"], k["cx"], k["cy"], H, W, vis, tex["base_color"], tex["orm"],
+                                             tex["normal_map"], srgb_tex, a.ss, vn)
+
+            return shade_views_pbr(v, f, m, k["fx"], k["fy"], k["cx"], k["cy"], H, W, light, None, None, None, ss=a.ss, shading="flat",
+                                   gamma=a.gamma, background=a.background, gbuffer=gbuffer)
         if material is not None:
             return shade_views_pbr(v, f, torch.as_tensor(np.ascontiguousarray(w2c)).to(dev), k["fx"], k["fy"], k["cx"], k["cy"], H, W, light,
                                    *material, ss=a.ss, shading=a.shading, gamma=a.gamma, background=a.background)
@@ -378,7 +501,10 @@ def view_files(a):
 
 def parser():
     ap = argparse.ArgumentParser(description="Shaded views and turntable frames of a mesh (scripts/vis_dtu.py, scripts/vis_shiny.py)")
-    ap.add_argument("--ply-path", required=True, help="the mesh (binary PLY), e.g. MODEL/train/ours_30000/mesh/tsdf_post.ply")
+    ap.add_argument("--ply-path", default="", help="the mesh (binary PLY), e.g. MODEL/train/ours_30000/mesh/tsdf_post.ply")
+    ap.add_argument("--glb", default="", metavar="FILE",
+                    help="instead of --ply-path: a textured .glb of gs2m_mesh_texture.py, drawn with --colour texture or --colour pbr")
+    ap.add_argument("--linear-texture", action="store_true", help="the .glb's base colour was written with --linear")
     src = ap.add_mutually_exclusive_group(required=True)
     src.add_argument("--cameras", default="", help="MODEL/cameras.json")
     src.add_argument("--source-path", "-s", default="", help="a COLMAP-format dataset")
@@ -391,8 +517,9 @@ def parser():
     ap.add_argument("--frames", type=int, default=FRAMES, help=argparse.SUPPRESS)  # for the tests
     ap.add_argument("--shift", type=float, nargs=3, default=(0.0, 0.0, 0.0), metavar=("X", "Y", "Z"), help="moves the mesh (still, animation)")
     ap.add_argument("--shading", choices=("flat", "smooth"), default="flat")
-    ap.add_argument("--colour", choices=("grey", "vertex", "pbr"), default="grey",
-                    help="pbr: a material mesh (gs2m_mesh_bake.py) shaded under --envmap; the options below belong to it")
+    ap.add_argument("--colour", choices=("grey", "vertex", "pbr", "texture"), default="grey",
+                    help="pbr: a material mesh (gs2m_mesh_bake.py), or the textures of --glb, shaded under --envmap; the options below "
+                         "belong to it.  texture: the base colour of --glb under the headlight")
     ap.add_argument("--envmap", default="", help="lat-long Radiance file (.hdr), as gs2m_relight.py takes it")
     ap.add_argument("--env-res", type=int, default=512, help="cube-map resolution: a power of two >= 64")
     ap.add_argument("--env-samples", type=int, default=None, help="S x S taps per texel, 1 .. 16")
@@ -408,7 +535,10 @@ def parser():
 
 
 def main(argv=None):
-    a = parser().parse_args(argv)
+    ap = parser()
+    a = ap.parse_args(argv)
+    if bool(a.ply_path) == bool(a.glb):
+        ap.error("one of --ply-path and --glb is required")
     r = view_files(a)
     print(f"[>] {len(r['views'])} views, {'a still, ' if r['still'] else ''}{len(r['frames'])} frames -> {r['out_dir']}")
     return r

@@ -221,6 +221,7 @@ SIGNATURES = {
     "gs2m_meshview_normals": (i, [ll, p, ll, p, p, p, p, s]),
     "gs2m_meshview_shade": (i, [ll, p, ll, p, i, p, d, d, d, d, i, i, i, p, p, p, d, d, d, d, d, i, p, p, p, s]),
     "gs2m_meshview_gbuffer": (i, [ll, p, ll, p, i, p, d, d, d, d, i, i, i, p, p, p, p, p, p, p, p, p, p, p, s]),
+    "gs2m_meshview_gbuffer_textured": (i, [ll, p, ll, p, p, i, p, d, d, d, d, i, i, i, p, p, i, i, p, i, p, p, p, p, p, p, p, p, s]),
     "gs2m_meshview_resolve_rgb": (i, [i, i, i, i, p, p, i, p, p, s]),
     # include/gs2m_meshbake.h
     "gs2m_meshbake_accumulate": (i, [ll, p, p, i, p, d, d, d, d, i, i, p, i, p, p, d, i, p, p, s]),
@@ -228,6 +229,7 @@ SIGNATURES = {
     "gs2m_texbake_accumulate": (i, [ll, p, p, p, i, p, d, d, d, d, i, i, p, i, p, p, d, i, p, p, s]),
     "gs2m_texbake_resolve": (i, [ll, i, i, i, p, p, d, p, p, ll, p, p, ll, p, p, p, s]),
     "gs2m_texture_pack": (i, [ll, i, p, i, p, p, s]),
+    "gs2m_texture_normals": (i, [ll, p, p, ll, p, p, ll, p, i, i, p, p, p, s]),
     # include/gs2m_atlas.h
     "gs2m_atlas_workspace_bytes": (i, [ll, p]),
     "gs2m_atlas_count": (i, [ll, ll, p, p, d, p, p, p, s]),

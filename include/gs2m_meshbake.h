@@ -63,7 +63,30 @@ int gs2m_meshbake_resolve(long long n_verts, int C, const double* sums, const do
  *   Pack           x = the fp32 value widened, clamped to [0, 1] (NaN -> 0).  base_color[p][d] = floor(255 enc(x_d) + 0.5),
  *                  d < 3, enc the sRGB encode of gs2m_meshview.h when srgb != 0, else the identity.  With C == 5 also
  *                  orm[p] = (255, floor(255 x_3 + 0.5), floor(255 x_4 + 0.5)): occlusion unused, roughness in G, metallic in
- *                  B, glTF's metallicRoughnessTexture layout.  C == 3 (a plain colour bake) takes orm == NULL. */
+ *                  B, glTF's metallicRoughnessTexture layout.  C == 3 (a plain colour bake) takes orm == NULL.
+ *
+ * ---- the tangent-space normal map (csrc/tangent_frame.h, shared with gs2m_meshview.h) ----
+ *
+ *   Tangent frame  of a point of a textured triangle: corners a, b, c in world space, their fp32 UVs widened to double (v from the
+ *                  top row, gs2m_atlas.h), a shading normal N at the point.  e1 = b - a, e2 = c - a, (du1, dv1) = uv_b - uv_a,
+ *                  (du2, dv2) = uv_c - uv_a, det = du1 dv2 - du2 dv1, d_u = (e1 dv2 - e2 dv1) / det per coordinate,
+ *                  Nf = cross(e1, e2).  unit(x) = x / sqrt(dot(x, x)), dot as above.  N = unit(N); where N is zero or not finite
+ *                  (or dot(N, N) is not > 0), or dot(N, Nf) <= 0, N = unit(Nf).  T = unit(d_u - N dot(N, d_u)),
+ *                  B = w cross(N, T) with w = -1: glTF's bitangent points towards decreasing v, and the two halves of an atlas
+ *                  cell are rotations of one another, so w is -1 for every chart of the atlas (tangent_frame.h derives it).
+ *                  valid = 0 when det == 0 or is not finite, when Nf or the argument of a unit() is zero or not finite: then
+ *                  T = B = 0, and N is the N above, or without a usable Nf the unit of the given normal, (0, 0, 1) without either.
+ *   Encode         a world normal n: n' = unit(n), m = (dot(n', T), dot(n', B), dot(n', N)), m_z = max(m_z, 0), m = unit(m);
+ *                  m = (0, 0, 1) for an invalid frame, for n zero or not finite, and where m becomes zero.
+ *                  byte_k = floor(255 (0.5 m_k + 0.5) + 0.5).
+ *   Decode         m_k = byte_k / 255 * 2 - 1 (a bilinear lookup mixes such values first); n = unit((T m_x + B m_y) + N m_z)
+ *                  per coordinate, N for an invalid frame or where that sum is zero or not finite.
+ *   Normals        per texel p with owner t: the frame of triangle t's corners and `uvs` at N = tnormals[p], the texel's
+ *                  interpolated normal (gs2m_atlas_texels); n = values[p][offset .. offset + 2], the resolved planes of the baked
+ *                  world normal, widened (the views' unit normals averaged: an unseen or empty texel carries 0 there and encodes
+ *                  flat).  tangent[p] = Encode's m, normal_map[p] = its bytes.  An empty texel, an owner not below n_triangles
+ *                  and a corner outside [0, n_verts) give m = (0, 0, 1), bytes (128, 128, 255).  The frame needs no cell: the
+ *                  chart enters through the UVs alone, so any run of texels may be converted in one call. */
 
 /* As gs2m_meshbake_accumulate; points, normals: double (n_texels, 3), normals may be NULL; owner: int (n_texels). */
 int gs2m_texbake_accumulate(long long n_texels, const double* points, const double* normals, const int* owner, int n_views,
@@ -81,6 +104,14 @@ int gs2m_texbake_resolve(long long n_texels, int C, int width, int row0, const d
 /* values: float (n_texels, C), C = 3 or 5; base_color, orm: unsigned char (n_texels, 3) (see Pack). */
 int gs2m_texture_pack(long long n_texels, int C, const float* values, int srgb, unsigned char* base_color, unsigned char* orm,
                       void* stream);
+
+/* The Normals paragraph for n_texels texels: owner: int (n_texels) and tnormals: double (n_texels, 3) as gs2m_atlas_texels wrote
+ * them; triangles: int (n_triangles, 3); uvs: float (n_triangles, 3, 2), gs2m_atlas_build's; vertices: double (n_verts, 3);
+ * values: float (n_texels, C), gs2m_texbake_resolve's output, 3 <= C <= 8, the normal in the planes offset .. offset + 2
+ * (0 <= offset <= C - 3).  normal_map: unsigned char (n_texels, 3); tangent: double (n_texels, 3), the m before packing, or NULL. */
+int gs2m_texture_normals(long long n_texels, const int* owner, const double* tnormals, long long n_triangles, const int* triangles,
+                         const float* uvs, long long n_verts, const double* vertices, int C, int offset, const float* values,
+                         unsigned char* normal_map, double* tangent, void* stream);
 
 #ifdef __cplusplus
 }

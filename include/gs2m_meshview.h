@@ -35,6 +35,18 @@
  *   Resolve RGB    the Resolve paragraph on samples shaded elsewhere: lin_k = min(max(rgb_k, 0), 1) of the sample's float RGB
  *                  widened to double, covered = its coverage byte is not 0.  With a background, (0, 0, 0) for enc where m == 0,
  *                  a = m / ss^2, the colour byte is floor(255 (a enc_k + (1 - a) min(max(bg_k, 0), 1)) + 0.5) and alpha is 255.
+ *   Textured       the G-buffer paragraph with the materials read from textures: uv = (l0 uv_a + l1 uv_b) + l2 uv_c
+ *                  per coordinate of the triangle's fp32 UVs widened to double, v from the top row.  An image is th rows of tw
+ *                  texels of three bytes; x = u tw - 0.5, y = v th - 0.5, and the taps and weights are those of the Taps paragraph
+ *                  of gs2m_meshbake.h with (x, y) for (u, v), except that a tap outside the image is clamped to the edge; the
+ *                  bytes are decoded before they are mixed, in the order of the Sample paragraph there.  base_color: byte / 255,
+ *                  then with srgb the inverse of the Resolve paragraph's encode (x / 12.92 up to 12.92 * 0.0031308, else
+ *                  pow((x + 0.055) / 1.055, 2.4)); orm: roughness = G / 255, metallic = B / 255, without it 1 and 0;
+ *                  normal_map: m_k = byte_k / 255 * 2 - 1.  With a normal map the Tangent frame paragraph of gs2m_meshbake.h
+ *                  (csrc/tangent_frame.h: one definition for the bake and for this decode) is built from the triangle's world-space
+ *                  corners, its UVs and N = Nw, the sample's flat or smooth normal taken to world space BEFORE the eye-facing
+ *                  flip; normal = Decode of the mixed m, negated when its dot with the ray taken to world space
+ *                  (rw_k = (M[0][k] r0 + M[1][k] r1) + M[2][k] r2) is > 0.  Without one the normal is the G-buffer paragraph's.
  *
  * Every buffer is the caller's; workspace sizes come from the *_workspace_bytes functions.  Return GS2M_OK (0) or a negative
  * GS2M_ERR_* code (gs2m_raster.h).  No float atomics: results are bitwise reproducible. */
@@ -83,6 +95,16 @@ int gs2m_meshview_gbuffer(long long n_verts, const double* verts, long long n_tr
                           const double* normals, const float* albedo, const float* roughness, const float* metallic,
                           float* out_normal, float* out_view_dir, float* out_albedo, float* out_roughness, float* out_metallic,
                           unsigned char* coverage, void* stream);
+
+/* As gs2m_meshview_gbuffer, the Textured paragraph in the place of the vertex arrays: uvs: float (n_tris, 3, 2); base_color,
+ * orm, normal_map: unsigned char (th, tw, 3), orm and normal_map may each be NULL; 1 <= tw, th, and beyond GS2M_ATLAS_MAX_WIDTH
+ * (gs2m_atlas.h) GS2M_ERR_UNSUPPORTED.  Keys are not trusted, as there. */
+int gs2m_meshview_gbuffer_textured(long long n_verts, const double* verts, long long n_tris, const int* tris, const float* uvs, int n_views,
+                                   const double* w2c, double fx, double fy, double cx, double cy, int W, int H, int ss,
+                                   const unsigned long long* vis, const double* normals, int tw, int th, const unsigned char* base_color,
+                                   int srgb, const unsigned char* orm, const unsigned char* normal_map, float* out_normal,
+                                   float* out_view_dir, float* out_albedo, float* out_roughness, float* out_metallic,
+                                   unsigned char* coverage, void* stream);
 
 /* rgba: unsigned char (n_views, H, W, 4) from rgb: float (n_views, H ss, W ss, 3), the samples' linear colour, and coverage:
  * unsigned char (n_views, H ss, W ss) (see above).  background: float (n_views, H, W, 3) composited under the alpha, in the

@@ -1,5 +1,5 @@
 // The per-point view loop of the attribute bakes (the Weight, Project, Mask, Sample and Accumulate paragraphs of
-// include/gs2m_meshbake.h), shared by the two kernels of mesh_bake.hip: a point is a vertex there, or a texel's point on its
+// include/gs2m_meshbake.h), the body of mesh_bake.hip's accumulate kernel: a point is a vertex there, or a texel's point on its
 // triangle.  fp64, as written: compile the including unit with -ffp-contract=off.
 //
 // The views' matrices and camera centres are staged in LDS, BAKE_CHUNK at a time, by the whole workgroup (every lane then reads

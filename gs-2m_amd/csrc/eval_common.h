@@ -127,9 +127,13 @@ static inline CompactWs carve_compact(char* base, long long nv, long long nt) {
     return w;
 }
 
-// a triangle's vertex indices against the vertex count; err[0] = 1 tells the host of one out of range
+// a triangle's vertex indices against the vertex count
+__device__ __forceinline__ bool ids_in_range(int a, int b, int c, long long nv) {
+    return !(a < 0 || b < 0 || c < 0 || a >= nv || b >= nv || c >= nv);
+}
+// the same; err[0] = 1 tells the host of one out of range
 __device__ __forceinline__ bool tri_in_range(int a, int b, int c, long long nv, int* __restrict__ err) {
-    if (a < 0 || b < 0 || c < 0 || a >= nv || b >= nv || c >= nv) {
+    if (!ids_in_range(a, b, c, nv)) {
         err[0] = 1;
         return false;
     }

@@ -26,52 +26,18 @@ namespace {
 
 constexpr int BAKE_CMAX = 8;
 
+// owner: null = every point below n is owned (the vertex bake); else a point with owner[i] < 0 -- an empty texel -- has no point: it
+// walks no view and its sums are 0.
 template <int C>
-__global__ void __launch_bounds__(256) bake_kernel(long long n, const double* __restrict__ verts, const double* __restrict__ normals,
-                                                   BakeViews views, int accumulate, double* __restrict__ sums,
-                                                   double* __restrict__ weights) {
+__global__ void __launch_bounds__(256) bake_kernel(long long n, const double* __restrict__ points, const double* __restrict__ normals,
+                                                   const int* __restrict__ owner, BakeViews views, int accumulate,
+                                                   double* __restrict__ sums, double* __restrict__ weights) {
     __shared__ double s_m[BAKE_CHUNK][BAKE_ROW];
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     const bool live = i < n;
+    const bool owned = live && (!owner || owner[i] >= 0);
     double p[3] = {0.0, 0.0, 0.0}, N[3] = {0.0, 0.0, 0.0}, nn = 0.0;
-    bool lit = live;  // false: every view weighs 0
-    if (live) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) p[k] = verts[3 * i + k];
-        if (normals) {
-#pragma unroll
-            for (int k = 0; k < 3; k++) N[k] = normals[3 * i + k];
-            nn = dot3(N, N);
-            lit = normal_ok(N);
-        }
-    }
-    double acc[C], wsum = 0.0;
-#pragma unroll
-    for (int c = 0; c < C; c++) acc[c] = 0.0;
-    if (live && accumulate) {
-#pragma unroll
-        for (int c = 0; c < C; c++) acc[c] = sums[(size_t)i * C + c];
-        wsum = weights[i];
-    }
-    bake_views<C>(views, lit, p, normals != nullptr, N, nn, s_m, acc, wsum);
-    if (live) {
-#pragma unroll
-        for (int c = 0; c < C; c++) sums[(size_t)i * C + c] = acc[c];
-        weights[i] = wsum;
-    }
-}
-
-// The texel bake: as bake_kernel, but a texel without an owner has no point -- it walks no view and its sums are 0.
-template <int C>
-__global__ void __launch_bounds__(256) texbake_kernel(long long n, const double* __restrict__ points, const double* __restrict__ normals,
-                                                      const int* __restrict__ owner, BakeViews views, int accumulate,
-                                                      double* __restrict__ sums, double* __restrict__ weights) {
-    __shared__ double s_m[BAKE_CHUNK][BAKE_ROW];
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    const bool live = i < n;
-    const bool owned = live && owner[i] >= 0;
-    double p[3] = {0.0, 0.0, 0.0}, N[3] = {0.0, 0.0, 0.0}, nn = 0.0;
-    bool lit = owned;
+    bool lit = owned;  // false: every view weighs 0
     if (owned) {
 #pragma unroll
         for (int k = 0; k < 3; k++) p[k] = points[3 * i + k];
@@ -90,7 +56,7 @@ __global__ void __launch_bounds__(256) texbake_kernel(long long n, const double*
         for (int c = 0; c < C; c++) acc[c] = sums[(size_t)i * C + c];
         wsum = weights[i];
     }
-    bake_views<C>(views, lit, p, normals != nullptr, N, nn, s_m, acc, wsum);
+    bake_views<C>(views, lit, p, normals != nullptr, N, nn, s_m, acc, wsum);  // every thread: it holds barriers
     if (live) {
 #pragma unroll
         for (int c = 0; c < C; c++) sums[(size_t)i * C + c] = acc[c];
@@ -102,26 +68,16 @@ struct Fallback {
     float v[BAKE_CMAX];
 };
 
-__global__ void __launch_bounds__(256) bake_resolve_kernel(long long n, int C, const double* __restrict__ sums,
-                                                           const double* __restrict__ weights, double min_weight, Fallback fb,
-                                                           float* __restrict__ out, unsigned char* __restrict__ seen) {
+// owner: null = every point is owned and none has a triangle (the vertex bake); else point i of the call is texel
+// (i % width, row0 + i / width) of the atlas.  attrs: null = a point no view reached takes the fallback.
+__global__ void __launch_bounds__(256) resolve_kernel(long long n, int C, int width, int row0, const double* __restrict__ sums,
+                                                      const double* __restrict__ weights, double min_weight, Fallback fb,
+                                                      const int* __restrict__ owner, long long nt, const int* __restrict__ tris,
+                                                      const int* __restrict__ cells, long long nv, const float* __restrict__ attrs,
+                                                      float* __restrict__ out, unsigned char* __restrict__ seen) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const double w = weights[i];
-    const bool ok = w >= min_weight && w > 0.0;
-    for (int c = 0; c < C; c++) out[(size_t)i * C + c] = ok ? (float)(sums[(size_t)i * C + c] / w) : fb.v[c];
-    seen[i] = ok ? 1 : 0;
-}
-
-// texel i of the call is texel (i % width, row0 + i / width) of the atlas
-__global__ void __launch_bounds__(256) texbake_resolve_kernel(long long n, int C, int width, int row0, const double* __restrict__ sums,
-                                                              const double* __restrict__ weights, double min_weight, Fallback fb,
-                                                              const int* __restrict__ owner, long long nt, const int* __restrict__ tris,
-                                                              const int* __restrict__ cells, long long nv, const float* __restrict__ attrs,
-                                                              float* __restrict__ out, unsigned char* __restrict__ seen) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const int t = owner[i];
+    const int t = owner ? owner[i] : 0;
     const double w = t >= 0 ? weights[i] : 0.0;
     const bool ok = w >= min_weight && w > 0.0;
     seen[i] = ok ? 1 : 0;
@@ -132,14 +88,12 @@ __global__ void __launch_bounds__(256) texbake_resolve_kernel(long long n, int C
     bool from_vertices = false;
     double l[3] = {0.0, 0.0, 0.0};
     int id[3] = {0, 0, 0};
-    if (attrs && t >= 0 && t < nt) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) id[k] = tris[3 * (size_t)t + k];
+    if (attrs && owner && t >= 0 && t < nt) {
         const int* cell = cells + 4 * (size_t)t;
         const int side = cell[2], half = cell[3];
         const int li = (int)(i % width) - cell[0], lj = row0 + (int)(i / width) - cell[1];
-        from_vertices = id[0] >= 0 && id[1] >= 0 && id[2] >= 0 && id[0] < nv && id[1] < nv && id[2] < nv && side >= 8 && side <= 256 &&
-                        (half == 0 || half == 1) && li >= 0 && lj >= 0 && li < side && lj < side;
+        from_vertices = load_ids(tris, t, nv, id) && side >= 8 && side <= 256 && (half == 0 || half == 1) && li >= 0 && lj >= 0 && li < side &&
+                        lj < side;
         if (from_vertices) atlas_bary(side, half, li, lj, l);
     }
     for (int c = 0; c < C; c++) {
@@ -151,24 +105,19 @@ __global__ void __launch_bounds__(256) texbake_resolve_kernel(long long n, int C
     }
 }
 
-__device__ __forceinline__ unsigned char to_byte(double x) {  // NaN -> 0
-    const double c = x > 0.0 ? (x < 1.0 ? x : 1.0) : 0.0;
-    return (unsigned char)floor(255.0 * c + 0.5);
-}
+__device__ __forceinline__ double clamp01(double x) { return x > 0.0 ? (x < 1.0 ? x : 1.0) : 0.0; }  // NaN -> 0
+__device__ __forceinline__ unsigned char to_byte(double x) { return (unsigned char)floor(255.0 * x + 0.5); }  // x in [0, 1]
 
 __global__ void __launch_bounds__(256) texture_pack_kernel(long long n, int C, const float* __restrict__ values, int srgb,
                                                            unsigned char* __restrict__ base, unsigned char* __restrict__ orm) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const float* v = values + (size_t)i * C;
-    for (int d = 0; d < 3; d++) {
-        const double x = (double)v[d], c = x > 0.0 ? (x < 1.0 ? x : 1.0) : 0.0;
-        base[3 * (size_t)i + d] = (unsigned char)floor(255.0 * encode(c, srgb) + 0.5);
-    }
+    for (int d = 0; d < 3; d++) base[3 * (size_t)i + d] = to_byte(encode(clamp01((double)v[d]), srgb));  // clamped, then encoded
     if (orm) {
         orm[3 * (size_t)i] = 255;
-        orm[3 * (size_t)i + 1] = to_byte((double)v[3]);
-        orm[3 * (size_t)i + 2] = to_byte((double)v[4]);
+        orm[3 * (size_t)i + 1] = to_byte(clamp01((double)v[3]));
+        orm[3 * (size_t)i + 2] = to_byte(clamp01((double)v[4]));
     }
 }
 
@@ -183,8 +132,8 @@ __global__ void __launch_bounds__(256) texture_normals_kernel(long long n, const
     double m[3] = {0.0, 0.0, 1.0};
     const int t = owner[i];
     if (t >= 0 && t < nt) {
-        const int id[3] = {tris[3 * (size_t)t], tris[3 * (size_t)t + 1], tris[3 * (size_t)t + 2]};
-        if (id[0] >= 0 && id[1] >= 0 && id[2] >= 0 && id[0] < nv && id[1] < nv && id[2] < nv) {
+        int id[3];
+        if (load_ids(tris, t, nv, id)) {
             double P[9], uv[6], N[3], w[3];
 #pragma unroll
             for (int k = 0; k < 3; k++) {
@@ -213,6 +162,43 @@ int views_status(int n_views, double fx, double fy, double cx, double cy, int W,
     return GS2M_OK;
 }
 
+// points: vertices (texels false: no owner) or texels with their owner
+int bake_accumulate(bool texels, long long n, const double* points, const double* normals, const int* owner, int n_views, const double* w2c,
+                    double fx, double fy, double cx, double cy, int W, int H, const float* depth, int C, const float* maps, const float* mask,
+                    double eps, int accumulate, double* sums, double* weights, void* stream) {
+    if (n < 0 || views_status(n_views, fx, fy, cx, cy, W, H, w2c, depth, C, maps, eps) != GS2M_OK) return GS2M_ERR_INVALID_ARG;
+    if (n > 0 && (!points || (texels && !owner) || !sums || !weights)) return GS2M_ERR_INVALID_ARG;
+    if (n == 0) return GS2M_OK;
+    if (n > MAX_LAUNCH) return GS2M_ERR_UNSUPPORTED;
+    if ((long long)n_views * C * W * H > MAX_LAUNCH) return GS2M_ERR_UNSUPPORTED;
+    const BakeViews views{n_views, w2c, Frame{fx, fy, cx, cy, 0.0, 0.0, W, H}, depth, maps, mask, eps};
+    hipStream_t s = (hipStream_t)stream;
+#define BAKE_CASE(c) \
+    case c: bake_kernel<c><<<blocks_of(n), 256, 0, s>>>(n, points, normals, owner, views, accumulate, sums, weights); break;
+    switch (C) {
+        BAKE_CASE(1) BAKE_CASE(2) BAKE_CASE(3) BAKE_CASE(4) BAKE_CASE(5) BAKE_CASE(6) BAKE_CASE(7) BAKE_CASE(8)
+    }
+#undef BAKE_CASE
+    return gs2m_status(hipGetLastError());
+}
+
+// texels false: no owner, no attributes, and the atlas arguments are unused
+int bake_resolve(bool texels, long long n, int C, int width, int row0, const double* sums, const double* weights, double min_weight,
+                 const float* fallback, const int* owner, long long n_triangles, const int* triangles, const int* cells, long long n_verts,
+                 const float* attributes, float* out, unsigned char* seen, void* stream) {
+    if (n < 0 || C < 1 || C > BAKE_CMAX || min_weight != min_weight || !fallback || width < 1 || row0 < 0 || n_triangles < 0 || n_verts < 0)
+        return GS2M_ERR_INVALID_ARG;
+    if (n > 0 && (!sums || !weights || (texels && !owner) || !out || !seen)) return GS2M_ERR_INVALID_ARG;
+    if (attributes && (!triangles || !cells)) return GS2M_ERR_INVALID_ARG;
+    if (n == 0) return GS2M_OK;
+    if (n > MAX_LAUNCH || (texels && (n + width - 1) / width + row0 > 0x7FFFFFFFll)) return GS2M_ERR_UNSUPPORTED;
+    Fallback fb{};
+    for (int c = 0; c < C; c++) fb.v[c] = fallback[c];
+    resolve_kernel<<<blocks_of(n), 256, 0, (hipStream_t)stream>>>(n, C, width, row0, sums, weights, min_weight, fb, owner, n_triangles, triangles,
+                                                                  cells, n_verts, attributes, out, seen);
+    return gs2m_status(hipGetLastError());
+}
+
 }  // namespace
 
 extern "C" {
@@ -220,69 +206,28 @@ extern "C" {
 int gs2m_meshbake_accumulate(long long n_verts, const double* verts, const double* normals, int n_views, const double* w2c,
                              double fx, double fy, double cx, double cy, int W, int H, const float* depth, int C, const float* maps,
                              const float* mask, double eps, int accumulate, double* sums, double* weights, void* stream) {
-    if (n_verts < 0 || views_status(n_views, fx, fy, cx, cy, W, H, w2c, depth, C, maps, eps) != GS2M_OK) return GS2M_ERR_INVALID_ARG;
-    if (n_verts > 0 && (!verts || !sums || !weights)) return GS2M_ERR_INVALID_ARG;
-    if (n_verts == 0) return GS2M_OK;
-    if (n_verts > MAX_LAUNCH) return GS2M_ERR_UNSUPPORTED;
-    if ((long long)n_views * C * W * H > MAX_LAUNCH) return GS2M_ERR_UNSUPPORTED;
-    const BakeViews views{n_views, w2c, Frame{fx, fy, cx, cy, 0.0, 0.0, W, H}, depth, maps, mask, eps};
-    hipStream_t s = (hipStream_t)stream;
-#define BAKE_CASE(c) \
-    case c: bake_kernel<c><<<blocks_of(n_verts), 256, 0, s>>>(n_verts, verts, normals, views, accumulate, sums, weights); break;
-    switch (C) {
-        BAKE_CASE(1) BAKE_CASE(2) BAKE_CASE(3) BAKE_CASE(4) BAKE_CASE(5) BAKE_CASE(6) BAKE_CASE(7) BAKE_CASE(8)
-    }
-#undef BAKE_CASE
-    return gs2m_status(hipGetLastError());
+    return bake_accumulate(false, n_verts, verts, normals, nullptr, n_views, w2c, fx, fy, cx, cy, W, H, depth, C, maps, mask, eps, accumulate, sums,
+                        weights, stream);
 }
 
 int gs2m_meshbake_resolve(long long n_verts, int C, const double* sums, const double* weights, double min_weight,
                           const float* fallback, float* out, unsigned char* seen, void* stream) {
-    if (n_verts < 0 || C < 1 || C > BAKE_CMAX || min_weight != min_weight || !fallback) return GS2M_ERR_INVALID_ARG;
-    if (n_verts > 0 && (!sums || !weights || !out || !seen)) return GS2M_ERR_INVALID_ARG;
-    if (n_verts == 0) return GS2M_OK;
-    if (n_verts > MAX_LAUNCH) return GS2M_ERR_UNSUPPORTED;
-    Fallback fb{};
-    for (int c = 0; c < C; c++) fb.v[c] = fallback[c];
-    bake_resolve_kernel<<<blocks_of(n_verts), 256, 0, (hipStream_t)stream>>>(n_verts, C, sums, weights, min_weight, fb, out, seen);
-    return gs2m_status(hipGetLastError());
+    return bake_resolve(false, n_verts, C, 1, 0, sums, weights, min_weight, fallback, nullptr, 0, nullptr, nullptr, 0, nullptr, out, seen, stream);
 }
 
 int gs2m_texbake_accumulate(long long n_texels, const double* points, const double* normals, const int* owner, int n_views,
                             const double* w2c, double fx, double fy, double cx, double cy, int W, int H, const float* depth, int C,
                             const float* maps, const float* mask, double eps, int accumulate, double* sums, double* weights,
                             void* stream) {
-    if (n_texels < 0 || views_status(n_views, fx, fy, cx, cy, W, H, w2c, depth, C, maps, eps) != GS2M_OK) return GS2M_ERR_INVALID_ARG;
-    if (n_texels > 0 && (!points || !owner || !sums || !weights)) return GS2M_ERR_INVALID_ARG;
-    if (n_texels == 0) return GS2M_OK;
-    if (n_texels > MAX_LAUNCH) return GS2M_ERR_UNSUPPORTED;
-    if ((long long)n_views * C * W * H > MAX_LAUNCH) return GS2M_ERR_UNSUPPORTED;
-    const BakeViews views{n_views, w2c, Frame{fx, fy, cx, cy, 0.0, 0.0, W, H}, depth, maps, mask, eps};
-    hipStream_t s = (hipStream_t)stream;
-#define BAKE_CASE(c) \
-    case c: texbake_kernel<c><<<blocks_of(n_texels), 256, 0, s>>>(n_texels, points, normals, owner, views, accumulate, sums, weights); break;
-    switch (C) {
-        BAKE_CASE(1) BAKE_CASE(2) BAKE_CASE(3) BAKE_CASE(4) BAKE_CASE(5) BAKE_CASE(6) BAKE_CASE(7) BAKE_CASE(8)
-    }
-#undef BAKE_CASE
-    return gs2m_status(hipGetLastError());
+    return bake_accumulate(true, n_texels, points, normals, owner, n_views, w2c, fx, fy, cx, cy, W, H, depth, C, maps, mask, eps, accumulate, sums,
+                        weights, stream);
 }
 
 int gs2m_texbake_resolve(long long n_texels, int C, int width, int row0, const double* sums, const double* weights, double min_weight,
                          const float* fallback, const int* owner, long long n_triangles, const int* triangles, const int* cells,
                          long long n_verts, const float* attributes, float* out, unsigned char* seen, void* stream) {
-    if (n_texels < 0 || C < 1 || C > BAKE_CMAX || min_weight != min_weight || !fallback || width < 1 || row0 < 0 || n_triangles < 0 ||
-        n_verts < 0)
-        return GS2M_ERR_INVALID_ARG;
-    if (n_texels > 0 && (!sums || !weights || !owner || !out || !seen)) return GS2M_ERR_INVALID_ARG;
-    if (attributes && (!triangles || !cells)) return GS2M_ERR_INVALID_ARG;
-    if (n_texels == 0) return GS2M_OK;
-    if (n_texels > MAX_LAUNCH || (n_texels + width - 1) / width + row0 > 0x7FFFFFFFll) return GS2M_ERR_UNSUPPORTED;
-    Fallback fb{};
-    for (int c = 0; c < C; c++) fb.v[c] = fallback[c];
-    texbake_resolve_kernel<<<blocks_of(n_texels), 256, 0, (hipStream_t)stream>>>(n_texels, C, width, row0, sums, weights, min_weight, fb, owner,
-                                                                                 n_triangles, triangles, cells, n_verts, attributes, out, seen);
-    return gs2m_status(hipGetLastError());
+    return bake_resolve(true, n_texels, C, width, row0, sums, weights, min_weight, fallback, owner, n_triangles, triangles, cells, n_verts,
+                   attributes, out, seen, stream);
 }
 
 int gs2m_texture_pack(long long n_texels, int C, const float* values, int srgb, unsigned char* base_color, unsigned char* orm,

@@ -158,6 +158,13 @@ __device__ __forceinline__ unsigned wave_append(bool want, unsigned* counter, in
     return base + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
 }
 
+// triangle t's three vertex ids -> id; false: one of them is outside [0, nv), and no vertex may be loaded through them
+__device__ __forceinline__ bool load_ids(const int* __restrict__ tris, long long t, long long nv, int* id) {
+#pragma unroll
+    for (int k = 0; k < 3; k++) id[k] = tris[3 * (size_t)t + k];
+    return ids_in_range(id[0], id[1], id[2], nv);
+}
+
 __device__ __forceinline__ void load_triangle(const double* __restrict__ verts, const int* __restrict__ tris, long long t, double* P) {
 #pragma unroll
     for (int k = 0; k < 3; k++) {

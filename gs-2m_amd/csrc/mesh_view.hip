@@ -83,8 +83,7 @@ __device__ __forceinline__ bool sample_surface(long long nv, const double* __res
     if (key == EMPTY_KEY) return false;
     const long long t = (long long)(key & 0xFFFFFFFFull);
     if (t >= nt) return false;
-    id[0] = tris[3 * t], id[1] = tris[3 * t + 1], id[2] = tris[3 * t + 2];
-    if (id[0] < 0 || id[1] < 0 || id[2] < 0 || id[0] >= nv || id[1] >= nv || id[2] >= nv) return false;
+    if (!load_ids(tris, t, nv, id)) return false;
     double P[9], a[3], b[3], c[3], x[3];
     load_triangle(verts, tris, t, P);
     to_camera(M, P, a);

@@ -543,9 +543,10 @@ _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short":
               "double": "<f8", "float64": "<f8"}
 
 
-def read_mesh(file):
-    """Binary little-endian PLY with a vertex element (x y z, optional red green blue uchar, other scalar properties
-    skipped) and a triangle face element (list uchar|int int|uint) -> TriangleMesh."""
+def _ply_elements(file):
+    """The elements of a binary little-endian PLY, one after the other in file order -> (name, structured array, is_list): a
+    list element (uchar|int counts, int|uint indices) has the fields n and v (3 indices), any other one field per scalar
+    property.  ValueError for another format, and for a list element that is not all triangles when the walk reaches it."""
     with open(str(file), "rb") as f:
         data = f.read()
     end = data.index(b"end_header\n") + len(b"end_header\n")
@@ -555,31 +556,40 @@ def read_mesh(file):
     elems = []
     for ln in lines:
         p = ln.split()
-        if not p:
-            continue
-        if p[0] == "element":
+        if p and p[0] == "element":
             elems.append([p[1], int(p[2]), []])
-        elif p[0] == "property":
+        elif p and p[0] == "property":
             elems[-1][2].append(p[1:])
-    off, verts, tris, cols = end, None, None, None
+    off = end
     for name, n, props in elems:
-        if props and props[0][0] == "list":
-            cnt, idx = _PLY_TYPES[props[0][1]], _PLY_TYPES[props[0][2]]
-            dt = np.dtype([("n", cnt), ("v", idx, (3,))])
-            a = np.frombuffer(data, dt, n, off)
-            if n and not np.all(a["n"] == 3):
-                raise ValueError(f"{file}: only triangle faces are read")
-            off += dt.itemsize * n
-            if name == "face":
-                tris = a["v"].astype(np.int32)
-            continue
-        dt = np.dtype([(q[1], _PLY_TYPES[q[0]]) for q in props])
+        is_list = bool(props) and props[0][0] == "list"
+        if is_list:
+            dt = np.dtype([("n", _PLY_TYPES[props[0][1]]), ("v", _PLY_TYPES[props[0][2]], (3,))])
+        else:
+            dt = np.dtype([(q[1], _PLY_TYPES[q[0]]) for q in props])
         a = np.frombuffer(data, dt, n, off)
+        if is_list and n and not np.all(a["n"] == 3):
+            raise ValueError(f"{file}: only triangle faces are read")
         off += dt.itemsize * n
-        if name == "vertex":
-            verts = np.stack([a[k].astype(np.float32) for k in "xyz"], axis=1) if n else np.zeros((0, 3), np.float32)
+        yield name, a, is_list
+
+
+def _ply_columns(a, names, scale=1.0):
+    """the scalar properties `names` of a PLY element as one float32 array (n, len(names)), divided by `scale`"""
+    return np.stack([a[k].astype(np.float32) / scale for k in names], axis=1) if len(a) else np.zeros((0, len(names)), np.float32)
+
+
+def read_mesh(file):
+    """Binary little-endian PLY with a vertex element (x y z, optional red green blue uchar, other scalar properties
+    skipped) and a triangle face element (list uchar|int int|uint) -> TriangleMesh."""
+    verts, tris, cols = None, None, None
+    for name, a, is_list in _ply_elements(file):
+        if is_list and name == "face":
+            tris = a["v"].astype(np.int32)
+        elif not is_list and name == "vertex":
+            verts = _ply_columns(a, "xyz")
             if "red" in a.dtype.names:
-                cols = np.stack([a[k].astype(np.float32) / 255.0 for k in ("red", "green", "blue")], axis=1)
+                cols = _ply_columns(a, ("red", "green", "blue"), 255.0)
     return TriangleMesh(verts, tris if tris is not None else np.zeros((0, 3), np.int32), cols)
 
 

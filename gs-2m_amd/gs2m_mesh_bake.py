@@ -24,7 +24,7 @@ import torch
 
 import gs2m_native as N
 from gs2m_eval_util import ptr as _ptr
-from gs2m_mesh_cull import EPS, FAR, NEAR, VIEW_BATCH, _on_device, render_mesh_depth
+from gs2m_mesh_cull import EPS, FAR, NEAR, VIEW_BATCH, _mesh_on_device, _on_device, render_mesh_depth
 
 MAX_CHANNELS = 8
 MIN_WEIGHT = 1e-3                          # a vertex seen only at a grazing angle keeps the fallback
@@ -32,30 +32,29 @@ FALLBACK = (0.5, 0.5, 0.5, 1.0, 0.0)        # albedo, roughness, metallic of a v
 CHANNELS = ("albedo_r", "albedo_g", "albedo_b", "roughness", "metallic")
 
 
-class Baker:
-    """The running sums of a bake: `add` takes a batch of views with their maps, `finish` resolves.  The views may come in any
-    grouping; the result depends only on their order."""
+class _Bake:
+    """What the vertex bake and the texel bake (gs2m_mesh_texture.TextureBaker) share: the running sums and weights of `n` points,
+    the reused depth buffer of the mesh `v`, `f`, the checks of `maps` and `mask`, the accumulate launch and the fallback of
+    `finish`.  A subclass names itself in `who` and its accumulate entry in `entry`, says in `_points` where its points, normals
+    and owner are, and shapes the result in `finish`."""
+    who = entry = None
 
-    def __init__(self, vertices, triangles, channels, eps=EPS, use_normals=True, near=NEAR, far=FAR):
-        who = "Baker"
-        self.v = _on_device(vertices, "vertices", who, torch.float64, (3,))
-        self.f = _on_device(triangles, "triangles", who, torch.int32, (3,))
-        self.channels = int(channels)
+    def __init__(self, v, f, n, channels, eps, near, far):
+        self.v, self.f, self.n, self.channels = v, f, int(n), int(channels)
         if not 1 <= self.channels <= MAX_CHANNELS:
-            raise RuntimeError(f"{who}: invalid argument: {channels} channels; 1 to {MAX_CHANNELS}")
+            raise RuntimeError(f"{self.who}: invalid argument: {channels} channels; 1 to {MAX_CHANNELS}")
         self.eps, self.near, self.far = float(eps), float(near), float(far)
-        self.normals = None
-        if use_normals:
-            from gs2m_mesh_view import vertex_normals
-            self.normals = vertex_normals(self.v, self.f)[0]
-        dev = self.v.device
-        self.sums = torch.zeros((len(self.v), self.channels), dtype=torch.float64, device=dev)
-        self.weights = torch.zeros(len(self.v), dtype=torch.float64, device=dev)
+        self.sums = torch.zeros((self.n, self.channels), dtype=torch.float64, device=v.device)
+        self.weights = torch.zeros(self.n, dtype=torch.float64, device=v.device)
         self._depth = None
+
+    def _points(self):
+        """the entry's arguments between the number of points and the number of views"""
+        raise NotImplementedError
 
     def add(self, w2c, fx, fy, cx, cy, maps, mask=None):
         """w2c (n, 4, 4); maps (n, C, H, W) float32; mask (n, H, W) float32 or bool, or None: device tensors."""
-        who = "Baker.add"
+        who = f"{self.who}.add"
         m = _on_device(w2c, "w2c", who, torch.float64, (4, 4))
         a = N.f32(maps, "maps", who=who)
         if a.dim() != 4 or a.shape[0] != len(m) or a.shape[1] != self.channels:
@@ -69,21 +68,55 @@ class Baker:
         if self._depth is None or self._depth.numel() < len(m) * H * W:
             self._depth = torch.empty(len(m) * H * W, dtype=torch.float32, device=self.v.device)
         depth = render_mesh_depth(self.v, self.f, m, fx, fy, cx, cy, H, W, self.near, self.far, out=self._depth)
-        N.launch("gs2m_meshbake_accumulate", self.v.device, len(self.v), _ptr(self.v), _ptr(self.normals), len(m), _ptr(m), float(fx),
-                 float(fy), float(cx), float(cy), W, H, _ptr(depth), self.channels, _ptr(a), _ptr(k), self.eps, 1, _ptr(self.sums),
-                 _ptr(self.weights))
+        N.launch(self.entry, self.v.device, self.n, *self._points(), len(m), _ptr(m), float(fx), float(fy), float(cx), float(cy), W, H,
+                 _ptr(depth), self.channels, _ptr(a), _ptr(k), self.eps, 1, _ptr(self.sums), _ptr(self.weights))
+
+    def _resolve(self, entry, shape, min_weight, fallback, head=(), tail=()):
+        """-> (values `shape` + (C,) float32, seen `shape` bool) of entry(n, C, *head, sums, weights, min_weight, fallback, *tail,
+        values, seen)"""
+        fb = [0.0] * self.channels if fallback is None else [float(x) for x in fallback]
+        if len(fb) != self.channels:
+            raise RuntimeError(f"{self.who}.finish: {len(fb)} fallback values for {self.channels} channels")
+        out = torch.empty(tuple(shape) + (self.channels,), dtype=torch.float32, device=self.v.device)
+        seen = torch.empty(tuple(shape), dtype=torch.uint8, device=self.v.device)
+        N.launch(entry, self.v.device, self.n, self.channels, *head, _ptr(self.sums), _ptr(self.weights), float(min_weight),
+                 (C.c_float * self.channels)(*fb), *tail, _ptr(out), _ptr(seen))
+        return out, seen.bool()
+
+
+class Baker(_Bake):
+    """The running sums of a bake: `add` takes a batch of views with their maps, `finish` resolves.  The views may come in any
+    grouping; the result depends only on their order."""
+    who, entry = "Baker", "gs2m_meshbake_accumulate"
+
+    def __init__(self, vertices, triangles, channels, eps=EPS, use_normals=True, near=NEAR, far=FAR):
+        v = _on_device(vertices, "vertices", self.who, torch.float64, (3,))
+        f = _on_device(triangles, "triangles", self.who, torch.int32, (3,))
+        super().__init__(v, f, len(v), channels, eps, near, far)
+        self.normals = None
+        if use_normals:
+            from gs2m_mesh_view import vertex_normals
+            self.normals = vertex_normals(self.v, self.f)[0]
+
+    def _points(self):
+        return _ptr(self.v), _ptr(self.normals)
 
     def finish(self, min_weight=MIN_WEIGHT, fallback=None):
         """-> (values (V, C) float32, seen (V,) bool, weights (V,) float64)"""
-        fb = [0.0] * self.channels if fallback is None else [float(x) for x in fallback]
-        if len(fb) != self.channels:
-            raise RuntimeError(f"Baker.finish: {len(fb)} fallback values for {self.channels} channels")
-        dev = self.v.device
-        out = torch.empty((len(self.v), self.channels), dtype=torch.float32, device=dev)
-        seen = torch.empty(len(self.v), dtype=torch.uint8, device=dev)
-        N.launch("gs2m_meshbake_resolve", dev, len(self.v), self.channels, _ptr(self.sums), _ptr(self.weights), float(min_weight),
-                 (C.c_float * self.channels)(*fb), _ptr(out), _ptr(seen))
-        return out, seen.bool(), self.weights
+        return self._resolve("gs2m_meshbake_resolve", (self.n,), min_weight, fallback) + (self.weights,)
+
+
+def bake_slices(who, new_baker, w2c, fx, fy, cx, cy, maps, mask, view_batch):
+    """The views of one size and one set of intrinsics through new_baker(C), `view_batch` at a time (default 8) -> the baker"""
+    m = _on_device(w2c, "w2c", who, torch.float64, (4, 4))
+    a = N.f32(maps, "maps", who=who)
+    if a.dim() != 4 or a.shape[0] != len(m):
+        raise RuntimeError(f"{who}: `maps` must have shape (n_views, C, H, W) with n_views = {len(m)}, got {tuple(a.shape)}")
+    baker = new_baker(a.shape[1])
+    batch = max(1, min(int(view_batch or VIEW_BATCH), max(len(m), 1)))
+    for k in range(0, len(m), batch):
+        baker.add(m[k:k + batch], fx, fy, cx, cy, a[k:k + batch], None if mask is None else mask[k:k + batch])
+    return baker
 
 
 def bake_vertex_attributes(vertices, triangles, w2c, fx, fy, cx, cy, maps, mask=None, eps=EPS, use_normals=True, view_batch=None,
@@ -95,16 +128,8 @@ def bake_vertex_attributes(vertices, triangles, w2c, fx, fy, cx, cy, maps, mask=
     cosine between the vertex normal and the direction to its camera (and drop back-facing views); else every view weighs 1.
     -> (values (V, C) float32, `fallback` (default 0) where not seen; seen (V,) bool: weight >= min_weight and > 0; weights (V,)
     float64), on the device."""
-    who = "bake_vertex_attributes"
-    m = _on_device(w2c, "w2c", who, torch.float64, (4, 4))
-    a = N.f32(maps, "maps", who=who)
-    if a.dim() != 4 or a.shape[0] != len(m):
-        raise RuntimeError(f"{who}: `maps` must have shape (n_views, C, H, W) with n_views = {len(m)}, got {tuple(a.shape)}")
-    baker = Baker(vertices, triangles, a.shape[1], eps, use_normals, near, far)
-    batch = max(1, min(int(view_batch or VIEW_BATCH), max(len(m), 1)))
-    for k in range(0, len(m), batch):
-        baker.add(m[k:k + batch], fx, fy, cx, cy, a[k:k + batch], None if mask is None else mask[k:k + batch])
-    return baker.finish(min_weight, fallback)
+    new = lambda channels: Baker(vertices, triangles, channels, eps, use_normals, near, far)
+    return bake_slices("bake_vertex_attributes", new, w2c, fx, fy, cx, cy, maps, mask, view_batch).finish(min_weight, fallback)
 
 
 def unit_normal_planes(normal_map):
@@ -145,10 +170,14 @@ def bake_materials(gaussians, views, mesh, metallic=False, eps=EPS, use_normals=
     rendered with render(..., material_stage=True, blend_metallic=metallic), the render's normal_mask is the foreground, and the
     views are baked in runs of up to `view_batch` (default 8) that share size and intrinsics; nothing leaves the device between
     render and bake.  -> (values (V, 5) float32: albedo rgb, roughness, metallic; seen (V,) bool; weights (V,) float64)."""
-    dev = gaussians.get_xyz.device
-    v = torch.as_tensor(np.asarray(mesh.vertices, np.float64)).to(dev) if not torch.is_tensor(mesh.vertices) else mesh.vertices.to(dev)
-    f = torch.as_tensor(np.asarray(mesh.triangles, np.int32)).to(dev) if not torch.is_tensor(mesh.triangles) else mesh.triangles.to(dev)
-    baker = Baker(v, f, 5, eps, use_normals, near, far)
+    baker = Baker(*_mesh_on_device(mesh, gaussians.get_xyz.device, "bake_materials"), 5, eps, use_normals, near, far)
+    bake_runs(baker, views, lambda view: material_maps(gaussians, view, metallic), view_batch)
+    return baker.finish(min_weight, fallback)
+
+
+def bake_runs(baker, views, maps_of, view_batch=None):
+    """Adds `views` (cameras of the trainer) to `baker` in runs of up to `view_batch` (default 8) that share size and intrinsics;
+    maps_of(view) -> (maps (C, H, W), mask (H, W)) of one view."""
     batch = max(1, int(view_batch or VIEW_BATCH))
     run, key = [], None
 
@@ -165,10 +194,9 @@ def bake_materials(gaussians, views, mesh, metallic=False, eps=EPS, use_normals=
         if k != key or len(run) == batch:
             flush()
             key = k
-        maps, mask = material_maps(gaussians, view, metallic)
+        maps, mask = maps_of(view)
         run.append((view.world_view_transform.transpose(0, 1).to(torch.float64), maps, mask))
     flush()
-    return baker.finish(min_weight, fallback)
 
 
 # ---- files -------------------------------------------------------------------------------------------------------------------
@@ -215,42 +243,19 @@ def write_material_mesh(file, vertices, triangles, values, seen=None):
 def read_material_mesh(file):
     """-> dict(vertices (V, 3) float32, triangles (F, 3) int32, albedo (V, 3) float32 = the bytes / 255, roughness (V,) float32,
     metallic (V,) float32, seen (V,) bool).  ValueError, naming what is absent, for a PLY without the material properties."""
-    from gs2m_mesh import _PLY_TYPES
-    with open(str(file), "rb") as f:
-        data = f.read()
-    end = data.index(b"end_header\n") + len(b"end_header\n")
-    lines = data[:end].decode("ascii").split("\n")
-    if "format binary_little_endian 1.0" not in lines:
-        raise ValueError(f"{file}: not a binary little-endian PLY")
-    elems = []
-    for ln in lines:
-        p = ln.split()
-        if p and p[0] == "element":
-            elems.append([p[1], int(p[2]), []])
-        elif p and p[0] == "property":
-            elems[-1][2].append(p[1:])
-    off, out = end, {}
-    for name, n, props in elems:
-        if props and props[0][0] == "list":
-            dt = np.dtype([("n", _PLY_TYPES[props[0][1]]), ("v", _PLY_TYPES[props[0][2]], (3,))])
-            a = np.frombuffer(data, dt, n, off)
-            if n and not np.all(a["n"] == 3):
-                raise ValueError(f"{file}: only triangle faces are read")
-            if name == "face":
-                out["triangles"] = a["v"].astype(np.int32)
-        else:
-            dt = np.dtype([(q[1], _PLY_TYPES[q[0]]) for q in props])
-            a = np.frombuffer(data, dt, n, off)
-            if name == "vertex":
-                missing = [k for k in ("x", "y", "z", "red", "green", "blue", "roughness", "metallic") if k not in (a.dtype.names or ())]
-                if missing:
-                    raise ValueError(f"{file}: not a material mesh: the vertex properties {', '.join(missing)} are absent "
-                                     "(gs2m_mesh_bake.py writes them)")
-                out["vertices"] = np.stack([a[k].astype(np.float32) for k in "xyz"], axis=1) if n else np.zeros((0, 3), np.float32)
-                out["albedo"] = np.stack([a[k].astype(np.float32) / 255.0 for k in ("red", "green", "blue")], axis=1) if n else np.zeros((0, 3), np.float32)
-                out["roughness"], out["metallic"] = a["roughness"].astype(np.float32), a["metallic"].astype(np.float32)
-                out["seen"] = a["seen"].astype(bool) if "seen" in a.dtype.names else np.ones(n, bool)
-        off += dt.itemsize * n
+    from gs2m_mesh import _ply_columns, _ply_elements
+    out = {}
+    for name, a, is_list in _ply_elements(file):
+        if is_list and name == "face":
+            out["triangles"] = a["v"].astype(np.int32)
+        elif not is_list and name == "vertex":
+            missing = [k for k in ("x", "y", "z", "red", "green", "blue", "roughness", "metallic") if k not in (a.dtype.names or ())]
+            if missing:
+                raise ValueError(f"{file}: not a material mesh: the vertex properties {', '.join(missing)} are absent "
+                                 "(gs2m_mesh_bake.py writes them)")
+            out["vertices"], out["albedo"] = _ply_columns(a, "xyz"), _ply_columns(a, ("red", "green", "blue"), 255.0)
+            out["roughness"], out["metallic"] = a["roughness"].astype(np.float32), a["metallic"].astype(np.float32)
+            out["seen"] = a["seen"].astype(bool) if "seen" in a.dtype.names else np.ones(len(a), bool)
     if "vertices" not in out:
         raise ValueError(f"{file}: no vertex element")
     out.setdefault("triangles", np.zeros((0, 3), np.int32))

@@ -46,6 +46,15 @@ def _mesh_args(vertices, triangles, w2c, who):
     return v, f, m
 
 
+def _mesh_on_device(mesh, device, who):
+    """a mesh -- anything with .vertices and .triangles as numpy arrays or tensors -> its checked (vertices (V, 3) float64,
+    triangles (F, 3) int32) on `device`"""
+    v, f = mesh.vertices, mesh.triangles
+    v = v.to(device) if torch.is_tensor(v) else torch.as_tensor(np.asarray(v, np.float64)).to(device)
+    f = f.to(device) if torch.is_tensor(f) else torch.as_tensor(np.asarray(f, np.int32)).to(device)
+    return _on_device(v, "vertices", who, torch.float64, (3,)), _on_device(f, "triangles", who, torch.int32, (3,))
+
+
 def render_mesh_depth(vertices, triangles, w2c, fx, fy, cx, cy, H, W, near=NEAR, far=FAR, out=None):
     """The mesh's depth from every view: (n_views, H, W) float32 on the device, the camera-space z of the nearest surface through
     each pixel centre (i + 0.5, j + 0.5), 0 where there is none.  vertices (V, 3), triangles (F, 3), w2c (n_views, 4, 4)
@@ -147,8 +156,7 @@ def cull_file(ply_path, traj_path, out_path=None, opengl=False, width=TNT_WIDTH,
     dev = _dev(device)
     mesh = M.read_mesh(ply_path)
     w2c = world_to_camera(read_trajectory(traj_path), opengl)
-    v = torch.as_tensor(np.asarray(mesh.vertices, np.float64)).to(dev)
-    f = torch.as_tensor(np.asarray(mesh.triangles, np.int32)).to(dev)
+    v, f = _mesh_on_device(mesh, dev, "cull_file")
     c = torch.zeros_like(v) if mesh.vertex_colors is None else torch.as_tensor(np.asarray(mesh.vertex_colors, np.float64).reshape(-1, 3)).to(dev)
     cv, cf, cc, votes = cull_mesh_by_visibility(v, f, torch.as_tensor(w2c).to(dev), fx, fy, cx, cy, height, width, near, far, eps,
                                                 min_views, view_batch, colors=c)

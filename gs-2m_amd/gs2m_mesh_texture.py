@@ -32,8 +32,8 @@ import torch
 import gs2m_native as N
 from gs2m_eval_util import ptr as _ptr
 from gs2m_eval_util import workspace_for
-from gs2m_mesh_bake import FALLBACK, MAX_CHANNELS, MIN_WEIGHT
-from gs2m_mesh_cull import EPS, FAR, NEAR, VIEW_BATCH, _on_device, render_mesh_depth
+from gs2m_mesh_bake import FALLBACK, MAX_CHANNELS, MIN_WEIGHT, _Bake, bake_runs, bake_slices
+from gs2m_mesh_cull import EPS, FAR, NEAR, VIEW_BATCH, _mesh_on_device, _on_device
 
 CLASSES = 6
 MAX_WIDTH = 16384
@@ -48,13 +48,6 @@ class Atlas:
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
-
-
-def _mesh_tensors(mesh, device, who):
-    v, f = mesh.vertices, mesh.triangles
-    v = v.to(device) if torch.is_tensor(v) else torch.as_tensor(np.asarray(v, np.float64)).to(device)
-    f = f.to(device) if torch.is_tensor(f) else torch.as_tensor(np.asarray(f, np.int32)).to(device)
-    return _on_device(v, "vertices", who, torch.float64, (3,)), _on_device(f, "triangles", who, torch.int32, (3,))
 
 
 def atlas_count(vertices, triangles, density):
@@ -116,7 +109,7 @@ def build_atlas(mesh, density=None, texture_size=None, device="cuda"):
     who = "build_atlas"
     if (density is None) == (texture_size is None):
         raise ValueError(f"{who}: give one of `density` and `texture_size`")
-    v, f = _mesh_tensors(mesh, device, who)
+    v, f = _mesh_on_device(mesh, device, who)
     rung = None
     if density is None:
         density, rung = target_density(v, f, texture_size)
@@ -148,81 +141,42 @@ def atlas_texels(atlas, normals=None, row0=0, n_rows=None):
     return owner, interior.bool(), points, tn
 
 
-class TextureBaker:
+class TextureBaker(_Bake):
     """The running sums of a texel bake: `add` takes a batch of views with their maps, `finish` resolves -- gs2m_mesh_bake.Baker
     with the atlas's texels in the place of the vertices.  The views may come in any grouping; the result depends only on their
     order."""
+    who, entry = "TextureBaker", "gs2m_texbake_accumulate"
 
     def __init__(self, atlas, channels, eps=EPS, use_normals=True, near=NEAR, far=FAR):
-        self.atlas, self.channels = atlas, int(channels)
-        if not 1 <= self.channels <= MAX_CHANNELS:
-            raise RuntimeError(f"TextureBaker: invalid argument: {channels} channels; 1 to {MAX_CHANNELS}")
-        self.eps, self.near, self.far = float(eps), float(near), float(far)
-        self.use_normals = bool(use_normals)
+        super().__init__(atlas.vertices, atlas.triangles, atlas.width * atlas.height, channels, eps, near, far)
+        self.atlas, self.use_normals = atlas, bool(use_normals)
         vn = None
         if use_normals and len(atlas.triangles):
             from gs2m_mesh_view import vertex_normals
             vn = vertex_normals(atlas.vertices, atlas.triangles)[0]
         self.owner, self.interior, self.points, self.normals = atlas_texels(atlas, vn)
-        dev = atlas.vertices.device
-        self.n = atlas.width * atlas.height
-        self.sums = torch.zeros((self.n, self.channels), dtype=torch.float64, device=dev)
-        self.weights = torch.zeros(self.n, dtype=torch.float64, device=dev)
-        self._depth = None
 
-    def add(self, w2c, fx, fy, cx, cy, maps, mask=None):
-        """w2c (n, 4, 4); maps (n, C, H, W) float32; mask (n, H, W) float32 or bool, or None: device tensors."""
-        who = "TextureBaker.add"
-        a = self.atlas
-        m = _on_device(w2c, "w2c", who, torch.float64, (4, 4))
-        x = N.f32(maps, "maps", who=who)
-        if x.dim() != 4 or x.shape[0] != len(m) or x.shape[1] != self.channels:
-            raise RuntimeError(f"{who}: `maps` must have shape ({len(m)}, {self.channels}, H, W), got {tuple(x.shape)}")
-        H, W = int(x.shape[2]), int(x.shape[3])
-        k = None
-        if mask is not None:
-            k = N.f32(mask.float() if torch.is_tensor(mask) and mask.dtype in (torch.bool, torch.uint8) else mask, "mask", who=who)
-            if k.numel() != len(m) * H * W:
-                raise RuntimeError(f"{who}: `mask` {tuple(k.shape)} does not match ({len(m)}, {H}, {W})")
-        if self._depth is None or self._depth.numel() < len(m) * H * W:
-            self._depth = torch.empty(len(m) * H * W, dtype=torch.float32, device=a.vertices.device)
-        depth = render_mesh_depth(a.vertices, a.triangles, m, fx, fy, cx, cy, H, W, self.near, self.far, out=self._depth)
-        N.launch("gs2m_texbake_accumulate", a.vertices.device, self.n, _ptr(self.points), _ptr(self.normals) if self.use_normals else None,
-                 _ptr(self.owner), len(m), _ptr(m), float(fx), float(fy), float(cx), float(cy), W, H, _ptr(depth), self.channels, _ptr(x),
-                 _ptr(k), self.eps, 1, _ptr(self.sums), _ptr(self.weights))
+    def _points(self):
+        return _ptr(self.points), _ptr(self.normals) if self.use_normals else None, _ptr(self.owner)
 
     def finish(self, min_weight=MIN_WEIGHT, fallback=None, attributes=None):
         """attributes: (V, C) float32 per-vertex values that owned texels no view reached interpolate, or None for the fallback.
         -> (values (H, W, C) float32, seen (H, W) bool, weights (H, W) float64)"""
         a = self.atlas
-        fb = [0.0] * self.channels if fallback is None else [float(x) for x in fallback]
-        if len(fb) != self.channels:
-            raise RuntimeError(f"TextureBaker.finish: {len(fb)} fallback values for {self.channels} channels")
-        dev = a.vertices.device
         att = None
         if attributes is not None:
             att = N.f32(attributes, "attributes", (len(a.vertices), self.channels), who="TextureBaker.finish")
-        out = torch.empty((a.height, a.width, self.channels), dtype=torch.float32, device=dev)
-        seen = torch.empty((a.height, a.width), dtype=torch.uint8, device=dev)
-        N.launch("gs2m_texbake_resolve", dev, self.n, self.channels, max(a.width, 1), 0, _ptr(self.sums), _ptr(self.weights), float(min_weight),
-                 (C.c_float * self.channels)(*fb), _ptr(self.owner), len(a.triangles), _ptr(a.triangles), _ptr(a.cells), len(a.vertices),
-                 _ptr(att), _ptr(out), _ptr(seen))
-        return out, seen.bool(), self.weights.reshape(a.height, a.width)
+        return self._resolve("gs2m_texbake_resolve", (a.height, a.width), min_weight, fallback, (max(a.width, 1), 0),
+                             (_ptr(self.owner), len(a.triangles), _ptr(a.triangles), _ptr(a.cells), len(a.vertices), _ptr(att))
+                             ) + (self.weights.reshape(a.height, a.width),)
 
 
 def bake_texel_attributes(atlas, w2c, fx, fy, cx, cy, maps, mask=None, eps=EPS, use_normals=True, view_batch=None, min_weight=MIN_WEIGHT,
                           fallback=None, attributes=None, near=NEAR, far=FAR):
     """Per-texel averages of the views' attribute maps: gs2m_mesh_bake.bake_vertex_attributes for the texels of `atlas`.  The
     result does not depend on `view_batch`, bit for bit.  -> (values (H, W, C) float32, seen (H, W) bool, weights (H, W) float64)"""
-    m = _on_device(w2c, "w2c", "bake_texel_attributes", torch.float64, (4, 4))
-    a = N.f32(maps, "maps", who="bake_texel_attributes")
-    if a.dim() != 4 or a.shape[0] != len(m):
-        raise RuntimeError(f"bake_texel_attributes: `maps` must have shape (n_views, C, H, W) with n_views = {len(m)}, got {tuple(a.shape)}")
-    baker = TextureBaker(atlas, a.shape[1], eps, use_normals, near, far)
-    batch = max(1, min(int(view_batch or VIEW_BATCH), max(len(m), 1)))
-    for k in range(0, len(m), batch):
-        baker.add(m[k:k + batch], fx, fy, cx, cy, a[k:k + batch], None if mask is None else mask[k:k + batch])
-    return baker.finish(min_weight, fallback, attributes)
+    new = lambda channels: TextureBaker(atlas, channels, eps, use_normals, near, far)
+    return bake_slices("bake_texel_attributes", new, w2c, fx, fy, cx, cy, maps, mask, view_batch).finish(min_weight, fallback, attributes)
 
 
 def rgb_maps(gaussians, view, normal=False):
@@ -244,7 +198,7 @@ def bake_textures(gaussians, views, mesh, atlas, metallic=False, rgb=False, eps=
                   min_weight=MIN_WEIGHT, fallback=None, attributes=None, near=NEAR, far=FAR, normal_map=False):
     """The model's albedo, roughness and metallic (gs2m_mesh_bake.material_maps), or with rgb=True its plain render, in the texels
     of `atlas` (build_atlas(mesh, ...)).  Views are baked in runs of up to `view_batch` that share size and intrinsics, with the
-    principal-point shift of bake_materials.  Texels no view reached take `attributes` (V, C) interpolated, else `fallback`.
+    principal-point shift of gs2m_mesh_bake.bake_runs.  Texels no view reached take `attributes` (V, C) interpolated, else `fallback`.
     normal_map: three more planes, the views' unit world-space normals averaged like the others (for pack_normal_map; the mean is
     not unit); `attributes` and `fallback` keep their 5 or 3 columns and are padded with zeros there, so that a texel no view
     reached carries a zero normal and encodes flat.
@@ -259,26 +213,8 @@ def bake_textures(gaussians, views, mesh, atlas, metallic=False, rgb=False, eps=
             att = N.f32(attributes, "attributes", (len(atlas.vertices), materials), who="bake_textures")
             attributes = torch.cat([att, torch.zeros((len(att), 3), dtype=torch.float32, device=att.device)], 1).contiguous()
     baker = TextureBaker(atlas, channels, eps, use_normals, near, far)
-    batch = max(1, int(view_batch or VIEW_BATCH))
-    run, key = [], None
-
-    def flush():
-        if run:
-            _, _, fx, fy, cx, cy = key  # (pixel (i, j) of a render is the ray through (i + 0.5, j + 0.5): see bake_materials)
-            baker.add(torch.stack([r[0] for r in run]), fx, fy, cx - 0.5, cy - 0.5, torch.stack([r[1] for r in run]), torch.stack([r[2] for r in run]))
-            run.clear()
-
-    for view in views:
-        k = (int(view.image_height), int(view.image_width), float(view.Fx), float(view.Fy), float(view.Cx), float(view.Cy))
-        if k != key or len(run) == batch:
-            flush()
-            key = k
-        if normal_map:
-            maps, mask = rgb_maps(gaussians, view, True) if rgb else material_maps(gaussians, view, metallic, True)
-        else:
-            maps, mask = rgb_maps(gaussians, view) if rgb else material_maps(gaussians, view, metallic)
-        run.append((view.world_view_transform.transpose(0, 1).to(torch.float64), maps, mask))
-    flush()
+    maps_of = lambda view: rgb_maps(gaussians, view, normal_map) if rgb else material_maps(gaussians, view, metallic, normal_map)
+    bake_runs(baker, views, maps_of, view_batch)
     return baker.finish(min_weight, fallback, attributes)
 
 

@@ -31,7 +31,7 @@ import torch
 
 import gs2m_native as N
 from gs2m_eval_util import device as _dev, ptr as _ptr, workspace_for
-from gs2m_mesh_cull import FAR, NEAR, _mesh_args, _on_device
+from gs2m_mesh_cull import FAR, NEAR, _mesh_args, _mesh_on_device, _on_device
 
 VIS_BUDGET = 512 << 20  # bytes of visibility buffer a batch of views may take
 BASE, AMBIENT, DIFFUSE = (0.7, 0.7, 0.7), 0.15, 0.85
@@ -101,21 +101,47 @@ def shade_views(vertices, triangles, w2c, fx, fy, cx, cy, H, W, ss=2, shading="f
         raise RuntimeError(f"{who}: `base` must hold three values")
     dev, n = v.device, len(m)
     normals = vertex_normals(v, f)[0] if shading == "smooth" else None
-    per_view = 8 * H * W * ss * ss
-    batch = int(view_batch) if view_batch else max(1, VIS_BUDGET // max(per_view, 1))
-    batch = max(1, min(batch, max(n, 1)))
     rgba = torch.empty((n, H, W, 4), dtype=torch.uint8, device=dev)
     depth = torch.empty((n, H, W), dtype=torch.float32, device=dev) if return_aux else None
     tri_id = torch.empty((n, H, W), dtype=torch.int32, device=dev) if return_aux else None
-    buf = torch.empty(batch * H * W * ss * ss, dtype=torch.int64, device=dev)
-    for k in range(0, max(n, 1), batch):  # (with no view one call still checks the arguments and the indices)
-        part = m[k:k + batch]
-        vis = visibility_buffer(v, f, part, fx, fy, cx, cy, H, W, ss, near, far, out=buf)
+    # (with no view one call still checks the arguments and the indices)
+    for k, part, vis in _view_batches(v, f, m, fx, fy, cx, cy, H, W, ss, near, far, 8 * H * W * ss * ss, view_batch, max(n, 1)):
         N.launch("gs2m_meshview_shade", dev, len(v), _ptr(v), len(f), _ptr(f), len(part), _ptr(part), float(fx), float(fy), float(cx),
                  float(cy), W, H, ss, _ptr(vis), _ptr(normals), _ptr(col), base[0], base[1], base[2], float(ambient), float(diffuse),
-                 1 if srgb else 0, _ptr(rgba[k:k + batch]), None if depth is None else _ptr(depth[k:k + batch]),
-                 None if tri_id is None else _ptr(tri_id[k:k + batch]))
+                 1 if srgb else 0, _ptr(rgba[k]), None if depth is None else _ptr(depth[k]), None if tri_id is None else _ptr(tri_id[k]))
     return (rgba, depth, tri_id) if return_aux else rgba
+
+
+GBUFFER_BYTES = 8 + 4 * 14 + 1  # per sample: the key, the G-buffer and the shaded sample, the coverage
+
+
+def _view_batches(v, f, m, fx, fy, cx, cy, H, W, ss, near, far, per_view, view_batch, stop=None):
+    """The views `m` through the rasterizer `view_batch` at a time (default: as many as keep `per_view` bytes each under
+    VIS_BUDGET) into one reused visibility buffer -> (the batch's slice of the views, its w2c, its visibility buffer), one
+    batch after the other.  stop: the views end there (default: at len(m))."""
+    n = len(m)
+    batch = int(view_batch) if view_batch else max(1, VIS_BUDGET // max(per_view, 1))
+    batch = max(1, min(batch, max(n, 1)))
+    buf = torch.empty(batch * H * W * ss * ss, dtype=torch.int64, device=v.device)
+    for k in range(0, n if stop is None else stop, batch):
+        part = m[k:k + batch]
+        yield slice(k, k + batch), part, visibility_buffer(v, f, part, fx, fy, cx, cy, H, W, ss, near, far, out=buf)
+
+
+def _check_vis(vis, who, dev, n, H, W, ss):
+    if not torch.is_tensor(vis) or vis.device != dev or vis.dtype != torch.int64 or not vis.is_contiguous() or vis.numel() != n * H * W * ss * ss:
+        raise RuntimeError(f"{who}: `vis` must be the contiguous int64 visibility buffer of {n} views of {W * ss} x {H * ss} samples on {dev}")
+
+
+GBUFFER_PLANES = (("normal", 3), ("view_dir", 3), ("albedo", 3), ("roughness", 1), ("metallic", 1))
+
+
+def _new_gbuffer(dev, n, H, W, ss):
+    """-> (the G-buffer dict of n views, uninitialised; its six pointers in the order of the C entries)"""
+    shape = (n, H * ss, W * ss)
+    g = {name: torch.empty(shape + (c,), dtype=torch.float32, device=dev) for name, c in GBUFFER_PLANES}
+    g["coverage"] = torch.empty(shape, dtype=torch.uint8, device=dev)
+    return g, tuple(_ptr(t) for t in g.values())
 
 
 def mesh_gbuffer(vertices, triangles, w2c, fx, fy, cx, cy, H, W, vis, albedo, roughness, metallic, ss=1, normals=None):
@@ -133,16 +159,11 @@ def mesh_gbuffer(vertices, triangles, w2c, fx, fy, cx, cy, H, W, vis, albedo, ro
     k = _on_device(metallic, "metallic", who, torch.float32, ())
     if not len(a) == len(r) == len(k) == len(v):
         raise RuntimeError(f"{who}: {len(a)} albedo, {len(r)} roughness and {len(k)} metallic values for {len(v)} vertices")
-    if not torch.is_tensor(vis) or vis.device != dev or vis.dtype != torch.int64 or not vis.is_contiguous() or vis.numel() != n * H * W * ss * ss:
-        raise RuntimeError(f"{who}: `vis` must be the contiguous int64 visibility buffer of {n} views of {W * ss} x {H * ss} samples on {dev}")
+    _check_vis(vis, who, dev, n, H, W, ss)
     nrm = None if normals is None else _on_device(normals, "normals", who, torch.float64, (3,))
-    shape = (n, H * ss, W * ss)
-    g = {name: torch.empty(shape + (c,), dtype=torch.float32, device=dev)
-         for name, c in (("normal", 3), ("view_dir", 3), ("albedo", 3), ("roughness", 1), ("metallic", 1))}
-    g["coverage"] = torch.empty(shape, dtype=torch.uint8, device=dev)
+    g, outputs = _new_gbuffer(dev, n, H, W, ss)
     N.launch("gs2m_meshview_gbuffer", dev, len(v), _ptr(v), len(f), _ptr(f), n, _ptr(m), float(fx), float(fy), float(cx), float(cy), W, H, ss,
-             _ptr(vis), _ptr(nrm), _ptr(a), _ptr(r), _ptr(k), _ptr(g["normal"]), _ptr(g["view_dir"]), _ptr(g["albedo"]), _ptr(g["roughness"]),
-             _ptr(g["metallic"]), _ptr(g["coverage"]))
+             _ptr(vis), _ptr(nrm), _ptr(a), _ptr(r), _ptr(k), *outputs)
     return g
 
 
@@ -169,16 +190,12 @@ def mesh_gbuffer_textured(vertices, triangles, uvs, w2c, fx, fy, cx, cy, H, W, v
     base = _image(base_color, "base_color", who, dev)
     o = None if orm is None else _image(orm, "orm", who, dev, base)
     nm = None if normal_map is None else _image(normal_map, "normal_map", who, dev, base)
-    if not torch.is_tensor(vis) or vis.device != dev or vis.dtype != torch.int64 or not vis.is_contiguous() or vis.numel() != n * H * W * ss * ss:
-        raise RuntimeError(f"{who}: `vis` must be the contiguous int64 visibility buffer of {n} views of {W * ss} x {H * ss} samples on {dev}")
+    _check_vis(vis, who, dev, n, H, W, ss)
     nrm = None if normals is None else _on_device(normals, "normals", who, torch.float64, (3,))
-    shape = (n, H * ss, W * ss)
-    g = {name: torch.empty(shape + (c,), dtype=torch.float32, device=dev)
-         for name, c in (("normal", 3), ("view_dir", 3), ("albedo", 3), ("roughness", 1), ("metallic", 1))}
-    g["coverage"] = torch.empty(shape, dtype=torch.uint8, device=dev)
+    g, outputs = _new_gbuffer(dev, n, H, W, ss)
     N.launch("gs2m_meshview_gbuffer_textured", dev, len(v), _ptr(v), len(f), _ptr(f), _ptr(uv), n, _ptr(m), float(fx), float(fy), float(cx),
              float(cy), W, H, ss, _ptr(vis), _ptr(nrm), int(base.shape[1]), int(base.shape[0]), _ptr(base), 1 if srgb else 0, _ptr(o), _ptr(nm),
-             _ptr(g["normal"]), _ptr(g["view_dir"]), _ptr(g["albedo"]), _ptr(g["roughness"]), _ptr(g["metallic"]), _ptr(g["coverage"]))
+             *outputs)
     return g
 
 
@@ -190,18 +207,11 @@ def shade_views_textured(vertices, triangles, uvs, w2c, fx, fy, cx, cy, H, W, ba
     who = "shade_views_textured"
     v, f, m = _mesh_args(vertices, triangles, w2c, who)
     H, W, ss = _check_frame(H, W, ss, who)
-    dev, n = v.device, len(m)
-    per_view = (8 + 4 * 14 + 1) * H * W * ss * ss
-    batch = int(view_batch) if view_batch else max(1, VIS_BUDGET // max(per_view, 1))
-    batch = max(1, min(batch, max(n, 1)))
-    rgba = torch.empty((n, H, W, 4), dtype=torch.uint8, device=dev)
-    buf = torch.empty(batch * H * W * ss * ss, dtype=torch.int64, device=dev)
-    for k in range(0, n, batch):
-        part = m[k:k + batch]
-        vis = visibility_buffer(v, f, part, fx, fy, cx, cy, H, W, ss, near, far, out=buf)
+    rgba = torch.empty((len(m), H, W, 4), dtype=torch.uint8, device=v.device)
+    for k, part, vis in _view_batches(v, f, m, fx, fy, cx, cy, H, W, ss, near, far, GBUFFER_BYTES * H * W * ss * ss, view_batch):
         g = mesh_gbuffer_textured(v, f, uvs, part, fx, fy, cx, cy, H, W, vis.reshape(-1), base_color, None, normal_map, texture_srgb, ss, normals)
         cos = (g["normal"] * g["view_dir"]).sum(-1, keepdim=True).abs()
-        rgba[k:k + batch] = resolve_rgb(g["albedo"] * (float(ambient) + float(diffuse) * cos), g["coverage"], ss, srgb)
+        rgba[k] = resolve_rgb(g["albedo"] * (float(ambient) + float(diffuse) * cos), g["coverage"], ss, srgb)
     return rgba
 
 
@@ -233,15 +243,16 @@ def pixel_view_dirs(w2c, fx, fy, cx, cy, H, W):
     return (-world / world.norm(dim=-1, keepdim=True)).to(torch.float32)
 
 
-def shade_views_pbr(vertices, triangles, w2c, fx, fy, cx, cy, H, W, light, albedo, roughness, metallic, ss=2, shading="smooth",
-                    gamma=False, background="none", view_batch=None, near=NEAR, far=FAR, gbuffer=None):
+def shade_views_pbr(vertices, triangles, w2c, fx, fy, cx, cy, H, W, light, albedo=None, roughness=None, metallic=None, ss=2,
+                    shading="smooth", gamma=False, background="none", view_batch=None, near=NEAR, far=FAR, textures=None):
     """Views of a material mesh under an environment light: (n_views, H, W, 4) uint8 on the device.  light: anything with
-    `.cubemap` (a CubemapLight) and `.brdf_lut`, e.g. gs2m_envmap.EnvLight; albedo (V, 3), roughness (V,), metallic (V,): float32
-    vertex attributes.  Per batch of views: the visibility buffer, the G-buffer of its samples, the project's fused split-sum
-    shading (pbr_shading_fused) on every sample, and the resolve over ss x ss samples; gamma: sRGB-encode the resolved colour.
-    background "none": straight alpha = the covered share of the pixel; "env": the environment along the pixel's ray
-    (gs2m_relight.environment_behind) under the alpha, which is then 255.  gbuffer: a function (views, vis, normals) -> the
-    G-buffer dict that takes mesh_gbuffer's place, e.g. around mesh_gbuffer_textured; the three vertex arrays are then unused."""
+    `.cubemap` (a CubemapLight) and `.brdf_lut`, e.g. gs2m_envmap.EnvLight.  The materials are either albedo (V, 3), roughness
+    (V,), metallic (V,), float32 vertex attributes, or `textures`: dict(uvs, base_color, and optionally orm, normal_map, srgb
+    (default True): what mesh_gbuffer_textured takes; normals: the mesh's own (V, 3) vertex normals, e.g. a .glb's, that smooth
+    shading then uses instead of vertex_normals).  Per batch of views: the visibility buffer, the G-buffer of its samples, the
+    project's fused split-sum shading (pbr_shading_fused) on every sample, and the resolve over ss x ss samples; gamma:
+    sRGB-encode the resolved colour.  background "none": straight alpha = the covered share of the pixel; "env": the environment
+    along the pixel's ray (gs2m_relight.environment_behind) under the alpha, which is then 255."""
     from pbr import pbr_shading_fused
     who = "shade_views_pbr"
     v, f, m = _mesh_args(vertices, triangles, w2c, who)
@@ -250,20 +261,19 @@ def shade_views_pbr(vertices, triangles, w2c, fx, fy, cx, cy, H, W, light, albed
         raise RuntimeError(f"{who}: `shading` must be 'flat' or 'smooth', got {shading!r}")
     if background not in ("none", "env"):
         raise RuntimeError(f"{who}: `background` must be 'none' or 'env', got {background!r}")
-    dev, n = v.device, len(m)
-    normals = vertex_normals(v, f)[0] if shading == "smooth" else None
-    per_view = (8 + 4 * 14 + 1) * H * W * ss * ss  # the keys, the G-buffer and the shaded samples
-    batch = int(view_batch) if view_batch else max(1, VIS_BUDGET // max(per_view, 1))
-    batch = max(1, min(batch, max(n, 1)))
-    rgba = torch.empty((n, H, W, 4), dtype=torch.uint8, device=dev)
-    buf = torch.empty(batch * H * W * ss * ss, dtype=torch.int64, device=dev)
+    t = textures
+    if (t is None) == (albedo is None and roughness is None and metallic is None):
+        raise RuntimeError(f"{who}: give the materials as `albedo`, `roughness` and `metallic`, or as `textures`")
+    normals = None
+    if shading == "smooth":
+        normals = t["normals"] if t is not None and t.get("normals") is not None else vertex_normals(v, f)[0]
+    rgba = torch.empty((len(m), H, W, 4), dtype=torch.uint8, device=v.device)
     with torch.no_grad():
         light.cubemap.build_mips()
-        for k in range(0, n, batch):
-            part = m[k:k + batch]
-            vis = visibility_buffer(v, f, part, fx, fy, cx, cy, H, W, ss, near, far, out=buf)
-            if gbuffer is not None:
-                g = gbuffer(part, vis.reshape(-1), normals)
+        for k, part, vis in _view_batches(v, f, m, fx, fy, cx, cy, H, W, ss, near, far, GBUFFER_BYTES * H * W * ss * ss, view_batch):
+            if t is not None:
+                g = mesh_gbuffer_textured(v, f, t["uvs"], part, fx, fy, cx, cy, H, W, vis.reshape(-1), t["base_color"], t.get("orm"),
+                                          t.get("normal_map"), t.get("srgb", True), ss, normals)
             else:
                 g = mesh_gbuffer(v, f, part, fx, fy, cx, cy, H, W, vis.reshape(-1), albedo, roughness, metallic, ss, normals)
             rgb = pbr_shading_fused(light.cubemap, g["normal"], g["view_dir"], g["albedo"], g["roughness"], metallic=g["metallic"],
@@ -273,7 +283,7 @@ def shade_views_pbr(vertices, triangles, w2c, fx, fy, cx, cy, H, W, light, albed
                 from gs2m_relight import environment_behind
                 dirs = pixel_view_dirs(part, fx, fy, cx, cy, H, W)
                 bg = torch.stack([environment_behind(light, d, gamma) for d in dirs]).contiguous()
-            rgba[k:k + batch] = resolve_rgb(rgb.reshape(len(part), H * ss, W * ss, 3), g["coverage"], ss, gamma, bg)
+            rgba[k] = resolve_rgb(rgb.reshape(len(part), H * ss, W * ss, 3), g["coverage"], ss, gamma, bg)
     return rgba
 
 
@@ -406,8 +416,7 @@ def _view_files(a, dev, mesh, tex):
             raise RuntimeError("--glb is drawn with --colour texture or --colour pbr")
         v, f = tex["vertices"], tex["triangles"]
     else:
-        v = torch.as_tensor(np.asarray(mesh.vertices, np.float64)).to(dev)
-        f = torch.as_tensor(np.asarray(mesh.triangles, np.int32)).to(dev)
+        v, f = _mesh_on_device(mesh, dev, "view_files")
     col = None
     if a.colour == "vertex":
         if mesh.vertex_colors is None:
@@ -429,37 +438,27 @@ def _view_files(a, dev, mesh, tex):
         from gs2m_mesh_bake import read_material_mesh
         if not a.envmap:
             raise RuntimeError("--colour pbr needs --envmap FILE.hdr")
+        srgb_tex = not getattr(a, "linear_texture", False)
         if tex is not None:
-            material = [None, None, None]
+            material = dict(textures=dict(tex, srgb=srgb_tex))
         else:
             try:
                 mm = read_material_mesh(a.ply_path)
             except ValueError as e:
                 raise RuntimeError(f"--colour pbr needs a material mesh (gs2m_mesh_bake.py writes one): {e}") from None
-            material = [torch.as_tensor(mm[k]).to(dev) for k in ("albedo", "roughness", "metallic")]
+            material = {k: torch.as_tensor(mm[k]).to(dev) for k in ("albedo", "roughness", "metallic")}
         light = EnvLight.from_hdr(a.envmap, a.env_res, a.env_samples, math.radians(a.env_rotation), a.exposure, device=dev)
         RL._check(light, "env", "normal")  # the light's size, as the relighting checks it
 
     def shade(w2c, k, H, W):
-        if tex is not None:
-            m = torch.as_tensor(np.ascontiguousarray(w2c)).to(dev)
-            vn = tex["normals"] if a.shading == "smooth" else None
-            srgb_tex = not getattr(a, "linear_texture", False)
-            if material is None:
-                return shade_views_textured(v, f, tex["uvs"], m, k["fx"], k["fy"], k["cx"], k["cy"], H, W, tex["base_color"], tex["normal_map"],
-                                            srgb_tex, ss=a.ss, normals=vn)
-
-            def gbuffer(part, vis, _):
-                return mesh_gbuffer_textured(v, f, tex["uvs"], part, k["fx"], k["fy"], k["cx"], k["cy"], H, W, vis, tex["base_color"], tex["orm"],
-                                             tex["normal_map"], srgb_tex, a.ss, vn)
-
-            return shade_views_pbr(v, f, m, k["fx"], k["fy"], k["cx"], k["cy"], H, W, light, None, None, None, ss=a.ss, shading="flat",
-                                   gamma=a.gamma, background=a.background, gbuffer=gbuffer)
+        m = torch.as_tensor(np.ascontiguousarray(w2c)).to(dev)
         if material is not None:
-            return shade_views_pbr(v, f, torch.as_tensor(np.ascontiguousarray(w2c)).to(dev), k["fx"], k["fy"], k["cx"], k["cy"], H, W, light,
-                                   *material, ss=a.ss, shading=a.shading, gamma=a.gamma, background=a.background)
-        return shade_views(v, f, torch.as_tensor(np.ascontiguousarray(w2c)).to(dev), k["fx"], k["fy"], k["cx"], k["cy"], H, W, ss=a.ss,
-                           shading=a.shading, colors=col)
+            return shade_views_pbr(v, f, m, k["fx"], k["fy"], k["cx"], k["cy"], H, W, light, ss=a.ss, shading=a.shading, gamma=a.gamma,
+                                   background=a.background, **material)
+        if tex is not None:
+            return shade_views_textured(v, f, tex["uvs"], m, k["fx"], k["fy"], k["cx"], k["cy"], H, W, tex["base_color"], tex["normal_map"],
+                                        not getattr(a, "linear_texture", False), ss=a.ss, normals=tex["normals"] if a.shading == "smooth" else None)
+        return shade_views(v, f, m, k["fx"], k["fy"], k["cx"], k["cy"], H, W, ss=a.ss, shading=a.shading, colors=col)
 
     if a.rendering:
         os.makedirs(os.path.join(out_dir, "views"), exist_ok=True)

@@ -122,6 +122,69 @@ def test_argument_handling():
         MB.bake_vertex_attributes(v, _cuda(c["tris"]), m, c["fx"], c["fy"], c["cx"], c["cy"], torch.zeros((3, 9, c["H"], c["W"]), device="cuda"))
 
 
+def _bake(c, maps, views, owner=None, sums=None, weights=None, masked=True, with_normals=True):
+    """one accumulate over views[a:b] of the case with `maps` (3, C, H, W): gs2m_meshbake_accumulate, or with `owner`
+    gs2m_texbake_accumulate on the vertices as its points -> (sums, weights)"""
+    a, b = views
+    V, ch = len(c["verts"]), maps.shape[1]
+    v, nrm, m = _cuda(c["verts"]), _cuda(c["normals"]), _cuda(c["w2c"][a:b])
+    depth, x, mask = _cuda(c["depth"][a:b]), _cuda(maps[a:b]), _cuda(c["mask"][a:b])
+    acc = 0 if sums is None else 1
+    sums = torch.full((V, ch), 7.0, dtype=torch.float64, device="cuda") if sums is None else sums.clone()
+    weights = torch.full((V,), 7.0, dtype=torch.float64, device="cuda") if weights is None else weights.clone()
+    head = (V, N.ptr(v), N.ptr(nrm) if with_normals else None)
+    tail = (b - a, N.ptr(m), c["fx"], c["fy"], c["cx"], c["cy"], c["W"], c["H"], N.ptr(depth), ch, N.ptr(x), N.ptr(mask) if masked else None,
+            c["eps"], acc, N.ptr(sums), N.ptr(weights))
+    if owner is None:
+        N.launch("gs2m_meshbake_accumulate", v.device, *head, *tail)
+    else:
+        N.launch("gs2m_texbake_accumulate", v.device, *head, N.ptr(owner), *tail)
+    torch.cuda.synchronize()
+    return sums, weights
+
+
+@pytest.mark.parametrize("with_normals", [True, False])
+@pytest.mark.parametrize("masked", [True, False])
+@pytest.mark.parametrize("channels", [1, 5, 8])
+def test_the_texel_bake_of_owned_points_is_the_vertex_bake(channels, masked, with_normals):
+    """gs2m_texbake_accumulate with the vertices as its points and every point owned gives the sums and weights of
+    gs2m_meshbake_accumulate bit for bit, in a first call and in an accumulating one; a point without an owner has zeros and
+    changes no other row.  gs2m_texbake_resolve without attributes, every point owned and one row as wide as the call, is
+    gs2m_meshbake_resolve."""
+    import ctypes as C
+    c = B.bake_case()
+    V = len(c["verts"])
+    maps = np.concatenate([c["maps"], c["maps"][:, 2::-1]], axis=1)[:, :channels]  # eight planes from the case's five
+    kw = dict(masked=masked, with_normals=with_normals)
+    owned = torch.zeros(V, dtype=torch.int32, device="cuda")
+    holes = owned.clone()
+    holes[::3] = -1
+    first = {}
+    for name, owner in (("vertex", None), ("owned", owned), ("holes", holes)):
+        first[name] = _bake(c, maps, (0, 2), owner, **kw)
+    assert (first["vertex"][1] > 0).any()
+    total = {}
+    for name, owner in (("vertex", None), ("owned", owned), ("holes", holes)):
+        total[name] = _bake(c, maps, (2, 3), owner, *first[name], **kw)
+    for stage in (first, total):
+        for k in range(2):
+            assert torch.equal(stage["owned"][k], stage["vertex"][k])
+            assert (stage["holes"][k][::3] == 0).all()
+            keep = torch.ones(V, dtype=torch.bool, device="cuda")
+            keep[::3] = False
+            assert torch.equal(stage["holes"][k][keep], stage["vertex"][k][keep])
+    # resolve
+    s, w = total["vertex"]
+    fb = [0.25 + 0.1 * k for k in range(channels)]
+    out, seen, _ = _resolve(s, w, 0.3, fb)
+    tout = torch.full((V, channels), -3.0, dtype=torch.float32, device="cuda")
+    tseen = torch.full((V,), 9, dtype=torch.uint8, device="cuda")
+    N.launch("gs2m_texbake_resolve", s.device, V, channels, V, 0, N.ptr(s), N.ptr(w), 0.3, (C.c_float * channels)(*fb), N.ptr(owned), 0, None, None,
+             0, None, N.ptr(tout), N.ptr(tseen))
+    assert seen.any() and not seen.all()
+    assert torch.equal(tout, out) and torch.equal(tseen.bool(), seen)
+
+
 # ---- G-buffer and resolve ------------------------------------------------------------------------------------------------------
 
 def _ulps(got, want):

@@ -29,11 +29,16 @@ def add_ingest_arguments(ap):
                     "(Pillow's default filter, loadCam's size), masks and alpha masks, on the GPU")
     ap.add_argument("--masks", default="", help="--device-ingest: folder of <stem>.png foreground masks (absolute, or relative to the dataset)")
     ap.add_argument("--mask_gt", action="store_true", help="--device-ingest: multiply the images by their masks before the resize")
+    ap.add_argument("--undistort", action="store_true", help="--device-ingest: undistort a SIMPLE_RADIAL / RADIAL / OPENCV / FULL_OPENCV model in memory "
+                    "(gs2m_undistort): PINHOLE cameras, the images warped on the GPU in front of the resize, the valid mask as the alpha mask; "
+                    "--masks then holds masks of the undistorted images")
 
 
 def ingest_keywords(a):
     """load_colmap_dataset's keywords for the flags of add_ingest_arguments"""
-    return dict(ingest="device" if a.device_ingest else "host", masks=a.masks, mask_gt=a.mask_gt)
+    if a.undistort and not a.device_ingest:
+        raise ValueError("--undistort needs --device-ingest: the images are warped on the GPU, the host route reads undistorted datasets only")
+    return dict(ingest="undistort" if a.undistort else ("device" if a.device_ingest else "host"), masks=a.masks, mask_gt=a.mask_gt)
 
 
 def target_resolution(orig_w, orig_h, resolution, resolution_scale=1.0):

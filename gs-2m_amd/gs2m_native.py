@@ -253,6 +253,10 @@ SIGNATURES = {
     "gs2m_hdr_decode": (i, [p, ll, i, i, p, p, s]),
     "gs2m_hdr_encode": (i, [i, i, p, p, s]),
     "gs2m_latlong_to_cubemap": (i, [i, i, p, i, i, f, f, p, s]),
+    # include/gs2m_undistort.h
+    "gs2m_undistort_camera": (i, [i, i, i, p, d, d, d, p, p, p]),
+    "gs2m_undistort_images_u8": (i, [i, p, i, i, i, i, p, p, i, i, p, p, s]),
+    "gs2m_undistort_points": (i, [ll, p, i, p, p, p, p, s]),
 }
 del p, i, f, d, ll, ull, A, s
 EXPORTS = tuple(SIGNATURES)

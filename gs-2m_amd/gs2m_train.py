@@ -129,21 +129,39 @@ def export_colmap_dataset(folder, scene):
                   (np.asarray(cols) * 255.0 + 0.5).astype(np.uint8))
 
 
-def _device_view(info, path, mask_dir, device, resolution, mask_gt, ncc_scale):
+def _undistorted_image(img, undist, device):
+    """`--undistort`: the decoded RGB / RGBA image of the distorted camera -> (image (H', W', 3) uint8 on the device, mask (H', W')
+    uint8 on the device): the warped alpha channel where the file has one, the valid mask of the warp otherwise."""
+    import numpy as np
+    import gs2m_undistort
+    cam, out_cam = undist
+    a = torch.from_numpy(np.array(img)).to(device)
+    rgb, valid = gs2m_undistort.undistort_images(a[:, :, :3].contiguous(), cam, out_cam, valid=True)
+    if a.shape[2] == 4:
+        return rgb, gs2m_undistort.undistort_images(a[:, :, 3:4].contiguous(), cam, out_cam)[:, :, 0]
+    return rgb, valid
+
+
+def _device_view(info, path, mask_dir, device, resolution, mask_gt, ncc_scale, undist=None):
     """One view of load_colmap_dataset(ingest="device"): loadCam + Camera.__init__ (utils/camera_utils.py:19-48,
     scene/cameras.py:49-56) through gs2m_ingest, one upload for the training image, the mask and the gray image.
+    `undist`: (the image's distorted camera, its undistorted one) -- the image is warped between the upload and the resize.
     -> (camera with alpha_mask [and gray_image], ground-truth image)"""
     from PIL import Image as PILImage
     import gs2m_ingest
     with PILImage.open(path) as f:
         img = f.copy()
-    assert img.size == (info.width, info.height), "image size differs from the COLMAP camera"
+    size = (info.width, info.height) if undist is None else (undist[0].width, undist[0].height)
+    assert img.size == size, "image size differs from the COLMAP camera"
     if img.mode not in ("RGB", "RGBA"):
         raise ValueError(f"load_colmap_dataset: {path} has mode {img.mode}; the device ingestion trains on 8-bit RGB and RGBA images")
     mask = None
     if mask_dir != "":  # scene/dataset_readers.py:97-101
         with PILImage.open(os.path.join(mask_dir, os.path.splitext(os.path.basename(info.image_name))[0] + ".png")) as f:
             mask = f.convert("L")
+    if undist is not None:  # a mask file is one of the undistorted image; without one the warp's own mask is the alpha mask
+        img, own = _undistorted_image(img, undist, device)
+        mask = own if mask is None else mask
     w, h = gs2m_ingest.target_resolution(info.width, info.height, resolution)
     staged = gs2m_ingest.stage(img, mask_gt, mask, device, name=path)
     gray_res = None if ncc_scale is None else (int(w / ncc_scale), int(h / ncc_scale))
@@ -165,24 +183,38 @@ def load_colmap_dataset(folder, images="images", device="cuda", resolution=1, *,
     `ingest="device"`: the images go through gs2m_ingest -- the reference's resize filter and target size,
     `masks` (a folder of <stem>.png, absolute or relative to the dataset) or the alpha channel of RGBA images, `mask_gt` -- and
     every camera gets `alpha_mask` (ones without a mask, scene/cameras.py:54) and, with `ncc_scale` not None, `gray_image` at
-    (int(w / ncc_scale), int(h / ncc_scale)) from the same upload (scene/__init__.py:193-204)."""
+    (int(w / ncc_scale), int(h / ncc_scale)) from the same upload (scene/__init__.py:193-204).
+    `ingest="undistort"`: the device route on a distorted model -- a SIMPLE_RADIAL / RADIAL / OPENCV / FULL_OPENCV model is
+    undistorted in memory (gs2m_undistort): the cameras become PINHOLE, every image is warped on the device
+    between the upload and the resize, and where no mask file exists the warp's valid mask is the view's alpha mask; no file is
+    written.  It reads what the mapper leaves, `distorted/sparse/0` and `input/`, where the dataset has them, `sparse/0` and
+    `images` otherwise.  On the other two routes a distorted model raises."""
     import numpy as np
     from PIL import Image as PILImage
     import gs2m_colmap as C
-    if ingest not in ("host", "device"):
-        raise ValueError(f"load_colmap_dataset: ingest must be 'host' or 'device', got {ingest!r}")
+    if ingest not in ("host", "device", "undistort"):
+        raise ValueError(f"load_colmap_dataset: ingest must be 'host', 'device' or 'undistort', got {ingest!r}")
+    undistort, ingest = ingest == "undistort", ("device" if ingest == "undistort" else ingest)
     if ingest == "host":
         for flag, on in (("masks", masks != ""), ("mask_gt", mask_gt), ("ncc_scale", ncc_scale is not None)):
             if on:
                 raise ValueError(f"load_colmap_dataset: `{flag}` needs ingest='device' (--device-ingest); ingest='host' reads no masks and no gray images")
     sparse = os.path.join(folder, "sparse", "0")
+    if undistort and os.path.isfile(os.path.join(folder, "distorted", "sparse", "0", "cameras.bin")) and os.path.isdir(os.path.join(folder, "input")):
+        sparse, images = os.path.join(folder, "distorted", "sparse", "0"), "input"
     intr = C.read_intrinsics_binary(os.path.join(sparse, "cameras.bin"))
+    distorted = None
+    if undistort:
+        import gs2m_undistort
+        distorted = intr
+        intr, _ = gs2m_undistort.undistort_model(intr, {}, observations=False)
     infos = sorted(C.colmap_cameras(C.read_extrinsics_binary(os.path.join(sparse, "images.bin")), intr), key=lambda c: c.image_name)
     cams, gts = [], []
     mask_dir = "" if masks == "" else (masks if os.path.isabs(masks) else os.path.join(folder, masks))
     for info in infos:
         if ingest == "device":
-            cam, gt = _device_view(info, os.path.join(folder, images, info.image_name), mask_dir, device, resolution, mask_gt, ncc_scale)
+            undist = None if distorted is None or distorted[info.uid].model in ("SIMPLE_PINHOLE", "PINHOLE") else (distorted[info.uid], intr[info.uid])
+            cam, gt = _device_view(info, os.path.join(folder, images, info.image_name), mask_dir, device, resolution, mask_gt, ncc_scale, undist)
             cams.append(cam)
             gts.append(gt)
             continue

@@ -534,6 +534,8 @@ int gs2m_pack_features_forward(int P, const float* xyz, const float* scales, con
     if (P == 0) return GS2M_OK;
     if (!xyz || !scales || !rotations || !albedo || !roughness || !metallic || !campos || !view || !features)
         return GS2M_ERR_INVALID_ARG;
+    // the kernel reads `rotations` as float4 and writes the feature rows (40 bytes each) as float2
+    if ((((uintptr_t)rotations) & 15) || (((uintptr_t)features) & 7)) return GS2M_ERR_UNSUPPORTED;
     pack_features_kernel<<<(P + 255) / 256, 256, 0, (hipStream_t)stream>>>(P, xyz, scales, rotations, albedo, roughness,
                                                                           metallic, campos, view, z_depth,
                                                                           blend_metallic, features);
@@ -549,6 +551,8 @@ int gs2m_pack_features_backward(int P, const float* xyz, const float* scales, co
     if (!xyz || !scales || !rotations || !campos || !view || !dL_dfeatures || !dL_dxyz || !dL_drotations || !dL_dalbedo ||
         !dL_droughness || !dL_dmetallic)
         return GS2M_ERR_INVALID_ARG;
+    // float4 reads of `rotations` and writes of dL_drotations, float2 reads of the gradient rows (40 bytes each)
+    if (((((uintptr_t)rotations) | ((uintptr_t)dL_drotations)) & 15) || (((uintptr_t)dL_dfeatures) & 7)) return GS2M_ERR_UNSUPPORTED;
     pack_features_bwd_kernel<<<(P + 255) / 256, 256, 0, (hipStream_t)stream>>>(
         P, xyz, scales, rotations, campos, view, z_depth, blend_metallic, dL_dfeatures, dL_dxyz, dL_drotations,
         dL_dalbedo, dL_droughness, dL_dmetallic);

@@ -218,7 +218,8 @@ int gs2m_raster_backward_split_sh(int P, int D, int M, int R, const float* backg
  *   normalised) -> features (P,10) = [1, distance, normal(3), albedo(3), roughness, metallic | 0], distance =
  *   |n_cam . p_cam| or p_cam.z when z_depth.  `scales`, `rotations`, `albedo`, ... are the ACTIVATED values
  *   (pc.get_scaling, pc.get_rotation, ...).  The backward returns the gradients autograd would: xyz, rotations,
- *   albedo, roughness, metallic (scales only select the axis: no gradient). */
+ *   albedo, roughness, metallic (scales only select the axis: no gradient).  `rotations` and dL_drotations must be
+ *   16-byte aligned, `features` and dL_dfeatures 8-byte aligned: GS2M_ERR_UNSUPPORTED otherwise, nothing is launched. */
 int gs2m_pack_features_forward(int P, const float* xyz, const float* scales, const float* rotations, const float* albedo,
                                const float* roughness, const float* metallic, const float* campos, const float* view,
                                int z_depth, int blend_metallic, float* features, void* stream);

@@ -14,11 +14,16 @@
 //     entries) on frames of many tiles, a WORKGROUP per tile (1 to 16 elements per lane: up to 4096 entries) on frames of few tiles and
 //     for long spans everywhere; beyond 4096 entries sorted runs of 4096 from the same network, merged over global memory;
 //   * equal depths (coincident Gaussians: a quarter of a trained model's tiles hold such a pair): the network compares depths only;
-//     the members of a run of equal depths then look along the run for their place in span order = id order (tie_positions);
+//     the members of a run of equal depths then look along the run for their place in span order = id order (tie_position);
 //   * ids and rows wait in LDS under their span position and are picked up in sorted order, then ballots give every instance
 //     its place in each of the four quadrant lists with coalesced stores; the gradient row of a list entry = the instance's
 //     first row (relative to its emit wave, emit_kernel; absolute and flagged GS2M_ROWS_BIG for a heavy Gaussian's) + the wave's base
 //     (rowscan_kernel) + its quadrants before this one.
+// The pieces of a tile's work, shared by the wave, the workgroup and the global-memory sort: tile_span / write_range (a tile's span
+// from ranges_raw; ranges[]), read_record (the 16-byte instance record), stage<E, STRIDE> (slots, records, LDS; sort_tile_wave holds
+// the same loop written out, for its registers), the network, settle<E, Scope> (row bases, pick-up, ties, parking; WaveScope /
+// WorkgroupScope: barrier, vote, neighbour's key), tie_position (the tie rule, over LDS or global memory), qlist_step / write_qlist
+// (the quadrant lists).
 #include "common.h"
 #include <atomic>
 #include <cstdlib>
@@ -147,40 +152,193 @@ __device__ __forceinline__ int skew(int p) { return p + (p >> 5); }  // LDS inde
 // they lie: with keys and span positions parked in sorted order (s_k, s_i), element i looks along its run and goes to
 // run start + the number of members with a smaller span position.  Linear in the run's length per member: coincident Gaussians come in
 // pairs; a tile whose instances ALL share one depth (the tests build such spans) still comes out right, in ~n^2 / lanes steps.
-template <int E>
+template <typename KeyAt, typename PosAt>  // key_at(j), pos_at(j): key and span position of the element at sorted position j (LDS or global memory)
+__device__ __forceinline__ uint32_t tie_position(const uint32_t i, const uint32_t K, const uint32_t X, const uint32_t n, KeyAt key_at, PosAt pos_at) {
+    uint32_t a = i, cnt = 0;
+    for (uint32_t j = i; j > 0u;) {
+        j--;
+        if (key_at(j) != K) break;
+        a = j;
+        cnt += pos_at(j) < X ? 1u : 0u;
+    }
+    for (uint32_t j = i + 1u; j < n; j++) {
+        if (key_at(j) != K) break;
+        cnt += pos_at(j) < X ? 1u : 0u;
+    }
+    return a + cnt;
+}
+template <int E>  // thread t's elements t E .. t E + E - 1, keys and span positions parked in LDS under skew(sorted position)
 __device__ __forceinline__ void tie_positions(const uint32_t (&key)[E], const uint32_t (&idx)[E], uint32_t (&pos)[E], const int t, const uint32_t n,
                                               const uint32_t* s_k, const uint32_t* s_i) {
 #pragma unroll
     for (int e = 0; e < E; e++) {
         const uint32_t i = (uint32_t)(t * E + e);
-        pos[e] = i;
-        if (i >= n) continue;
-        const uint32_t K = key[e], X = idx[e];
-        uint32_t a = i, cnt = 0;
-        for (uint32_t j = i; j > 0u;) {
-            j--;
-            if (s_k[skew((int)j)] != K) break;
-            a = j;
-            cnt += s_i[skew((int)j)] < X ? 1u : 0u;
-        }
-        for (uint32_t j = i + 1u; j < n; j++) {
-            if (s_k[skew((int)j)] != K) break;
-            cnt += s_i[skew((int)j)] < X ? 1u : 0u;
-        }
-        pos[e] = a + cnt;
+        pos[e] = i < n ? tie_position(i, key[e], idx[e], n, [&](uint32_t j) { return s_k[skew((int)j)]; }, [&](uint32_t j) { return s_i[skew((int)j)]; }) : i;
     }
 }
 
-// One tile by one wave: the span's emission slots (coalesced: span position p = e * 64 + lane sits in register e of lane `lane` --
-// the network sorts whatever arrangement it is given) and, through them, the 16-byte records (one gather each, 8 in flight per
-// lane); staging in LDS, the network, ties, the sorted list and the four quadrant lists.
+// ---- the instance record (BinningState::e_rec, written by emit_kernel / emit_heavy_kernel), read here and nowhere else -----------------
+struct Record {
+    uint32_t key;   // bit pattern of the view depth (> 0.2: never all ones, the padding's key)
+    uint32_t v;     // Gaussian id | quadrant mask << 28: what the lists carry
+    uint32_t row;   // first gradient row: relative to its emit wave's first row, or (a heavy Gaussian's instance) absolute
+    bool absolute;
+    uint32_t wave;  // a relative row's entry of wave_rowbase
+};
+__device__ __forceinline__ Record read_record(const uint4 rc) {
+    return {rc.z, rc.x, rc.y & ~GS2M_ROWS_BIG, (rc.y & GS2M_ROWS_BIG) != 0u, (rc.x & GS2M_GID_MASK) >> 6};
+}
+
+// ---- staging ------------------------------------------------------------------------------------------------------------------------
+// The span's emission slots (coalesced: span position p = e * STRIDE + t sits in register e of thread t of STRIDE -- the network
+// sorts whatever arrangement it is given) and, through them, the 16-byte records (one gather each, batches of up to 8 in flight per
+// lane: 32 registers of records, whatever E).  id | mask and the first row wait in LDS under their span position; the row's base
+// (rb, a dependent gather: the first row of the emit wave that owns the element) is asked for now and added behind the sort: its
+// latency disappears behind the network.
+template <int E, int STRIDE>
+__device__ __forceinline__ void stage(uint32_t (&key)[E], uint32_t (&idx)[E], uint32_t (&rb)[E], const int t, const uint32_t start, const uint32_t n,
+                                      const uint32_t* __restrict__ slot_sorted, const uint4* __restrict__ e_rec, const uint32_t* __restrict__ wave_rowbase,
+                                      uint32_t* s_v, uint32_t* s_r) {
+    constexpr int BATCH = E < 8 ? E : 8;
+    static_for<0, E / BATCH>([&](auto bc) {
+        constexpr int e0 = BATCH * decltype(bc)::value;
+        uint32_t slot[BATCH];
+#pragma unroll
+        for (int e = 0; e < BATCH; e++) {
+            const uint32_t p = (uint32_t)((e0 + e) * STRIDE + t);
+            slot[e] = p < n ? slot_sorted[start + p] : 0u;
+        }
+        uint4 rc[BATCH];
+#pragma unroll
+        for (int e = 0; e < BATCH; e++) rc[e] = (uint32_t)((e0 + e) * STRIDE + t) < n ? e_rec[slot[e]] : make_uint4(0u, 0u, 0xFFFFFFFFu, 0u);
+        static_for<0, BATCH>([&](auto ec) {
+            constexpr int e = decltype(ec)::value;
+            const uint32_t p = (uint32_t)((e0 + e) * STRIDE + t);
+            const Record r = read_record(rc[e]);
+            key[e0 + e] = r.key;
+            idx[e0 + e] = p;
+            s_v[skew((int)p)] = r.v;
+            s_r[skew((int)p)] = r.row;
+            rb[e0 + e] = p < n && !r.absolute ? wave_rowbase[r.wave] : 0u;
+        });
+        asm volatile("" ::: "memory");  // the next batch's loads stay behind this batch's staging (registers: one batch in flight)
+    });
+}
+
+// ---- behind the network ---------------------------------------------------------------------------------------------------------------
+// Who settles a sorted span: the lanes of one wave, or the 256 threads of a workgroup.  The two differ in their barrier, in the vote
+// "any thread has a tie", and in how a thread learns the first key of the thread to its right.
+struct WaveScope {
+    static constexpr int kThreads = GS2M_WAVE;
+    __device__ __forceinline__ void sync() const { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }  // (LDS operations of one wave execute in order)
+    __device__ __forceinline__ bool any(const bool p) const { return __builtin_amdgcn_ballot_w64(p) != 0ull; }  // (wave-uniform)
+    __device__ __forceinline__ uint32_t right_key(const uint32_t key0, const int) const {
+        sync();  // (closes the pick-up: the staging arrays are free)
+        return (uint32_t)__shfl_down((int)key0, 1, 64);
+    }
+};
+struct WorkgroupScope {
+    static constexpr int kThreads = 256;
+    uint32_t* s_x;  // the network's exchange array
+    __device__ __forceinline__ void sync() const { gs2m_sync(); }
+    __device__ __forceinline__ bool any(const bool p) const { return gs2m_sync_or(p) != 0; }  // (the barrier also closes the pick-up: the staging arrays are free)
+    __device__ __forceinline__ uint32_t right_key(const uint32_t key0, const int t) const {
+        s_x[t] = key0;
+        gs2m_sync();
+        return s_x[t + 1];  // (the last thread has no neighbour; the word it reads lies inside the array and is not looked at)
+    }
+};
+// The sorted span's ids and rows, picked up by span position (sorted element i = t * E + e, the network's index space) and parked again
+// under their sorted position -- a member of a run of equal depths under the position tie_positions gives it.  The caller's barrier
+// follows; s_v / s_r are then read position-major.
+template <int E, typename Scope>
+__device__ __forceinline__ void settle(const Scope sc, const uint32_t (&key)[E], const uint32_t (&idx)[E], const uint32_t (&rb)[E], const int t, const uint32_t n,
+                                       uint32_t* s_v, uint32_t* s_r) {
+#pragma unroll
+    for (int e = 0; e < E; e++) s_r[skew(e * Scope::kThreads + t)] += rb[e];  // (this thread parked it)
+    sc.sync();  // (the row bases added above)
+    uint32_t sv[E], sr[E];
+#pragma unroll
+    for (int e = 0; e < E; e++) {
+        const bool real = (uint32_t)(t * E + e) < n;  // (padding sorts behind every real element: idx < n for the first n)
+        sv[e] = real ? s_v[skew((int)idx[e])] : 0u;
+        sr[e] = real ? s_r[skew((int)idx[e])] : 0u;
+    }
+    // equal depths anywhere in the sorted span (neighbours inside a lane, across lanes, across waves): tie_positions above
+    bool tie = false;
+#pragma unroll
+    for (int e = 0; e + 1 < E; e++) tie |= (uint32_t)(t * E + e + 1) < n && key[e] == key[e + 1];
+    const uint32_t nxt = sc.right_key(key[0], t);
+    tie |= t < Scope::kThreads - 1 && (uint32_t)(t * E + E) < n && key[E - 1] == nxt;
+    if (sc.any(tie)) {  // (the pick-up is closed in either scope: sv / sr hold the staging arrays' content)
+#pragma unroll
+        for (int e = 0; e < E; e++) {
+            s_v[skew(t * E + e)] = key[e];
+            s_r[skew(t * E + e)] = idx[e];
+        }
+        sc.sync();
+        uint32_t pos[E];
+        tie_positions<E>(key, idx, pos, t, n, s_v, s_r);
+        sc.sync();  // every look along a run is done: the arrays take the payload
+#pragma unroll
+        for (int e = 0; e < E; e++) {
+            s_v[skew((int)pos[e])] = sv[e];
+            s_r[skew((int)pos[e])] = sr[e];
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < E; e++) {
+            s_v[skew(t * E + e)] = sv[e];
+            s_r[skew(t * E + e)] = sr[e];
+        }
+    }
+}
+
+// ---- the quadrant lists --------------------------------------------------------------------------------------------------------------
+// One step of one quadrant's list: of the 64 entries the wave holds (entry k = {v, r} in lane `lane`, v = 0 behind the span's end), those
+// that touch quadrant q go to the list in order; an entry's gradient row = the instance's first row + its quadrants before this one.
+__device__ __forceinline__ unsigned long long lanes_below(const int lane) { return lane == 0 ? 0ull : (~0ull >> (64 - lane)); }
+template <typename Index>  // the list starts at out[first] / orow[first] and holds `run` entries so far
+__device__ __forceinline__ void qlist_step(const int q, const uint32_t v, const uint32_t r, const uint32_t k, const unsigned long long lt,
+                                           uint2* __restrict__ out, uint32_t* __restrict__ orow, const Index first, uint32_t& run) {
+    const uint32_t mask = v >> GS2M_GID_BITS;
+    const bool hit = ((mask >> q) & 1u) != 0u;
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
+    if (hit) {
+        const Index o = first + run + (uint32_t)__popcll(m & lt);
+        out[o] = make_uint2(v, k);
+        orow[o] = r + (uint32_t)__popc(mask & ((1u << q) - 1u));
+    }
+    run += (uint32_t)__popcll(m);
+}
+// One wave compacts quadrant q of a sorted span of n entries; fetch(k) = {v, r} of sorted entry k.
+template <typename Fetch>
+__device__ __forceinline__ void write_qlist(const int tile, const int q, const uint32_t start, const uint32_t n, const int lane, Fetch fetch,
+                                            uint2* __restrict__ qlist, uint32_t* __restrict__ qrow, uint32_t* __restrict__ qcount) {
+    uint2* out = qlist + (size_t)4 * start + (size_t)q * n;
+    uint32_t* orow = qrow + (size_t)4 * start + (size_t)q * n;
+    uint32_t run = 0;
+    const unsigned long long lt = lanes_below(lane);
+    for (uint32_t base = 0; base < n; base += GS2M_WAVE) {
+        const uint32_t k = base + (uint32_t)lane;
+        const uint2 vr = k < n ? fetch(k) : make_uint2(0u, 0u);
+        qlist_step(q, vr.x, vr.y, k, lt, out, orow, 0u, run);
+    }
+    if (lane == 0) qcount[tile * 4 + q] = run;
+}
+
+// One tile by one wave: staging, the network, ties, the sorted list and the four quadrant lists (all four from one LDS read and one
+// point_list store per entry).
 template <int E, int LE>
 __device__ __forceinline__ void sort_tile_wave(const int tile, const uint32_t start, const uint32_t n, const uint32_t* __restrict__ slot_sorted,
                                                const uint4* __restrict__ e_rec, const uint32_t* __restrict__ wave_rowbase,
                                                uint32_t* __restrict__ point_list, uint2* __restrict__ qlist, uint32_t* __restrict__ qrow,
                                                uint32_t* __restrict__ qcount, uint32_t* s_v, uint32_t* s_r, const int lane) {
-    uint32_t key[E], idx[E], rb[E];  // rb: first row of the emit wave that owns the element at span position e * 64 + lane
-    static_for<0, E / 8>([&](auto bc) {  // batches of 8 elements per lane: 32 registers of records in flight, whatever E
+    const WaveScope sc;
+    uint32_t key[E], idx[E], rb[E];
+    // stage<E, GS2M_WAVE>, written out: with BOTH stage and settle as calls here the compiler gives tile_sort_wave_kernel 64 registers
+    // and 102 scalar ones instead of 52 / 66 -- seven waves per SIMD instead of eight (profiles/tile_sort_refactor.md)
+    static_for<0, E / 8>([&](auto bc) {
         constexpr int e0 = 8 * decltype(bc)::value;
         uint32_t slot[8];
 #pragma unroll
@@ -188,77 +346,29 @@ __device__ __forceinline__ void sort_tile_wave(const int tile, const uint32_t st
             const uint32_t p = (uint32_t)((e0 + e) * GS2M_WAVE + lane);
             slot[e] = p < n ? slot_sorted[start + p] : 0u;
         }
-        uint4 rc[8];  // {id | mask, relative first row, depth key, -}
+        uint4 rc[8];
 #pragma unroll
         for (int e = 0; e < 8; e++) rc[e] = (uint32_t)((e0 + e) * GS2M_WAVE + lane) < n ? e_rec[slot[e]] : make_uint4(0u, 0u, 0xFFFFFFFFu, 0u);
         static_for<0, 8>([&](auto ec) {
             constexpr int e = decltype(ec)::value;
             const uint32_t p = (uint32_t)((e0 + e) * GS2M_WAVE + lane);
-            key[e0 + e] = rc[e].z;  // (a real key is the bit pattern of a depth > 0.2: never all ones, the padding's key)
+            const Record r = read_record(rc[e]);
+            key[e0 + e] = r.key;
             idx[e0 + e] = p;
-            // id | mask and the first row wait in LDS under their span position; the row's base (a dependent gather) is asked
-            // for now and added behind the sort: its latency disappears behind the network
-            s_v[skew((int)p)] = rc[e].x;
-            s_r[skew((int)p)] = rc[e].y & ~GS2M_ROWS_BIG;
-            rb[e0 + e] = p < n && (rc[e].y & GS2M_ROWS_BIG) == 0u ? wave_rowbase[(rc[e].x & GS2M_GID_MASK) >> 6] : 0u;  // (a heavy instance's row is absolute)
+            s_v[skew((int)p)] = r.v;
+            s_r[skew((int)p)] = r.row;
+            rb[e0 + e] = p < n && !r.absolute ? wave_rowbase[r.wave] : 0u;
         });
         asm volatile("" ::: "memory");  // the next batch's loads stay behind this batch's staging (registers: one batch in flight)
     });
     // (the padding is spread over the lanes in this arrangement: every level runs)
     levels<E, LE, 1>(key, idx, lane, 0xFFFFFFFFu);
-#pragma unroll
-    for (int e = 0; e < E; e++) s_r[skew(e * GS2M_WAVE + lane)] += rb[e];
-    // ---- ids and rows of the sorted elements: picked up by span position (sorted element i = lane * E + e, the network's index space) ----
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    uint32_t sv[E], sr[E];
-    auto pick_up = [&]() {
-#pragma unroll
-        for (int e = 0; e < E; e++) {
-            const bool real = (uint32_t)(lane * E + e) < n;  // (padding sorts behind every real element: idx < n for the first n)
-            sv[e] = real ? s_v[skew((int)idx[e])] : 0u;
-            sr[e] = real ? s_r[skew((int)idx[e])] : 0u;
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    };
-    auto park = [&]() {  // parked again under their sorted position, read position-major below
-#pragma unroll
-        for (int e = 0; e < E; e++) {
-            s_v[skew(lane * E + e)] = sv[e];
-            s_r[skew(lane * E + e)] = sr[e];
-        }
-    };
-    pick_up();
-    // ---- equal depths (tie_positions above) ----
-    bool tie = false;
-#pragma unroll
-    for (int e = 0; e + 1 < E; e++) tie |= (uint32_t)(lane * E + e + 1) < n && key[e] == key[e + 1];
-    {
-        const uint32_t nxt = (uint32_t)__shfl_down((int)key[0], 1, 64);
-        tie |= lane < 63 && (uint32_t)(lane * E + E) < n && key[E - 1] == nxt;
-    }
-    if (__builtin_amdgcn_ballot_w64(tie) != 0ull) {  // (wave-uniform)
-#pragma unroll
-        for (int e = 0; e < E; e++) {  // (the staging arrays are free: their content is in sv / sr)
-            s_v[skew(lane * E + e)] = key[e];
-            s_r[skew(lane * E + e)] = idx[e];
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        uint32_t pos[E];
-        tie_positions<E>(key, idx, pos, lane, n, s_v, s_r);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-        for (int e = 0; e < E; e++) {
-            s_v[skew((int)pos[e])] = sv[e];
-            s_r[skew((int)pos[e])] = sr[e];
-        }
-    } else {
-        park();
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    settle<E>(sc, key, idx, rb, lane, n, s_v, s_r);
+    sc.sync();
     uint2* out = qlist + (size_t)4 * start;
     uint32_t* orow = qrow + (size_t)4 * start;
     uint32_t run[4] = {0u, 0u, 0u, 0u};
-    const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+    const unsigned long long lt = lanes_below(lane);
     for (uint32_t base = 0; base < n; base += GS2M_WAVE) {
         const uint32_t k = base + (uint32_t)lane;
         uint32_t v = 0, r = 0;
@@ -267,27 +377,17 @@ __device__ __forceinline__ void sort_tile_wave(const int tile, const uint32_t st
             r = s_r[skew((int)k)];
             point_list[start + k] = v;
         }
-        const uint32_t mask = v >> GS2M_GID_BITS;  // 0 for k >= n
 #pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const bool hit = ((mask >> q) & 1u) != 0u;
-            const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
-            if (hit) {
-                const size_t o = (size_t)q * n + run[q] + (uint32_t)__popcll(m & lt);
-                out[o] = make_uint2(v, k);
-                orow[o] = r + (uint32_t)__popc(mask & ((1u << q) - 1u));
-            }
-            run[q] += (uint32_t)__popcll(m);
-        }
+        for (int q = 0; q < 4; q++) qlist_step(q, v, r, k, lt, out, orow, (size_t)q * n, run[q]);
     }
     if (lane < 4) qcount[tile * 4 + lane] = lane == 0 ? run[0] : (lane == 1 ? run[1] : (lane == 2 ? run[2] : run[3]));
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the LDS arrays are the next tile's from here on
+    sc.sync();  // the LDS arrays are the next tile's from here on
 }
 
 // Which tile a one-wave workgroup takes: workgroup ids go round the 8 XCDs (each with its own L2), and the records a tile gathers are
 // 16 bytes out of a 64-byte sector whose other three records usually belong to the SAME Gaussian's instances in the neighbouring
-// tiles (emit_kernel writes a Gaussian's instances to consecutive slots).  So the four tiles of a 2 x 2 block run back to back on
-// ONE XCD: the sector one of them pulls in is in that L2 when the others ask for it (4 x 4 tiles since the measurement below).  -1: no tile (grid padding).
+// tiles (emit_kernel writes a Gaussian's instances to consecutive slots).  So the sixteen tiles of a 4 x 4 block run back to back on
+// ONE XCD: the sector one of them pulls in is in that L2 when the others ask for it.  -1: no tile (grid padding).
 #ifndef GS2M_TS_SUPER_LOG
 #define GS2M_TS_SUPER_LOG 2  // the block of tiles that shares an XCD is 2^LOG x 2^LOG tiles (measured: 1x1 82 us, 2x2 80, 4x4 73, 8x8 72)
 #endif
@@ -308,12 +408,18 @@ __host__ __device__ inline unsigned tile_grid(int tiles_x, int tiles_y) {
 }
 
 // identifyTileRanges (rasterizer_impl.cu:108-129): the tile sort's last pass recorded where the tile's run of instances starts
-// and ends (radix_sort.hip: range_raw); (0, 0) for an untouched tile, as the reference's memset leaves it
-__device__ __forceinline__ uint2 tile_range(const uint32_t* __restrict__ ranges_raw, uint2* __restrict__ ranges, int tile, int lane) {
+// and ends (radix_sort.hip: range_raw = {~first, last + 1}); (0, 0) for an untouched tile, as the reference's memset leaves it
+struct Span {
+    uint32_t start, n;
+};
+__device__ __forceinline__ Span tile_span(const uint32_t* __restrict__ ranges_raw, const int tile) {
     const uint2 raw = reinterpret_cast<const uint2*>(ranges_raw)[tile];
-    const uint2 range = raw.y != 0u ? make_uint2(~raw.x, raw.y) : make_uint2(0u, 0u);
-    if (lane == 0) ranges[tile] = range;
-    return range;
+    return raw.y != 0u ? Span{~raw.x, raw.y - ~raw.x} : Span{0u, 0u};
+}
+// by the first kernel of a frame's tile sort: ranges[tile], and the four empty lists of a tile without instances (no later kernel looks at it)
+__device__ __forceinline__ void write_range(uint2* __restrict__ ranges, uint32_t* __restrict__ qcount, const int tile, const Span sp, const int t) {
+    if (t == 0) ranges[tile] = make_uint2(sp.start, sp.start + sp.n);
+    if (sp.n == 0u && t < 4) qcount[tile * 4 + t] = 0u;
 }
 
 // One wave per tile; spans of up to 512 entries are sorted here (8 elements per lane: 4 KB of LDS and ~45 registers per wave, i.e.
@@ -332,14 +438,13 @@ __global__ void __launch_bounds__(64) tile_sort_wave_kernel(const uint32_t* __re
     const int lane = threadIdx.x;
     const int tile = tile_of_block(blockIdx.x, tiles_x, tiles_y);
     if (tile < 0) return;
-    const uint2 range = tile_range(ranges_raw, ranges, tile, lane);
-    const uint32_t n = range.y - range.x;
-    if (n == 0u) {
-        if (lane < 4) qcount[tile * 4 + lane] = 0u;
-    } else if (n <= wave_max) {
-        sort_tile_wave<8, 3>(tile, range.x, n, slot_sorted, e_rec, wave_rowbase, point_list, qlist, qrow, qcount, s_v, s_r, lane);
+    const Span sp = tile_span(ranges_raw, tile);
+    write_range(ranges, qcount, tile, sp, lane);
+    if (sp.n == 0u) return;
+    if (sp.n <= wave_max) {
+        sort_tile_wave<8, 3>(tile, sp.start, sp.n, slot_sorted, e_rec, wave_rowbase, point_list, qlist, qrow, qcount, s_v, s_r, lane);
     } else if (lane == 0) {  // tells the kernels behind this one that they have work (a plain store of 1: any number of writers)
-        counters[n <= 1024u ? GS2M_CNT_SPAN_MID : GS2M_CNT_SPAN_LONG] = 1u;
+        counters[sp.n <= 1024u ? GS2M_CNT_SPAN_MID : GS2M_CNT_SPAN_LONG] = 1u;
     }
 }
 
@@ -356,10 +461,9 @@ tile_sort_wave16_kernel(const uint32_t* __restrict__ ranges_raw, const uint32_t*
     const int lane = threadIdx.x;
     const int tile = tile_of_block(blockIdx.x, tiles_x, tiles_y);
     if (tile < 0) return;
-    const uint2 raw = reinterpret_cast<const uint2*>(ranges_raw)[tile];
-    const uint32_t start = ~raw.x, n = raw.y != 0u ? raw.y - start : 0u;
-    if (n <= 512u || n > 1024u) return;
-    sort_tile_wave<16, 4>(tile, start, n, slot_sorted, e_rec, wave_rowbase, point_list, qlist, qrow, qcount, s_v, s_r, lane);
+    const Span sp = tile_span(ranges_raw, tile);
+    if (sp.n <= 512u || sp.n > 1024u) return;
+    sort_tile_wave<16, 4>(tile, sp.start, sp.n, slot_sorted, e_rec, wave_rowbase, point_list, qlist, qrow, qcount, s_v, s_r, lane);
 }
 
 // ---- a workgroup per tile, the span still in registers -------------------------------------------------------------------------------
@@ -418,105 +522,19 @@ __device__ __forceinline__ void sort_tile_wg(const int tile, const uint32_t star
 #else
 #define TS_CLK() do {} while (0)
 #endif
+    const WorkgroupScope sc{s_x};
     uint32_t key[E], idx[E], rb[E];
-    // span position p = e * 256 + tid: coalesced slot loads, one 16-byte gather per element, batches of up to 8 elements per lane in flight
-    constexpr int BATCH = E < 8 ? E : 8;
-    static_for<0, E / BATCH>([&](auto bc) {
-        constexpr int e0 = BATCH * decltype(bc)::value;
-        uint32_t slot[BATCH];
-#pragma unroll
-        for (int e = 0; e < BATCH; e++) {
-            const uint32_t p = (uint32_t)((e0 + e) * 256 + tid);
-            slot[e] = p < n ? slot_sorted[start + p] : 0u;
-        }
-        uint4 rc[BATCH];
-#pragma unroll
-        for (int e = 0; e < BATCH; e++) rc[e] = (uint32_t)((e0 + e) * 256 + tid) < n ? e_rec[slot[e]] : make_uint4(0u, 0u, 0xFFFFFFFFu, 0u);
-        static_for<0, BATCH>([&](auto ec) {
-            constexpr int e = decltype(ec)::value;
-            const uint32_t p = (uint32_t)((e0 + e) * 256 + tid);
-            key[e0 + e] = rc[e].z;
-            idx[e0 + e] = p;
-            s_v[skew((int)p)] = rc[e].x;
-            s_r[skew((int)p)] = rc[e].y & ~GS2M_ROWS_BIG;
-            rb[e0 + e] = p < n && (rc[e].y & GS2M_ROWS_BIG) == 0u ? wave_rowbase[(rc[e].x & GS2M_GID_MASK) >> 6] : 0u;  // (a heavy instance's row is absolute)
-        });
-        asm volatile("" ::: "memory");  // the next batch's loads stay behind this batch's staging (registers: one batch in flight)
-    });
+    stage<E, 256>(key, idx, rb, tid, start, n, slot_sorted, e_rec, wave_rowbase, s_v, s_r);
     TS_CLK();  // 0: records staged (loads done)
     network_wg<E, LE>(key, idx, tid, s_x);
     TS_CLK();  // 1: sorted
-#pragma unroll
-    for (int e = 0; e < E; e++) s_r[skew(e * 256 + tid)] += rb[e];  // (this thread parked it: LDS operations of one wave execute in order)
-    // ids and rows of the sorted elements: picked up by span position
-    uint32_t sv[E], sr[E];
-    auto pick_up = [&]() {
-#pragma unroll
-        for (int e = 0; e < E; e++) {
-            const bool real = (uint32_t)(tid * E + e) < n;
-            sv[e] = real ? s_v[skew((int)idx[e])] : 0u;
-            sr[e] = real ? s_r[skew((int)idx[e])] : 0u;
-        }
-    };
-    auto park = [&]() {  // parked again under their sorted position
-#pragma unroll
-        for (int e = 0; e < E; e++) {
-            s_v[skew(tid * E + e)] = sv[e];
-            s_r[skew(tid * E + e)] = sr[e];
-        }
-    };
-    gs2m_sync();  // (the row bases added above)
-    pick_up();
-    // equal depths anywhere in the sorted span (neighbours inside a lane, across lanes, across waves): tie_positions above
-    bool tie = false;
-#pragma unroll
-    for (int e = 0; e + 1 < E; e++) tie |= (uint32_t)(tid * E + e + 1) < n && key[e] == key[e + 1];
-    s_x[tid] = key[0];
-    gs2m_sync();
-    tie |= tid < 255 && (uint32_t)(tid * E + E) < n && key[E - 1] == s_x[tid + 1];
-    if (gs2m_sync_or(tie) != 0) {  // (the barrier also closes the pick-up: the staging arrays are free)
-#pragma unroll
-        for (int e = 0; e < E; e++) {
-            s_v[skew(tid * E + e)] = key[e];
-            s_r[skew(tid * E + e)] = idx[e];
-        }
-        gs2m_sync();
-        uint32_t pos[E];
-        tie_positions<E>(key, idx, pos, tid, n, s_v, s_r);
-        gs2m_sync();  // every look along a run is done: the arrays take the payload
-#pragma unroll
-        for (int e = 0; e < E; e++) {
-            s_v[skew((int)pos[e])] = sv[e];
-            s_r[skew((int)pos[e])] = sr[e];
-        }
-    } else {
-        park();
-    }
+    settle<E>(sc, key, idx, rb, tid, n, s_v, s_r);
     TS_CLK();  // 2: ties settled
-    gs2m_sync();
+    sc.sync();
     TS_CLK();  // 3: payload in sorted order
     for (uint32_t k = (uint32_t)tid; k < n; k += 256) point_list[start + k] = s_v[skew((int)k)];
     // quadrant lists: wave q compacts quadrant q
-    const int q = wave;
-    uint2* out = qlist + (size_t)4 * start + (size_t)q * n;
-    uint32_t* orow = qrow + (size_t)4 * start + (size_t)q * n;
-    uint32_t run = 0;
-    const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-    for (uint32_t base = 0; base < n; base += GS2M_WAVE) {
-        const uint32_t k = base + (uint32_t)lane;
-        uint32_t v = 0, r = 0;
-        if (k < n) { v = s_v[skew((int)k)]; r = s_r[skew((int)k)]; }
-        const uint32_t mask = v >> GS2M_GID_BITS;
-        const bool hit = ((mask >> q) & 1u) != 0u;
-        const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
-        if (hit) {
-            const uint32_t o = run + (uint32_t)__popcll(m & lt);
-            out[o] = make_uint2(v, k);
-            orow[o] = r + (uint32_t)__popc(mask & ((1u << q) - 1u));
-        }
-        run += (uint32_t)__popcll(m);
-    }
-    if (lane == 0) qcount[tile * 4 + q] = run;
+    write_qlist(tile, wave, start, n, lane, [&](uint32_t k) { return make_uint2(s_v[skew((int)k)], s_r[skew((int)k)]); }, qlist, qrow, qcount);
     TS_CLK();  // 4: lists written (stores issued)
 #ifdef GS2M_TS_CLOCK
     if (tid == 0 && clk) { clk[16 * tile + 14] = n; clk[16 * tile + 15] = (uint32_t)(c0 & 0xFFFFFFFFull); }
@@ -529,7 +547,7 @@ __device__ __forceinline__ void sort_tile_wg(const int tile, const uint32_t star
 //   A. every chunk of 4096 entries is gathered and sorted by depth with the register network above (16 per lane), written out as a run;
 //   B. merge level by level (runs of 4096 -> 8192 -> ...): the mirrored compare of a level and its strides of 4096 and more run over
 //      global memory (one step for two runs, three for four, ...), the strides 2048 .. 1 again in registers, a chunk at a time;
-//   C. equal depths: every entry looks along its run for its place (tie_positions' rule).
+//   C. equal depths: every entry looks along its run for its place (tie_position, here over K and I).
 // Exercised by tests/test_tile_sort_gpu.py (spans of up to 20000 entries, with equal depths) and the dense-scene tests.
 constexpr int BIG_CHUNK = 4096;
 __device__ __forceinline__ void sort_tile_big(const int tile, const uint32_t start, const uint32_t n, const uint32_t* __restrict__ slot_sorted,
@@ -559,7 +577,7 @@ __device__ __forceinline__ void sort_tile_big(const int tile, const uint32_t sta
             static_for<0, 8>([&](auto ec) {
                 constexpr int e = decltype(ec)::value;
                 const uint32_t p = base + (uint32_t)((e0 + e) * 256 + tid);
-                key[e0 + e] = p < n ? e_rec[slot[e]].z : 0xFFFFFFFFu;  // (a real key is the bit pattern of a depth > 0.2: never all ones)
+                key[e0 + e] = p < n ? read_record(e_rec[slot[e]]).key : 0xFFFFFFFFu;  // (the key alone: nothing is staged here)
                 idx[e0 + e] = p;
             });
         });
@@ -620,49 +638,19 @@ __device__ __forceinline__ void sort_tile_big(const int tile, const uint32_t sta
     // ---- C: equal depths in span order ----
     uint32_t* const I2 = I + n;
     for (uint32_t p = tid; p < n; p += 256) {
-        const uint32_t Kp = K[p], X = I[p];
-        uint32_t a = p, cnt = 0;
-        for (uint32_t j = p; j > 0u;) {
-            j--;
-            if (K[j] != Kp) break;
-            a = j;
-            cnt += I[j] < X ? 1u : 0u;
-        }
-        for (uint32_t j = p + 1u; j < n; j++) {
-            if (K[j] != Kp) break;
-            cnt += I[j] < X ? 1u : 0u;
-        }
-        I2[a + cnt] = X;
+        const uint32_t X = I[p];
+        I2[tie_position(p, K[p], X, n, [&](uint32_t j) { return K[j]; }, [&](uint32_t j) { return I[j]; })] = X;
     }
     barrier();
     // sorted ids -> point_list (final), absolute rows -> row_tmp
     for (uint32_t p = tid; p < n; p += 256) {
-        const uint4 rc = e_rec[slot_sorted[start + I2[p]]];
-        point_list[start + p] = rc.x;
-        row_tmp[start + p] = (rc.y & GS2M_ROWS_BIG) != 0u ? (rc.y & ~GS2M_ROWS_BIG) : rc.y + wave_rowbase[(rc.x & GS2M_GID_MASK) >> 6];
+        const Record r = read_record(e_rec[slot_sorted[start + I2[p]]]);
+        point_list[start + p] = r.v;
+        row_tmp[start + p] = r.absolute ? r.row : r.row + wave_rowbase[r.wave];
     }
     barrier();
     // quadrant lists: wave q compacts quadrant q (the scratch in the list region is dead behind the barrier above)
-    const int q = wave;
-    uint2* out = qlist + (size_t)4 * start + (size_t)q * n;
-    uint32_t* orow = qrow + (size_t)4 * start + (size_t)q * n;
-    uint32_t run = 0;
-    const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-    for (uint32_t base = 0; base < n; base += GS2M_WAVE) {
-        const uint32_t k = base + (uint32_t)lane;
-        uint32_t v = 0, r = 0;
-        if (k < n) { v = point_list[start + k]; r = row_tmp[start + k]; }
-        const uint32_t mask = v >> GS2M_GID_BITS;
-        const bool hit = ((mask >> q) & 1u) != 0u;
-        const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
-        if (hit) {
-            const uint32_t o = run + (uint32_t)__popcll(m & lt);
-            out[o] = make_uint2(v, k);
-            orow[o] = r + (uint32_t)__popc(mask & ((1u << q) - 1u));
-        }
-        run += (uint32_t)__popcll(m);
-    }
-    if (lane == 0) qcount[tile * 4 + q] = run;
+    write_qlist(tile, wave, start, n, lane, [&](uint32_t k) { return make_uint2(point_list[start + k], row_tmp[start + k]); }, qlist, qrow, qcount);
 }
 
 // A workgroup per tile, in two launches: spans of up to 1024 entries (MAXE = 4: 13 KB of LDS and 80 registers, six workgroups per CU;
@@ -695,13 +683,10 @@ tile_sort_wg_kernel(const uint32_t* __restrict__ ranges_raw, uint2* __restrict__
     for (uint32_t blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {  // (gridDim.x is a multiple of 8: a workgroup stays on its XCD's tiles)
         const int tile = tile_of_block((int)blk, tiles_x, tiles_y);
         if (tile < 0) continue;
-        const uint2 raw = reinterpret_cast<const uint2*>(ranges_raw)[tile];
-        const uint32_t start = raw.y != 0u ? ~raw.x : 0u, n = raw.y != 0u ? raw.y - start : 0u;
+        const Span sp = tile_span(ranges_raw, tile);
+        const uint32_t start = sp.start, n = sp.n;
         if constexpr (MAXE < 8) {
-            if (ranges != nullptr) {
-                if (tid == 0) ranges[tile] = raw.y != 0u ? make_uint2(start, raw.y) : make_uint2(0u, 0u);
-                if (n == 0u && tid < 4) qcount[tile * 4 + tid] = 0u;
-            }
+            if (ranges != nullptr) write_range(ranges, qcount, tile, sp, tid);
             if (n > 1024u && tid == 0) counters[GS2M_CNT_SPAN_LONG] = 1u;
             if (n == 0u || n > 1024u) continue;
             if (n <= 256u) sort_tile_wg<1, 0>(tile, start, n, slot_sorted, e_rec, wave_rowbase, point_list, qlist, qrow, qcount, s_v, s_r, s_x, tid, row_tmp);
@@ -734,7 +719,8 @@ void gs2m_launch_tile_sort(size_t tiles, int tiles_x, int tiles_y, size_t R /* i
     // 900 entries the workgroup kernels lose, 315 against 173 us: 1536 tiles resident instead of 4096).  policy: 0 = by tile count,
     // 1 = workgroups, 2 = waves, 3 = waves with the spans of 513 .. 1024 entries left to the workgroup kernel behind (what 0 and 2 do
     // by themselves in a frame whose AVERAGE span is short: see below).
-    static const int env_policy = getenv("GS2M_TS_POLICY") ? atoi(getenv("GS2M_TS_POLICY")) : 0;  // (experiments)
+    static const char* const env = getenv("GS2M_TS_POLICY");  // (experiments)
+    static const int env_policy = env ? atoi(env) : 0;
     const int set_policy = g_ts_policy.load(std::memory_order_relaxed), policy = set_policy != 0 ? set_policy : env_policy;
     const bool waves = policy == 2 || policy == 3 || (policy == 0 && tiles >= 2560);
     // Spans of 513 .. 1024 entries under the wave policy: a kernel of their own, one wave per tile with 16 elements per lane -- launched

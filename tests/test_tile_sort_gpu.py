@@ -11,6 +11,8 @@ import torch
 pytestmark = pytest.mark.gpu
 
 ROWS_BIG = np.uint32(0x80000000)   # common.h: GS2M_ROWS_BIG
+GUARD_WORDS, GUARD = 64, 0x5A5A5A5A   # behind every output array: words no kernel may touch
+UNWRITTEN = np.uint32(0xFFFFFFFF)     # what ranges and qcount hold before the call: no range and no count of a test has this value
 
 
 @pytest.fixture(params=[0, 1, 2, 3], ids=["auto", "workgroups", "waves", "waves-mid-by-workgroup"], autouse=True)
@@ -60,8 +62,13 @@ def _run(lengths, max_tile, seed, tie_levels):
     dev = "cuda"
     T = lambda a: torch.from_numpy(np.ascontiguousarray(a).astype(np.uint32).view(np.int32).reshape(-1).copy()).to(dev)
     t_raw, t_slot, t_erec, t_wrb = T(raw), T(slot), T(e_rec), T(wave_rowbase)
-    Z = lambda k, fill=0: torch.full((k,), fill, dtype=torch.int32, device=dev)
-    o_rg, o_pl, o_tmp, o_ql, o_qr, o_qc = Z(2 * tiles, -1), Z(nn), Z(nn), Z(8 * nn), Z(4 * nn), Z(4 * tiles, -1)
+    def Z(k, fill=0, guard=True):
+        # k words + the guard words: what a writer with a wrong base or stride puts behind its tile's region is overwritten by the
+        # next tile -- except behind the last one
+        t = torch.full((k + (GUARD_WORDS if guard else 0),), fill, dtype=torch.int32, device=dev)
+        t[k:] = GUARD
+        return t
+    o_rg, o_pl, o_tmp, o_ql, o_qr, o_qc = Z(2 * tiles, -1, guard=False), Z(nn), Z(nn), Z(8 * nn), Z(4 * nn), Z(4 * tiles, -1)
     L = gs2m_native.lib()
     rc = L.gs2m_debug_tile_sort(tiles, t_raw.data_ptr(), o_rg.data_ptr(), t_slot.data_ptr(), t_erec.data_ptr(), t_wrb.data_ptr(),
                                 o_pl.data_ptr(), o_tmp.data_ptr(), o_ql.data_ptr(), o_qr.data_ptr(), o_qc.data_ptr(),
@@ -69,7 +76,11 @@ def _run(lengths, max_tile, seed, tie_levels):
     gs2m_native.check(rc, "gs2m_debug_tile_sort")
     torch.cuda.synchronize()
     U = lambda t: t.cpu().numpy().view(np.uint32)
-    rg, pl, ql, qr, qc = U(o_rg).reshape(tiles, 2), U(o_pl), U(o_ql).reshape(-1, 2), U(o_qr), U(o_qc).reshape(tiles, 4)
+    for name, t, k in (("point_list", o_pl, nn), ("row_tmp", o_tmp, nn), ("qlist", o_ql, 8 * nn), ("qrow", o_qr, 4 * nn), ("qcount", o_qc, 4 * tiles)):
+        assert t.numel() == k + GUARD_WORDS and np.all(U(t)[k:] == GUARD), f"{name}: written behind its end"
+    rg, pl, ql, qr, qc = U(o_rg).reshape(tiles, 2), U(o_pl)[:nn], U(o_ql)[:8 * nn].reshape(-1, 2), U(o_qr)[:4 * nn], U(o_qc)[:4 * tiles].reshape(tiles, 4)
+    assert not np.any(rg == UNWRITTEN), f"ranges: words of tiles {np.nonzero((rg == UNWRITTEN).any(axis=1))[0][:8]} not written"
+    assert not np.any(qc == UNWRITTEN), f"qcount: words of tiles {np.nonzero((qc == UNWRITTEN).any(axis=1))[0][:8]} not written"
     for t, Ln in enumerate(lengths):
         lo = int(starts[t])
         if Ln == 0:
@@ -105,6 +116,13 @@ def test_one_wave_per_tile_up_to_1024(tie_levels):
 @pytest.mark.parametrize("tie_levels", [0, 5, 2000])
 def test_workgroup_per_tile_lds_and_global(tie_levels):
     _run([1025, 10, 2047, 2048, 2049, 4095, 4096, 4097, 0, 9000, 513, 1024, 300, 20000], 20000, 21 + tie_levels, tie_levels)
+
+
+@pytest.mark.parametrize("tie_levels", [1])
+def test_one_depth_for_the_whole_span(tie_levels):
+    """every instance of every span at the same depth: the output is pure Gaussian-id order, and a run of equal depths crosses every
+    lane, wave and 4096-chunk boundary at once; lengths on both sides of every class boundary"""
+    _run([1, 2, 63, 64, 65, 256, 257, 512, 513, 1024, 1025, 2048, 2049, 4096, 4097, 0], 4097, 41, tie_levels)
 
 
 def test_many_tiles_like_a_frame():

@@ -5,33 +5,22 @@
 // boundary as the reference's extension (fused_ssim/__init__.py:8-41): forward returns the map plus the three
 // partial derivatives the backward needs, backward turns dL/dmap into dL/dimg1.
 //
-// Layout for wave64: ONE WAVE walks down a 64-column strip.  Per image row it stages the 74 halo columns of both
-// images in LDS, every lane forms the five horizontal sums (a, a^2, b, b^2, ab) for its column, and feeds them into
-// a ring of 11 vertical accumulators per quantity that lives in registers (scatter form: row t adds w[k]*h into the
-// output that started k rows ago) -- so the vertical pass costs no LDS traffic at all and each input row is read
-// from HBM once per strip (+10 halo rows per SSIM_ROWS).  The epilogue (SSIM value and derivatives) runs on the
+// Layout for wave64: ONE WAVE walks down a 64-column strip with the shared walk of window11.h.  Per image row it stages
+// the 74 halo columns in LDS (both images forward, the three products dL dm/d. backward) and every lane forms the
+// horizontal sums for its column; the walk's register ring does the vertical pass, so each input row is read from HBM
+// once per strip (+10 halo rows per SSIM_ROWS).  The epilogue (SSIM value and derivatives, or dL/dimg1) runs on the
 // row that completes.  HBM: 8 B read + 16 B written per element forward, 24 + 4 B backward; the kernels are VALU
 // bound (~200 lane-ops per element), not HBM bound.
 #include "common.h"
+#include "window11.h"
 #include "../../include/gs2m_ssim.h"
 
 namespace {
-
-// torch.Tensor([exp(-(x - 5)^2 / (2 * 1.5^2)) for x in range(11)]) / sum, in fp32 (utils/loss_utils.py:41-43)
-__device__ __constant__ const float SSIM_W[11] = {0.001028380123898387f, 0.0075987582094967365f, 0.036000773310661316f,
-                                                  0.10936068743467331f,  0.21300552785396576f,   0.26601171493530273f,
-                                                  0.21300552785396576f,  0.10936068743467331f,   0.036000773310661316f,
-                                                  0.0075987582094967365f, 0.001028380123898387f};
 
 constexpr int SSIM_ROWS = 45;   // output rows per strip at most (1080 = 24 * 45); +10 halo rows of input.  ssim_rows() below picks fewer on small frames
 constexpr int SSIM_LDSW = 80;   // 64 + 10 halo columns, padded
 constexpr int SSIM_PF_FWD = 3;  // input rows in flight ahead of the row being consumed: the strip walk is a chain of
 constexpr int SSIM_PF_BWD = 5;  // dependent HBM round trips (~1 us each) with only ~2 waves per SIMD to hide them
-
-template <int NQ>
-struct Ring {  // NQ quantities x 11 vertical accumulators
-    float a[NQ][11];
-};
 
 // ---------------------------------------------------------------- forward
 __global__ void __launch_bounds__(64) ssim_fwd_kernel(int H, int W, int rows, float C1, float C2, const float* __restrict__ img1,
@@ -44,94 +33,40 @@ __global__ void __launch_bounds__(64) ssim_fwd_kernel(int H, int W, int rows, fl
     const size_t plane = (size_t)blockIdx.z * H * W;
     const float* __restrict__ A = img1 + plane;
     const float* __restrict__ Bm = img2 + plane;
-    float w[11];
-#pragma unroll
-    for (int k = 0; k < 11; k++) w[k] = SSIM_W[k];
-
     const int xa = x0 - 5 + lane, xb = x0 + 59 + lane;  // main column and (lanes 0..9) the right halo column
     const bool ina = xa >= 0 && xa < W, inb = lane < 10 && xb < W;
-    auto fetch = [&](int y, float& a0, float& b0, float& a1, float& b1) {
-        const bool row = y >= 0 && y < H;
-        const size_t o = (size_t)(row ? y : 0) * W;
-        a0 = (row && ina) ? A[o + xa] : 0.f;
-        b0 = (row && ina) ? Bm[o + xa] : 0.f;
-        a1 = (row && inb) ? A[o + xb] : 0.f;
-        b1 = (row && inb) ? Bm[o + xb] : 0.f;
-    };
-
-    Ring<5> R;
-#pragma unroll
-    for (int q = 0; q < 5; q++)
-#pragma unroll
-        for (int j = 0; j < 11; j++) R.a[q][j] = 0.f;
-
-    const int nrows = min(rows, H - y0) + 10;  // input rows y0-5 .. y0+rows+4
-    float pf[SSIM_PF_FWD][4];  // queue of fetched rows: pf[0] is the next one to consume
-#pragma unroll
-    for (int d = 0; d < SSIM_PF_FWD; d++) fetch(d < nrows ? y0 - 5 + d : -1, pf[d][0], pf[d][1], pf[d][2], pf[d][3]);
     const int x = x0 + lane;
-    for (int t0 = 0; t0 < nrows; t0 += 11) {
-#pragma unroll
-        for (int u = 0; u < 11; u++) {
-            const int t = t0 + u;
-            if (t < nrows) {  // wave-uniform
-                const int buf = u & 1;
-                s_a[buf][lane] = pf[0][0]; s_b[buf][lane] = pf[0][1];
-                if (lane < 10) { s_a[buf][64 + lane] = pf[0][2]; s_b[buf][64 + lane] = pf[0][3]; }
-#pragma unroll
-                for (int d = 0; d + 1 < SSIM_PF_FWD; d++)
-#pragma unroll
-                    for (int c = 0; c < 4; c++) pf[d][c] = pf[d + 1][c];
-                {
-                    constexpr int D = SSIM_PF_FWD - 1;
-                    fetch(t + SSIM_PF_FWD < nrows ? y0 - 5 + t + SSIM_PF_FWD : -1, pf[D][0], pf[D][1], pf[D][2], pf[D][3]);
+    window11_walk<float, float, 5, 4, SSIM_PF_FWD, 64>(
+        y0, min(rows, H - y0),
+        [&](int y, float (&v)[4]) {
+            const bool row = y >= 0 && y < H;
+            const size_t o = (size_t)(row ? y : 0) * W;
+            v[0] = (row && ina) ? A[o + xa] : 0.f;
+            v[1] = (row && ina) ? Bm[o + xa] : 0.f;
+            v[2] = (row && inb) ? A[o + xb] : 0.f;
+            v[3] = (row && inb) ? Bm[o + xb] : 0.f;
+        },
+        [&](int buf, int, const float (&v)[4]) {
+            s_a[buf][lane] = v[0]; s_b[buf][lane] = v[1];
+            if (lane < 10) { s_a[buf][64 + lane] = v[2]; s_b[buf][64 + lane] = v[3]; }
+        },
+        [&](int buf, const float (&w)[11], float (&h)[5]) { window11_moments<1>(s_a[buf], s_b[buf], lane, w, h); },
+        [&](int yo, const float (&m)[5]) {
+            const float mu1 = m[0], mu2 = m[2];
+            const auto [Cc, Dd, Aa, Bb] = window11_ssim(mu1, m[1], mu2, m[3], m[4], C1, C2);
+            const float rAB = 1.f / (Aa * Bb);
+            if (x < W) {
+                const size_t o = plane + (size_t)yo * W + x;
+                ssim_map[o] = (Cc * Dd) * rAB;
+                if (dm_dmu1 != nullptr) {
+                    // d/dmu1 of (C D)/(A B) with sigma1_sq, sigma12 depending on mu1 through -mu1^2, -mu1 mu2
+                    dm_dmu1[o] = (mu2 * 2.f * Dd) * rAB - (mu2 * 2.f * Cc) * rAB - (mu1 * 2.f * Cc * Dd) * rAB / Aa +
+                                 (mu1 * 2.f * Cc * Dd) * rAB / Bb;
+                    dm_dsigma1_sq[o] = (-Cc * Dd) * rAB / Bb;
+                    dm_dsigma12[o] = (2.f * Cc) * rAB;
                 }
-                __syncthreads();
-                float h[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int k = 0; k < 11; k++) {
-                    const float a = s_a[buf][lane + k], b = s_b[buf][lane + k];
-                    const float wa = w[k] * a, wb = w[k] * b;
-                    h[0] += wa; h[1] = __builtin_fmaf(wa, a, h[1]);
-                    h[2] += wb; h[3] = __builtin_fmaf(wb, b, h[3]);
-                    h[4] = __builtin_fmaf(wa, b, h[4]);
-                }
-                // input row t is tap k of the output row t - k: ring slot (u - k) mod 11
-#pragma unroll
-                for (int k = 0; k < 11; k++) {
-                    const int j = (u - k + 11) % 11;
-#pragma unroll
-                    for (int q = 0; q < 5; q++) R.a[q][j] = __builtin_fmaf(w[k], h[q], R.a[q][j]);
-                }
-                const int jo = (u + 1) % 11;  // output row t - 10 is complete
-                const int yo = y0 + t - 10;
-                if (t >= 10) {
-                    const float mu1 = R.a[0][jo], mu2 = R.a[2][jo];
-                    const float sigma1_sq = R.a[1][jo] - mu1 * mu1;
-                    const float sigma2_sq = R.a[3][jo] - mu2 * mu2;
-                    const float sigma12 = R.a[4][jo] - mu1 * mu2;
-                    const float Cc = 2.f * (mu1 * mu2) + C1;
-                    const float Dd = 2.f * sigma12 + C2;
-                    const float Aa = mu1 * mu1 + mu2 * mu2 + C1;
-                    const float Bb = sigma1_sq + sigma2_sq + C2;
-                    const float rAB = 1.f / (Aa * Bb);
-                    if (x < W) {
-                        const size_t o = plane + (size_t)yo * W + x;
-                        ssim_map[o] = (Cc * Dd) * rAB;
-                        if (dm_dmu1 != nullptr) {
-                            // d/dmu1 of (C D)/(A B) with sigma1_sq, sigma12 depending on mu1 through -mu1^2, -mu1 mu2
-                            dm_dmu1[o] = (mu2 * 2.f * Dd) * rAB - (mu2 * 2.f * Cc) * rAB - (mu1 * 2.f * Cc * Dd) * rAB / Aa +
-                                         (mu1 * 2.f * Cc * Dd) * rAB / Bb;
-                            dm_dsigma1_sq[o] = (-Cc * Dd) * rAB / Bb;
-                            dm_dsigma12[o] = (2.f * Cc) * rAB;
-                        }
-                    }
-                }
-#pragma unroll
-                for (int q = 0; q < 5; q++) R.a[q][jo] = 0.f;
             }
-        }
-    }
+        });
 }
 
 // ---------------------------------------------------------------- backward
@@ -147,74 +82,46 @@ __global__ void __launch_bounds__(64) ssim_bwd_kernel(int H, int W, int rows, co
     const int lane = threadIdx.x;
     const int x0 = blockIdx.x * 64, y0 = blockIdx.y * rows;
     const size_t plane = (size_t)blockIdx.z * H * W;
-    float w[11];
-#pragma unroll
-    for (int k = 0; k < 11; k++) w[k] = SSIM_W[k];
     const int xa = x0 - 5 + lane, xb = x0 + 59 + lane;
     const bool ina = xa >= 0 && xa < W, inb = lane < 10 && xb < W;
-    auto fetch = [&](int y, float (&v)[8]) {  // dL and the three derivative maps, main and halo column
-        const bool row = y >= 0 && y < H;
-        const size_t o = plane + (size_t)(row ? y : 0) * W;
-        const bool m0 = row && ina, m1 = row && inb;
-        v[0] = m0 ? (dL_dmap ? dL_dmap[o + xa] : gu) : 0.f;
-        v[1] = m0 ? dm_dmu1[o + xa] : 0.f;
-        v[2] = m0 ? dm_dsigma1_sq[o + xa] : 0.f;
-        v[3] = m0 ? dm_dsigma12[o + xa] : 0.f;
-        v[4] = m1 ? (dL_dmap ? dL_dmap[o + xb] : gu) : 0.f;
-        v[5] = m1 ? dm_dmu1[o + xb] : 0.f;
-        v[6] = m1 ? dm_dsigma1_sq[o + xb] : 0.f;
-        v[7] = m1 ? dm_dsigma12[o + xb] : 0.f;
-    };
-    Ring<3> R;
-#pragma unroll
-    for (int q = 0; q < 3; q++)
-#pragma unroll
-        for (int j = 0; j < 11; j++) R.a[q][j] = 0.f;
-    const int nrows = min(rows, H - y0) + 10;
-    float pf[SSIM_PF_BWD][8];
-#pragma unroll
-    for (int d = 0; d < SSIM_PF_BWD; d++) fetch(d < nrows ? y0 - 5 + d : -1, pf[d]);
     const int x = x0 + lane;
-    for (int t0 = 0; t0 < nrows; t0 += 11) {
+    window11_walk<float, float, 3, 8, SSIM_PF_BWD, 64>(
+        y0, min(rows, H - y0),
+        [&](int y, float (&v)[8]) {  // dL and the three derivative maps, main and halo column
+            const bool row = y >= 0 && y < H;
+            const size_t o = plane + (size_t)(row ? y : 0) * W;
+            const bool m0 = row && ina, m1 = row && inb;
+            v[0] = m0 ? (dL_dmap ? dL_dmap[o + xa] : gu) : 0.f;
+            v[1] = m0 ? dm_dmu1[o + xa] : 0.f;
+            v[2] = m0 ? dm_dsigma1_sq[o + xa] : 0.f;
+            v[3] = m0 ? dm_dsigma12[o + xa] : 0.f;
+            v[4] = m1 ? (dL_dmap ? dL_dmap[o + xb] : gu) : 0.f;
+            v[5] = m1 ? dm_dmu1[o + xb] : 0.f;
+            v[6] = m1 ? dm_dsigma1_sq[o + xb] : 0.f;
+            v[7] = m1 ? dm_dsigma12[o + xb] : 0.f;
+        },
+        [&](int buf, int, const float (&v)[8]) {
 #pragma unroll
-        for (int u = 0; u < 11; u++) {
-            const int t = t0 + u;
-            if (t < nrows) {
-                const int buf = u & 1;
-#pragma unroll
-                for (int q = 0; q < 3; q++) {
-                    s_x[buf][q][lane] = pf[0][0] * pf[0][1 + q];
-                    if (lane < 10) s_x[buf][q][64 + lane] = pf[0][4] * pf[0][5 + q];
-                }
-#pragma unroll
-                for (int d = 0; d + 1 < SSIM_PF_BWD; d++)
-#pragma unroll
-                    for (int c = 0; c < 8; c++) pf[d][c] = pf[d + 1][c];
-                fetch(t + SSIM_PF_BWD < nrows ? y0 - 5 + t + SSIM_PF_BWD : -1, pf[SSIM_PF_BWD - 1]);
-                __syncthreads();
-                float h[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-                for (int k = 0; k < 11; k++)
-#pragma unroll
-                    for (int q = 0; q < 3; q++) h[q] = __builtin_fmaf(w[k], s_x[buf][q][lane + k], h[q]);
-#pragma unroll
-                for (int k = 0; k < 11; k++) {
-                    const int j = (u - k + 11) % 11;
-#pragma unroll
-                    for (int q = 0; q < 3; q++) R.a[q][j] = __builtin_fmaf(w[k], h[q], R.a[q][j]);
-                }
-                const int jo = (u + 1) % 11;
-                const int yo = y0 + t - 10;
-                if (t >= 10 && x < W) {
-                    const size_t o = plane + (size_t)yo * W + x;
-                    const float a = img1[o], b = img2[o];
-                    dL_dimg1[o] = R.a[0][jo] + 2.f * a * R.a[1][jo] + b * R.a[2][jo];
-                }
-#pragma unroll
-                for (int q = 0; q < 3; q++) R.a[q][jo] = 0.f;
+            for (int q = 0; q < 3; q++) {
+                s_x[buf][q][lane] = v[0] * v[1 + q];
+                if (lane < 10) s_x[buf][q][64 + lane] = v[4] * v[5 + q];
             }
-        }
-    }
+        },
+        [&](int buf, const float (&w)[11], float (&h)[3]) {
+#pragma unroll
+            for (int q = 0; q < 3; q++) h[q] = 0.f;
+#pragma unroll
+            for (int k = 0; k < 11; k++)
+#pragma unroll
+                for (int q = 0; q < 3; q++) h[q] = __builtin_fmaf(w[k], s_x[buf][q][lane + k], h[q]);
+        },
+        [&](int yo, const float (&m)[3]) {
+            if (x < W) {
+                const size_t o = plane + (size_t)yo * W + x;
+                const float a = img1[o], b = img2[o];
+                dL_dimg1[o] = m[0] + 2.f * a * m[1] + b * m[2];
+            }
+        });
 }
 
 // Rows per strip: a strip is ONE wave walking its rows as a chain of dependent memory round trips, so a frame has to be cut into
@@ -229,6 +136,28 @@ inline bool ssim_dims_ok(int B, int CH, int H, int W) {
     return B > 0 && CH > 0 && H > 0 && W > 0 && (long long)B * CH <= 65535 && (H + 11) / 12 <= 65535;
 }
 
+// What the three entry points share.  `ptrs_ok`: the caller's own pointer validation, which counts on a frame that is not empty
+// only; launch(grid, rows) starts the kernel.
+template <class Launch>
+int ssim_run(int B, int CH, int H, int W, bool ptrs_ok, Launch launch) {
+    if (B == 0 || CH == 0 || H == 0 || W == 0) return GS2M_OK;
+    if (B < 0 || CH < 0 || H < 0 || W < 0 || !ptrs_ok) return GS2M_ERR_INVALID_ARG;
+    if (!ssim_dims_ok(B, CH, H, W)) return GS2M_ERR_UNSUPPORTED;
+    const int rows = ssim_rows(B, CH, H, W);
+    launch(dim3((W + 63) / 64, (H + rows - 1) / rows, B * CH), rows);
+    return hipGetLastError() == hipSuccess ? GS2M_OK : GS2M_ERR_HIP;
+}
+
+// the two backward entry points: dL_dmap, or nullptr and the uniform gradient dL_dvalue[0] * mul / div
+int ssim_backward(int B, int CH, int H, int W, bool ptrs_ok, const float* img1, const float* img2, const float* dL_dmap,
+                  const float* dm_dmu1, const float* dm_dsigma1_sq, const float* dm_dsigma12, float* dL_dimg1,
+                  const float* dL_dvalue, float mul, float div, void* stream) {
+    return ssim_run(B, CH, H, W, ptrs_ok, [&](dim3 grid, int rows) {
+        ssim_bwd_kernel<<<grid, 64, 0, (hipStream_t)stream>>>(H, W, rows, img1, img2, dL_dmap, dm_dmu1, dm_dsigma1_sq, dm_dsigma12,
+                                                             dL_dimg1, dL_dvalue, mul, div);
+    });
+}
+
 }  // namespace
 
 extern "C" int gs2m_ssim_strip_rows(int B, int CH, int H, int W) {
@@ -239,42 +168,24 @@ extern "C" int gs2m_ssim_strip_rows(int B, int CH, int H, int W) {
 
 extern "C" int gs2m_ssim_forward(int B, int CH, int H, int W, float C1, float C2, const float* img1, const float* img2,
                                  float* ssim_map, float* dm_dmu1, float* dm_dsigma1_sq, float* dm_dsigma12, void* stream) {
-    if (B == 0 || CH == 0 || H == 0 || W == 0) return GS2M_OK;
-    if (B < 0 || CH < 0 || H < 0 || W < 0 || !img1 || !img2 || !ssim_map) return GS2M_ERR_INVALID_ARG;
-    const bool train = dm_dmu1 || dm_dsigma1_sq || dm_dsigma12;
-    if (train && !(dm_dmu1 && dm_dsigma1_sq && dm_dsigma12)) return GS2M_ERR_INVALID_ARG;
-    if (!ssim_dims_ok(B, CH, H, W)) return GS2M_ERR_UNSUPPORTED;
-    const int rows = ssim_rows(B, CH, H, W);
-    dim3 grid((W + 63) / 64, (H + rows - 1) / rows, B * CH);
-    ssim_fwd_kernel<<<grid, 64, 0, (hipStream_t)stream>>>(H, W, rows, C1, C2, img1, img2, ssim_map, dm_dmu1, dm_dsigma1_sq,
-                                                         dm_dsigma12);
-    return hipGetLastError() == hipSuccess ? GS2M_OK : GS2M_ERR_HIP;
+    const bool train = dm_dmu1 || dm_dsigma1_sq || dm_dsigma12;  // all three maps or none
+    const bool ok = img1 && img2 && ssim_map && (!train || (dm_dmu1 && dm_dsigma1_sq && dm_dsigma12));
+    return ssim_run(B, CH, H, W, ok, [&](dim3 grid, int rows) {
+        ssim_fwd_kernel<<<grid, 64, 0, (hipStream_t)stream>>>(H, W, rows, C1, C2, img1, img2, ssim_map, dm_dmu1, dm_dsigma1_sq,
+                                                             dm_dsigma12);
+    });
 }
 
 extern "C" int gs2m_ssim_backward(int B, int CH, int H, int W, const float* img1, const float* img2, const float* dL_dmap,
                                   const float* dm_dmu1, const float* dm_dsigma1_sq, const float* dm_dsigma12,
                                   float* dL_dimg1, void* stream) {
-    if (B == 0 || CH == 0 || H == 0 || W == 0) return GS2M_OK;
-    if (B < 0 || CH < 0 || H < 0 || W < 0 || !img1 || !img2 || !dL_dmap || !dm_dmu1 || !dm_dsigma1_sq || !dm_dsigma12 || !dL_dimg1)
-        return GS2M_ERR_INVALID_ARG;
-    if (!ssim_dims_ok(B, CH, H, W)) return GS2M_ERR_UNSUPPORTED;
-    const int rows = ssim_rows(B, CH, H, W);
-    dim3 grid((W + 63) / 64, (H + rows - 1) / rows, B * CH);
-    ssim_bwd_kernel<<<grid, 64, 0, (hipStream_t)stream>>>(H, W, rows, img1, img2, dL_dmap, dm_dmu1, dm_dsigma1_sq, dm_dsigma12,
-                                                         dL_dimg1, nullptr, 0.f, 1.f);
-    return hipGetLastError() == hipSuccess ? GS2M_OK : GS2M_ERR_HIP;
+    const bool ok = img1 && img2 && dL_dmap && dm_dmu1 && dm_dsigma1_sq && dm_dsigma12 && dL_dimg1;
+    return ssim_backward(B, CH, H, W, ok, img1, img2, dL_dmap, dm_dmu1, dm_dsigma1_sq, dm_dsigma12, dL_dimg1, nullptr, 0.f, 1.f, stream);
 }
 
 extern "C" int gs2m_ssim_backward_uniform(int B, int CH, int H, int W, const float* img1, const float* img2, const float* dL_dvalue,
                                           float mul, float div, const float* dm_dmu1, const float* dm_dsigma1_sq,
                                           const float* dm_dsigma12, float* dL_dimg1, void* stream) {
-    if (B == 0 || CH == 0 || H == 0 || W == 0) return GS2M_OK;
-    if (B < 0 || CH < 0 || H < 0 || W < 0 || !img1 || !img2 || !dL_dvalue || !dm_dmu1 || !dm_dsigma1_sq || !dm_dsigma12 || !dL_dimg1 || div == 0.f)
-        return GS2M_ERR_INVALID_ARG;
-    if (!ssim_dims_ok(B, CH, H, W)) return GS2M_ERR_UNSUPPORTED;
-    const int rows = ssim_rows(B, CH, H, W);
-    dim3 grid((W + 63) / 64, (H + rows - 1) / rows, B * CH);
-    ssim_bwd_kernel<<<grid, 64, 0, (hipStream_t)stream>>>(H, W, rows, img1, img2, nullptr, dm_dmu1, dm_dsigma1_sq, dm_dsigma12,
-                                                         dL_dimg1, dL_dvalue, mul, div);
-    return hipGetLastError() == hipSuccess ? GS2M_OK : GS2M_ERR_HIP;
+    const bool ok = img1 && img2 && dL_dvalue && dm_dmu1 && dm_dsigma1_sq && dm_dsigma12 && dL_dimg1 && div != 0.f;
+    return ssim_backward(B, CH, H, W, ok, img1, img2, nullptr, dm_dmu1, dm_dsigma1_sq, dm_dsigma12, dL_dimg1, dL_dvalue, mul, div, stream);
 }

@@ -50,15 +50,18 @@ def test_squared_error_hand_computed():
 
 
 def test_window_is_the_kernels():
-    """the eleven weights csrc/image_metrics.hip and csrc/ssim.hip carry are the restatement's (torch's fp32 arithmetic)"""
+    """the eleven weights csrc/image_metrics.hip and csrc/ssim.hip take from csrc/window11.h, and nowhere else, are the
+    restatement's (torch's fp32 arithmetic)"""
     from math import exp
     g = torch.Tensor([exp(-(x - 5) ** 2 / float(2 * 1.5 ** 2)) for x in range(11)])
     assert np.array_equal((g / g.sum()).numpy(), MR.window_1d())
+    csrc = os.path.join(ROOT, "gs-2m_amd", "csrc")
     for f in ("image_metrics.hip", "ssim.hip"):
-        src = open(os.path.join(ROOT, "gs-2m_amd", "csrc", f)).read()
-        body = re.search(r"_W\[11\] = \{([^}]*)\}", src).group(1)
-        w = np.array([np.float32(t.strip().rstrip("f")) for t in body.split(",")], dtype=np.float32)
-        assert np.array_equal(w, MR.window_1d()), f
+        src = open(os.path.join(csrc, f)).read()
+        assert '#include "window11.h"' in src and "WINDOW11_W" not in src and "_W[11]" not in src, f
+    body = re.search(r"_W\[11\] = \{([^}]*)\}", open(os.path.join(csrc, "window11.h")).read()).group(1)
+    w = np.array([np.float32(t.strip().rstrip("f")) for t in body.split(",")], dtype=np.float32)
+    assert np.array_equal(w, MR.window_1d())
 
 
 def test_tile_constants_are_the_headers():

@@ -44,9 +44,11 @@ IDS = [f[0] for f in FAMILIES]
 
 
 def test_window_is_the_kernels_window():
-    """the 11 constants of csrc/ssim.hip are these float32 weights, bit for bit; they sum to 1 within float32"""
-    src = open(os.path.join(ROOT, "gs-2m_amd", "csrc", "ssim.hip")).read()
-    body = re.search(r"SSIM_W\[11\]\s*=\s*\{(.*?)\}", src, flags=re.S).group(1)
+    """the 11 constants of csrc/window11.h, the one window csrc/ssim.hip walks, are these float32 weights, bit for bit; they
+    sum to 1 within float32"""
+    src = open(os.path.join(ROOT, "gs-2m_amd", "csrc", "window11.h")).read()
+    assert '#include "window11.h"' in open(os.path.join(ROOT, "gs-2m_amd", "csrc", "ssim.hip")).read()
+    body = re.search(r"WINDOW11_W\[11\]\s*=\s*\{(.*?)\}", src, flags=re.S).group(1)
     consts = np.array([np.float32(x.strip().rstrip("f")) for x in body.split(",")], dtype=np.float32)
     assert np.array_equal(consts, R.window32().numpy())
     assert abs(float(R.window().sum()) - 1.0) < 4 * R.U

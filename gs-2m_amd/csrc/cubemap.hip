@@ -434,26 +434,46 @@ __global__ void __launch_bounds__(256) specular_prescale_kernel(int n, const flo
     g4[i] = make_float4(g3[3 * (size_t)i] / w, g3[3 * (size_t)i + 1] / w, g3[3 * (size_t)i + 2] / w, 0.f);
 }
 
-template <bool BWD>
-int launch_specular(int res, float roughness, float cos_cut, const float* tab, const float* in, float* out, hipStream_t s) {
+// The kernel a specular level runs, forward and backward alike (gs2m_specular_cubemap_route returns this number).
+enum { ROUTE_TPO1 = 0, ROUTE_TPO16 = 1, ROUTE_TPO64 = 2, ROUTE_TILE8 = 3, ROUTE_TILE4 = 4 };
+
+int specular_route(int res, float cos_cut, bool out_aligned16) {
     const long long total = 6LL * res * res;
     // expected texel pairs per output: the cone's share of the sphere
     const double pairs = 0.5 * (1.0 - (double)cos_cut) * (double)total;
     // one output per wave for wide lobes and for small levels (few outputs: 16 lanes each would leave the chip empty);
     // measured: 64 lanes per output LOSE on the 256^2 / 128^2 levels (1.37 vs 0.88 ms, 0.55 vs 0.41 ms)
-    if (pairs >= 48.0 && pairs < 4096.0 && res >= 64 && res % 8 == 0 && ((uintptr_t)out & 15) == 0) {
+    if (pairs >= 48.0 && pairs < 4096.0 && res >= 64 && res % 8 == 0 && out_aligned16) {
         const int tiles = 6 * (res / 8) * (res / 8);
-        if (tiles >= 1024) specular_tile_kernel<BWD, 4><<<tiles, 256, 0, s>>>(res, roughness, cos_cut, tab, in, out);
-        else specular_tile_kernel<BWD, 8><<<tiles, 512, 0, s>>>(res, roughness, cos_cut, tab, in, out);
-    } else if (pairs >= 2048.0 || (pairs >= 48.0 && total <= 8192)) specular_kernel<BWD, 64><<<(unsigned)((total * 64 + 255) / 256), 256, 0, s>>>(res, roughness, cos_cut, tab, in, out);
-    else if (pairs >= 48.0) specular_kernel<BWD, 16><<<(unsigned)((total * 16 + 255) / 256), 256, 0, s>>>(res, roughness, cos_cut, tab, in, out);
-    else specular_kernel<BWD, 1><<<(unsigned)((total + 255) / 256), 256, 0, s>>>(res, roughness, cos_cut, tab, in, out);
+        return tiles >= 1024 ? ROUTE_TILE4 : ROUTE_TILE8;
+    }
+    if (pairs >= 2048.0 || (pairs >= 48.0 && total <= 8192)) return ROUTE_TPO64;
+    if (pairs >= 48.0) return ROUTE_TPO16;
+    return ROUTE_TPO1;
+}
+
+template <bool BWD>
+int launch_specular(int res, float roughness, float cos_cut, const float* tab, const float* in, float* out, hipStream_t s) {
+    const long long total = 6LL * res * res;
+    const int tiles = 6 * (res / 8) * (res / 8);
+    switch (specular_route(res, cos_cut, ((uintptr_t)out & 15) == 0)) {
+        case ROUTE_TILE4: specular_tile_kernel<BWD, 4><<<tiles, 256, 0, s>>>(res, roughness, cos_cut, tab, in, out); break;
+        case ROUTE_TILE8: specular_tile_kernel<BWD, 8><<<tiles, 512, 0, s>>>(res, roughness, cos_cut, tab, in, out); break;
+        case ROUTE_TPO64: specular_kernel<BWD, 64><<<(unsigned)((total * 64 + 255) / 256), 256, 0, s>>>(res, roughness, cos_cut, tab, in, out); break;
+        case ROUTE_TPO16: specular_kernel<BWD, 16><<<(unsigned)((total * 16 + 255) / 256), 256, 0, s>>>(res, roughness, cos_cut, tab, in, out); break;
+        default: specular_kernel<BWD, 1><<<(unsigned)((total + 255) / 256), 256, 0, s>>>(res, roughness, cos_cut, tab, in, out); break;
+    }
     return hipGetLastError() == hipSuccess ? GS2M_OK : GS2M_ERR_HIP;
 }
 
 }  // namespace
 
 extern "C" {
+
+int gs2m_specular_cubemap_route(int res, float costheta_cutoff, int out_aligned16) {
+    if (res < 1 || res > 4096) return GS2M_ERR_INVALID_ARG;
+    return specular_route(res, costheta_cutoff, out_aligned16 != 0);
+}
 
 int gs2m_diffuse_cubemap_forward(int res, const float* cubemap, float* out, void* stream) {
     if (res < 1 || res > 1024 || !cubemap || !out) return GS2M_ERR_INVALID_ARG;

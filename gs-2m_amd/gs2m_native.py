@@ -95,6 +95,7 @@ SIGNATURES = {
     "gs2m_cubemap_texel_table": (i, [i, p, s]),
     "gs2m_specular_cubemap_forward": (i, [i, f, f, p, p, p, s]),
     "gs2m_specular_cubemap_backward": (i, [i, f, f, p, p, p, s]),
+    "gs2m_specular_cubemap_route": (i, [i, f, i]),
     "gs2m_specular_cubemap_normalized_forward": (i, [i, f, f, p, p, p, p, s]),
     "gs2m_specular_cubemap_normalized_backward": (i, [i, f, f, p, p, p, p, p, s]),
     # include/gs2m_pbr.h

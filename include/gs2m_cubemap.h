@@ -31,6 +31,12 @@ int gs2m_specular_cubemap_forward(int res, float roughness, float costheta_cutof
 int gs2m_specular_cubemap_backward(int res, float roughness, float costheta_cutoff, const float* texel_table, const float* dL_dout,
                                    float* dL_dcubemap, void* stream);
 
+/* Host-only query, launches nothing: the kernel the four specular calls run at this level, forward and backward alike --
+ * 0, 1, 2: 1, 16 or 64 lanes per output texel; 3, 4: one 8x8 tile of outputs per workgroup of 8 or 4 waves.  out_aligned16:
+ * whether the forward's `out` (the backward's `dL_dcubemap`) is 16-byte aligned; the tile kernels need it.  Negative: the
+ * status with which the calls refuse `res`.  The kernel-level tests read the route of each of their cases from here. */
+int gs2m_specular_cubemap_route(int res, float costheta_cutoff, int out_aligned16);
+
 /* The same operator INCLUDING the division by the weight sum (what `specular_cubemap` returns, render_utils/ops.py:391-403) and
  * its backward: out, dL_dout (6, res, res, 3); raw (6, res, res, 4), 16-byte aligned, is written by the forward and must be
  * handed to the backward unchanged; scratch: (6, res, res, 4) floats, 16-byte aligned. */

@@ -17,9 +17,12 @@
 // V spans longitudes psi_V +- asin(sin(theta) / |V_xz|).
 //
 // 1, 16 or 64 lanes per output texel by the size of the cone (a 512^2 level with a sub-texel lobe has 1.5M outputs of
-// ~11 pairs, a 128^2 level with a 15-degree lobe 98k outputs of ~1600).  A pair costs ~5 operations for the cone test
-// (directions are recomputed, not loaded: loading a 16-byte table row per pair made the kernel L2-bandwidth bound)
-// and, inside the cone, a 12-byte colour load and ~12 more operations.
+// ~11 pairs, a 128^2 level with a 15-degree lobe 98k outputs of ~1600), one wave per 8x8 tile of outputs in between.
+// A pair costs ~5 operations for the cone test (directions are recomputed, not loaded: loading a 16-byte table row per
+// pair made the kernel L2-bandwidth bound) and, inside the cone, a 12-byte colour load and ~12 more operations.
+// The two specular kernels differ in how they walk the texels, i.e. in the order of each output's sum.  Which pairs count
+// and what a pair weighs is defined once for both kernels and both directions: face_point, FaceDot (L . V), cone_box,
+// Lobe, OutTexel, Acc::add (the pair weight), store_result and axis_area.
 #include "common.h"
 #include "../../include/gs2m_cubemap.h"
 
@@ -47,14 +50,7 @@ __device__ __forceinline__ V3 face_point(int side, float fx, float fy) {  // unn
 __device__ __forceinline__ V3 texel_dir(int x, int y, int side, int N) {  // cubemap.cu:32-46
     const float fx = 2.0f * (((float)x + 0.5f) / (float)N) - 1.0f;
     const float fy = 2.0f * (((float)y + 0.5f) / (float)N) - 1.0f;
-    switch (side) {
-        case 0: return safe_normalize(v3(1.f, -fy, -fx));
-        case 1: return safe_normalize(v3(-1.f, -fy, fx));
-        case 2: return safe_normalize(v3(fx, 1.f, fy));
-        case 3: return safe_normalize(v3(fx, -1.f, -fy));
-        case 4: return safe_normalize(v3(fx, -fy, 1.f));
-        default: return safe_normalize(v3(-fx, -fy, -1.f));
-    }
+    return safe_normalize(face_point(side, fx, fy));
 }
 
 // world direction -> the face's own frame, in which the face is the plane z = 1 and (x, y) are the face coordinates
@@ -69,15 +65,12 @@ __device__ __forceinline__ V3 to_face_frame(int side, V3 v) {
     }
 }
 
-__device__ __forceinline__ float texel_area(int x, int y, int N) {  // cubemap.cu:17-30
+__device__ __forceinline__ float axis_area(int x, int N) {  // cubemap.cu:17-30, one axis
     if (N <= 1) return 1.f;
-    const int H = N / 2;
-    x = abs(x - H);
-    y = abs(y - H);
-    const float dx = atanf((float)(x + 1) / (float)H) - atanf((float)x / (float)H);
-    const float dy = atanf((float)(y + 1) / (float)H) - atanf((float)y / (float)H);
-    return dx * dy;
+    const int H = N / 2, k = abs(x - H);
+    return atanf((float)(k + 1) / (float)H) - atanf((float)k / (float)H);
 }
+__device__ __forceinline__ float texel_area(int x, int y, int N) { return axis_area(x, N) * axis_area(y, N); }
 
 // texel index range [lo, hi] along one face axis that can contain directions within the cone (sin_t = sin of the half
 // angle) about c = V in the face frame; `u` is the in-plane component of that axis.  Empty: lo > hi.
@@ -93,6 +86,25 @@ __device__ __forceinline__ void cone_range(float u, float cz, float sin_t, int N
     if (a0 > 1.f || a1 < -1.f) { lo = 1; hi = 0; return; }
     lo = max((int)floorf((fmaxf(a0, -1.f) + 1.f) * (0.5f * (float)N)) - 1, 0);
     hi = min((int)floorf((fminf(a1, 1.f) + 1.f) * (0.5f * (float)N)) + 1, N - 1);
+}
+
+// The box [x0, x1] x [y0, y1] of face s outside which no texel lies within the cone (cos_cut, sin_t) about Vo.  False, and
+// at least one of the ranges empty as cone_range leaves it: the cone misses the face.
+__device__ __forceinline__ bool cone_box(int s, V3 Vo, float cos_cut, float sin_t, int N, int& x0, int& x1, int& y0, int& y1) {
+    x0 = 1; x1 = 0; y0 = 1; y1 = 0;  // (one exit: with early returns specular_kernel<., 16> took 2 more VGPRs, one wave less per SIMD)
+    const V3 c = to_face_frame(s, Vo);
+    // No box when the whole cone is behind the face's plane, nor when it misses the face's wedge |longitude| <= pi/4 along an
+    // axis: sqrt(2) rho sin(psi - pi/4) = |u| - cz exceeds sqrt(2) sin_t (psi, rho: cone_range's polar coordinates).
+    // cone_range finds the same by way of atan2 / asin / tan -- ~300 instructions per axis, and with a narrow lobe (the 256^2
+    // level: 28 steps of box per output) the five faces it ends up rejecting cost twice what the box of the sixth costs.  The
+    // margin (2e-3 against cone_range's 1e-4 rad) makes this a strict subset of its rejections: the boxes that remain, and
+    // with them the order of every sum, are unchanged.
+    if (cos_cut <= 0.70710678f) { x0 = 0; x1 = N - 1; y0 = 0; y1 = N - 1; }  // half-angle >= 45 deg: no useful box
+    else if (c.z > -sin_t && !(fmaxf(fabsf(c.x), fabsf(c.y)) - c.z > 1.41421356f * sin_t + 2e-3f)) {
+        cone_range(c.x, c.z, sin_t, N, x0, x1);
+        cone_range(c.y, c.z, sin_t, N, y0, y1);
+    }
+    return x0 <= x1 && y0 <= y1;
 }
 
 // ---------------------------------------------------------------- diffuse
@@ -129,10 +141,82 @@ __global__ void __launch_bounds__(64) diffuse_kernel(int N, const float* __restr
 // area(x, y) = ax[x] * ax[y]; ax is the one table (res floats), and for unit vectors V . H = sqrt((1 + L . V) / 2).
 __global__ void __launch_bounds__(256) axis_area_kernel(int N, float* __restrict__ ax) {
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
-    if (x >= N) return;
-    if (N <= 1) { ax[x] = 1.f; return; }
-    const int H = N / 2, k = abs(x - H);
-    ax[x] = atanf((float)(k + 1) / (float)H) - atanf((float)k / (float)H);
+    if (x < N) ax[x] = axis_area(x, N);
+}
+
+// The GGX lobe of a level: the cone L . V >= cos_cut with the sine of its half-angle, alpha^2 / pi and (alpha^2 - 1) / 2 of
+// the weight (alpha = roughness^2), and cos_cut > 0 (every lobe narrower than a hemisphere).
+struct Lobe { float cos_cut, sin_t, pi_inv_a2, a2m1h; bool pos_cut; };
+__device__ __forceinline__ Lobe make_lobe(float roughness, float cos_cut) {
+    const float alpha = roughness * roughness, alpha_sqr = alpha * alpha;
+    return {cos_cut, sqrtf(fmaxf(1.f - cos_cut * cos_cut, 0.f)), alpha_sqr / 3.14159265358979323846f, 0.5f * (alpha_sqr - 1.f), cos_cut > 0.f};
+}
+
+__device__ __forceinline__ float rcp_len(float fx, float fy) { return __builtin_amdgcn_rsqf((fx * fx + fy * fy) + 1.f); }  // 1 / |P|
+
+// The texel a thread sums for: index, face grid (the coordinate of texel k along either axis is org + step * k), normalised
+// direction Vo for the boxes, unnormalised face point Po and ro = 1 / |Po| for L . V.
+struct OutTexel { int ox, oy, os, o; float step, org, ro; V3 Vo, Po; };
+__device__ __forceinline__ OutTexel out_texel(int os, int oy, int ox, int N) {
+    const float step = 2.0f / (float)N, org = 1.0f / (float)N - 1.0f;
+    const float fxo = org + step * (float)ox, fyo = org + step * (float)oy;
+    return {ox, oy, os, (os * N + oy) * N + ox, step, org, rcp_len(fxo, fyo), texel_dir(ox, oy, os, N), face_point(os, fxo, fyo)};
+}
+
+// L . V must come out bit-identical whichever of the two texels plays the output (the backward applies the same
+// cone test with the roles swapped; a pair accepted one way and rejected the other breaks the adjoint): products of
+// the UNNORMALISED face points summed in world-axis order, (x + y) + z, times the product of the two reciprocal lengths.
+// The face's selection is hoisted out of the texel loops (left inside, the switch on the face costs ~20 scalar branches
+// per pair): exactly one axis carries fx, the others are constant or carry fy, so  P_o . P_t = (dc fx + b) + e  with
+// b = bk + br fy, e = ek + er fy per row  (adding an exact 0 changes nothing, and the commuted first sum of faces 0 / 1
+// is the same number).
+struct FaceDot {
+    float dc, bk, br, ek, er;
+    __device__ __forceinline__ float b(float fy) const { return bk + br * fy; }
+    __device__ __forceinline__ float e(float fy) const { return ek + er * fy; }
+    __device__ __forceinline__ float cosine(float fx, float b, float e, float ro, float rt) const { return ((dc * fx + b) + e) * (ro * rt); }
+};
+__device__ __forceinline__ FaceDot face_dot(int s, V3 Po) {
+    switch (s) {
+        case 0: return {-Po.z, Po.x, -Po.y, 0.f, 0.f};     // ( 1, -fy, -fx)
+        case 1: return {Po.z, -Po.x, -Po.y, 0.f, 0.f};     // (-1, -fy,  fx)
+        case 2: return {Po.x, Po.y, 0.f, 0.f, Po.z};       // (fx,  1,  fy)
+        case 3: return {Po.x, -Po.y, 0.f, 0.f, -Po.z};     // (fx, -1, -fy)
+        case 4: return {Po.x, 0.f, -Po.y, Po.z, 0.f};      // (fx, -fy,  1)
+        default: return {-Po.x, 0.f, -Po.y, -Po.z, 0.f};   // (-fx, -fy, -1)
+    }
+}
+
+struct Acc {  // one output's sums: three colour channels and the weight
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, ws = 0.f;
+    // The pair whose L . V is d (area: already x 1/4).  D_ggx at cos^2(theta_h) = V.H^2 = (1 + L.V) / 2 for unit vectors: no
+    // half vector, no square root; the clamp of ndfGGX (cubemap.cu:193-198) cannot bind for L.V in [cutoff, 1]
+    // (the file is compiled with -ffp-contract=off: the FMAs are spelled out where rounding symmetry is not at stake)
+    // (a branch-free form -- weight 0 outside the cone -- was measured: 3-13 % slower; the exec-mask regions do skip work)
+    template <bool BWD>
+    __device__ __forceinline__ void add(const Lobe& lb, float d, float area, float c0, float c1, float c2) {
+        if (d >= lb.cos_cut) {
+            const float den = __builtin_fmaf(1.f + d, lb.a2m1h, 1.f);  // cos^2 (alpha^2 - 1) + 1
+            // inside the cone d >= cos_cut; for a positive cutoff max(d, 0) = d (a wave-uniform select)
+            const float k = (lb.pos_cut ? d : fmaxf(d, 0.f)) * lb.pi_inv_a2 * __builtin_amdgcn_rcpf(den * den);
+            const float w = BWD ? k : k * area;
+            a0 = __builtin_fmaf(w, c0, a0); a1 = __builtin_fmaf(w, c1, a1); a2 = __builtin_fmaf(w, c2, a2);
+            ws += w;
+        }
+    }
+};
+
+// forward: 4 channels, one float4 where the caller knows `out` to be 16-byte aligned (vec4); backward: 3, times the texel's area
+template <bool BWD>
+__device__ __forceinline__ void store_result(float* out, int o, const Acc& acc, const float* ax, int ox, int oy, bool vec4) {
+    if (BWD) {
+        const float k = ax[ox] * ax[oy] * 0.25f;
+        out[3 * (size_t)o] = acc.a0 * k; out[3 * (size_t)o + 1] = acc.a1 * k; out[3 * (size_t)o + 2] = acc.a2 * k;
+    } else if (vec4) {
+        reinterpret_cast<float4*>(out)[o] = make_float4(acc.a0, acc.a1, acc.a2, acc.ws);
+    } else {
+        out[4 * (size_t)o] = acc.a0; out[4 * (size_t)o + 1] = acc.a1; out[4 * (size_t)o + 2] = acc.a2; out[4 * (size_t)o + 3] = acc.ws;
+    }
 }
 
 // forward: o = output texel, gathers inputs (3 channels in, 4 out); backward: o = input texel, gathers output gradients
@@ -146,66 +230,15 @@ __global__ void __launch_bounds__(256) specular_kernel(int N, float roughness, f
     const int o_raw = gt / TPO, sub = gt % TPO;
     const bool live = o_raw < total;
     const int o = live ? o_raw : total - 1;  // keep whole groups converged for the reduction
-    const int os = o / (N * N), oy = (o / N) % N, ox = o % N;
-    const V3 Vo = texel_dir(ox, oy, os, N);
-    const float alpha = roughness * roughness, alpha_sqr = alpha * alpha;
-    const float sin_t = sqrtf(fmaxf(1.f - cos_cut * cos_cut, 0.f));
+    const OutTexel T = out_texel(o / (N * N), (o / N) % N, o % N, N);
+    const Lobe lb = make_lobe(roughness, cos_cut);
     constexpr int IC = BWD ? 4 : 3;
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, ws = 0.f;
-    // D_ggx at cos^2(theta_h) = V.H^2 = (1 + L.V) / 2 for unit vectors: no half vector, no square root; the clamp of
-    // ndfGGX (cubemap.cu:193-198) cannot bind for L.V in [cutoff, 1]
-    const float pi_inv_a2 = alpha_sqr / 3.14159265358979323846f, a2m1h = 0.5f * (alpha_sqr - 1.f);
-    // (the file is compiled with -ffp-contract=off: the FMAs are spelled out where rounding symmetry is not at stake)
-    // (a branch-free form -- weight 0 outside the cone -- was measured: 3-13 % slower; the exec-mask regions do skip work)
-    auto accumulate = [&](float d, float area, const float c0, const float c1, const float c2) {  // area: already x 1/4
-        if (d >= cos_cut) {
-            const float den = __builtin_fmaf(1.f + d, a2m1h, 1.f);          // cos^2 (alpha^2 - 1) + 1
-            const float k = fmaxf(d, 0.f) * pi_inv_a2 * __builtin_amdgcn_rcpf(den * den);
-            const float w = BWD ? k : k * area;
-            a0 = __builtin_fmaf(w, c0, a0); a1 = __builtin_fmaf(w, c1, a1); a2 = __builtin_fmaf(w, c2, a2);
-            ws += w;
-        }
-    };
-    const float step = 2.0f / (float)N, org = 1.0f / (float)N - 1.0f;  // fx = org + step * x
-    // L . V must come out bit-identical whichever of the two texels plays the output (the backward applies the same
-    // cone test with the roles swapped; a pair accepted one way and rejected the other breaks the adjoint): products of
-    // the UNNORMALISED face points summed in world-axis order, times the product of the two reciprocal lengths
-    const float fxo = org + step * (float)ox, fyo = org + step * (float)oy;
-    const V3 Po = face_point(os, fxo, fyo);
-    const float ro = __builtin_amdgcn_rsqf((fxo * fxo + fyo * fyo) + 1.f);
+    Acc acc;
+    const float step = T.step, org = T.org, ro = T.ro;
     for (int s = 0; s < 6; s++) {
-        const V3 c = to_face_frame(s, Vo);
         int x0, x1, y0, y1;
-        if (cos_cut <= 0.70710678f) { x0 = 0; x1 = N - 1; y0 = 0; y1 = N - 1; }  // half-angle >= 45 deg: no useful box
-        else {
-            if (c.z <= -sin_t) continue;  // the whole cone is behind the face's plane
-            // The cone misses the face's wedge |longitude| <= pi/4 along an axis when sqrt(2) rho sin(psi - pi/4) =
-            // |u| - cz exceeds sqrt(2) sin_t (psi, rho: cone_range's polar coordinates).  cone_range finds the same by way
-            // of atan2 / asin / tan -- ~300 instructions per axis, and with a narrow lobe (the 256^2 level: 28 steps of
-            // box per output) the five faces it ends up rejecting cost twice what the box of the sixth costs.  The margin
-            // (2e-3 against cone_range's 1e-4 rad) makes this a strict subset of its rejections: the boxes that remain,
-            // and with them the order of every sum, are unchanged.
-            if (fmaxf(fabsf(c.x), fabsf(c.y)) - c.z > 1.41421356f * sin_t + 2e-3f) continue;
-            cone_range(c.x, c.z, sin_t, N, x0, x1);
-            cone_range(c.y, c.z, sin_t, N, y0, y1);
-            if (x0 > x1 || y0 > y1) continue;
-        }
-        // (P_o . P_t) summed in world-axis order, (x + y) + z, with the face's selection hoisted out of the loops (left
-        // inside, the switch on the face costs ~20 scalar branches per pair): exactly one axis carries fx, the others
-        // are constant or carry fy, so  P_o . P_t = (c fx + b) + e  with b = bk + br fy, e = ek + er fy  (adding an
-        // exact 0 changes nothing, and the commuted first sum of faces 0 / 1 is the same number)
-        float dc, bk, br, ek, er;
-        switch (s) {
-            case 0: dc = -Po.z; bk = Po.x; br = -Po.y; ek = 0.f; er = 0.f; break;     // ( 1, -fy, -fx)
-            case 1: dc = Po.z; bk = -Po.x; br = -Po.y; ek = 0.f; er = 0.f; break;     // (-1, -fy,  fx)
-            case 2: dc = Po.x; bk = Po.y; br = 0.f; ek = 0.f; er = Po.z; break;       // (fx,  1,  fy)
-            case 3: dc = Po.x; bk = -Po.y; br = 0.f; ek = 0.f; er = -Po.z; break;     // (fx, -1, -fy)
-            case 4: dc = Po.x; bk = 0.f; br = -Po.y; ek = Po.z; er = 0.f; break;      // (fx, -fy,  1)
-            default: dc = -Po.x; bk = 0.f; br = -Po.y; ek = -Po.z; er = 0.f; break;   // (-fx, -fy, -1)
-        }
-        auto cosine = [&](float fx, float fy, float b, float e) {
-            return ((dc * fx + b) + e) * (ro * __builtin_amdgcn_rsqf((fx * fx + fy * fy) + 1.f));
-        };
+        if (!cone_box(s, T.Vo, lb.cos_cut, lb.sin_t, N, x0, x1, y0, y1)) continue;
+        const FaceDot F = face_dot(s, T.Po);
         if (TPO == 64) {
             // one output per wave: the lanes tile the box in 16 x 4 blocks (a box is ~30 texels wide at the 256^2 level:
             // 64 lanes along one row would leave half of them idle), two blocks per step
@@ -215,20 +248,20 @@ __global__ void __launch_bounds__(256) specular_kernel(int N, float roughness, f
                 const bool ra = ya <= y1, rc = yc <= y1;
                 const float fya = org + step * (float)ya, fyc = org + step * (float)yc;
                 const float aya = (BWD || !ra) ? 0.f : 0.25f * ax[ya], ayc = (BWD || !rc) ? 0.f : 0.25f * ax[yc];
-                const float ba = bk + br * fya, ea = ek + er * fya, bc = bk + br * fyc, ec = ek + er * fyc;
+                const float ba = F.b(fya), ea = F.e(fya), bc = F.b(fyc), ec = F.e(fyc);
                 const int r0 = N * N * s + N * (ra ? ya : y0), r1 = N * N * s + N * (rc ? yc : y0);
                 for (int xb = x0; xb <= x1; xb += 16) {
                     const int x = xb + lx;
                     const bool cx = x <= x1;
                     const int xs = cx ? x : x0;
                     const float fx = org + step * (float)xs;
-                    const float da = cosine(fx, fya, ba, ea), db = cosine(fx, fyc, bc, ec);
+                    const float da = F.cosine(fx, ba, ea, ro, rcp_len(fx, fya)), db = F.cosine(fx, bc, ec, ro, rcp_len(fx, fyc));
                     const float* pa = in + (uint32_t)(r0 + xs) * (uint32_t)IC;  // 32-bit offset from the uniform base
                     const float* pb = in + (uint32_t)(r1 + xs) * (uint32_t)IC;
                     const float ca0 = pa[0], ca1 = pa[1], ca2 = pa[2], cb0 = pb[0], cb1 = pb[1], cb2 = pb[2];
                     const float axx = BWD ? 0.f : ax[xs];
-                    if (cx && ra) accumulate(da, axx * aya, ca0, ca1, ca2);
-                    if (cx && rc) accumulate(db, axx * ayc, cb0, cb1, cb2);
+                    if (cx && ra) acc.add<BWD>(lb, da, axx * aya, ca0, ca1, ca2);
+                    if (cx && rc) acc.add<BWD>(lb, db, axx * ayc, cb0, cb1, cb2);
                 }
             }
             continue;
@@ -239,32 +272,27 @@ __global__ void __launch_bounds__(256) specular_kernel(int N, float roughness, f
             const int r0 = N * N * s + N * y, r1 = two ? r0 + N : r0;
             const float fya = org + step * (float)y, fyb = fya + step;
             const float aya = BWD ? 0.f : 0.25f * ax[y], ayb = BWD ? 0.f : 0.25f * ax[two ? y + 1 : y];
-            const float ba = bk + br * fya, ea = ek + er * fya, bb = bk + br * fyb, eb = ek + er * fyb;
+            const float ba = F.b(fya), ea = F.e(fya), bb = F.b(fyb), eb = F.e(fyb);
             for (int x = x0 + sub; x <= x1; x += TPO) {
                 const float fx = org + step * (float)x;
-                const float da = cosine(fx, fya, ba, ea), db = cosine(fx, fyb, bb, eb);
+                const float da = F.cosine(fx, ba, ea, ro, rcp_len(fx, fya)), db = F.cosine(fx, bb, eb, ro, rcp_len(fx, fyb));
                 const float* pa = in + (uint32_t)(r0 + x) * (uint32_t)IC;  // 32-bit offset from the uniform base
                 const float* pb = in + (uint32_t)(r1 + x) * (uint32_t)IC;
                 const float ca0 = pa[0], ca1 = pa[1], ca2 = pa[2], cb0 = pb[0], cb1 = pb[1], cb2 = pb[2];
                 const float axx = BWD ? 0.f : ax[x];
-                accumulate(da, axx * aya, ca0, ca1, ca2);
-                if (two) accumulate(db, axx * ayb, cb0, cb1, cb2);
+                acc.add<BWD>(lb, da, axx * aya, ca0, ca1, ca2);
+                if (two) acc.add<BWD>(lb, db, axx * ayb, cb0, cb1, cb2);
             }
         }
     }
     if (TPO > 1) {
 #pragma unroll
         for (int d = TPO / 2; d >= 1; d >>= 1) {
-            a0 += __shfl_xor(a0, d); a1 += __shfl_xor(a1, d); a2 += __shfl_xor(a2, d); ws += __shfl_xor(ws, d);
+            acc.a0 += __shfl_xor(acc.a0, d); acc.a1 += __shfl_xor(acc.a1, d); acc.a2 += __shfl_xor(acc.a2, d); acc.ws += __shfl_xor(acc.ws, d);
         }
     }
     if (!live || sub != 0) return;
-    if (BWD) {
-        const float k = ax[ox] * ax[oy] * 0.25f;
-        out[3 * (size_t)o] = a0 * k; out[3 * (size_t)o + 1] = a1 * k; out[3 * (size_t)o + 2] = a2 * k;
-    } else {
-        out[4 * (size_t)o] = a0; out[4 * (size_t)o + 1] = a1; out[4 * (size_t)o + 2] = a2; out[4 * (size_t)o + 3] = ws;
-    }
+    store_result<BWD>(out, o, acc, ax, T.ox, T.oy, false);
 }
 
 // Mid-size lobes (tens to a couple of thousand pairs per output: the 256^2 and 128^2 levels of a 512^2 light, 80 % of the
@@ -275,8 +303,7 @@ __global__ void __launch_bounds__(256) specular_kernel(int N, float roughness, f
 // per (output, texel) pair 5 operations for L . V from the lane's own constants plus the cone test, and inside the
 // cone the 13 of the weight and the sums.  The 16-lanes-per-output form above spends three times
 // that: addressing and conversions per pair, a 16-lane group that covers a 27-texel row in two steps, row and face
-// set-up repeated by every group, and a shuffle reduction per output.  L . V is formed by the same expression from the
-// same numbers (bit-identical, so forward and backward accept the same pairs); only the order of each output's sum differs
+// set-up repeated by every group, and a shuffle reduction per output.  Only the order of each output's sum differs
 // (row-major over the union box, one lane).
 // SPLIT waves share a tile when the level has too few tiles to fill the chip (128^2: 1536): wave k takes every SPLIT-th row
 // of the union box and the partial sums are added in wave order at the end.
@@ -286,18 +313,11 @@ __global__ void __launch_bounds__(64 * SPLIT) specular_tile_kernel(int N, float 
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int tiles = N >> 3;
     const int os = blockIdx.x / (tiles * tiles), tt = blockIdx.x - os * tiles * tiles;
-    const int ox = (tt % tiles) * 8 + (lane & 7), oy = (tt / tiles) * 8 + (lane >> 3);
-    const int o = (os * N + oy) * N + ox;
-    const V3 Vo = texel_dir(ox, oy, os, N);
-    const float alpha = roughness * roughness, alpha_sqr = alpha * alpha;
-    const float sin_t = sqrtf(fmaxf(1.f - cos_cut * cos_cut, 0.f));
+    const OutTexel T = out_texel(os, (tt / tiles) * 8 + (lane >> 3), (tt % tiles) * 8 + (lane & 7), N);
+    const Lobe lb = make_lobe(roughness, cos_cut);
     constexpr int IC = BWD ? 4 : 3;
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, ws = 0.f;
-    const float pi_inv_a2 = alpha_sqr / 3.14159265358979323846f, a2m1h = 0.5f * (alpha_sqr - 1.f);
-    const float step = 2.0f / (float)N, org = 1.0f / (float)N - 1.0f;
-    const float fxo = org + step * (float)ox, fyo = org + step * (float)oy;
-    const V3 Po = face_point(os, fxo, fyo);
-    const float ro = __builtin_amdgcn_rsqf((fxo * fxo + fyo * fyo) + 1.f);
+    Acc acc;
+    const float step = T.step, org = T.org, ro = T.ro;
     __shared__ float4 s_geo_[SPLIT][64];  // per texel of the segment: fx, 1 / |P_t|, area / 4, colour.x
     __shared__ float2 s_col_[SPLIT][64];  // colour.y, colour.z
     float4* const s_geo = s_geo_[wv];
@@ -305,20 +325,12 @@ __global__ void __launch_bounds__(64 * SPLIT) specular_tile_kernel(int N, float 
     // LDS operations of one wave execute in order: what orders a wave's parking writes and broadcast reads is only the
     // compiler (the waves of a split tile run different trip counts: no workgroup barrier inside the loops)
     auto wave_fence = [] { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); };
-    const bool pos_cut = cos_cut > 0.f;
     // The union of the tile's 64 cone boxes on every face, found ONCE per workgroup: the waves of the tile share the faces
     // (a box costs two cone_range calls: atan2 / asin / tan, ~700 instructions -- as much as 35 texels of the walk).
     __shared__ int s_box[6][4];
     for (int s = wv; s < 6; s += SPLIT) {
-        // this lane's box on face s, exactly as specular_kernel finds it (empty: x0 > x1)
-        const V3 c = to_face_frame(s, Vo);
-        int x0 = N, x1 = -1, y0 = N, y1 = -1;
-        if (cos_cut <= 0.70710678f) { x0 = 0; x1 = N - 1; y0 = 0; y1 = N - 1; }
-        else if (c.z > -sin_t && !(fmaxf(fabsf(c.x), fabsf(c.y)) - c.z > 1.41421356f * sin_t + 2e-3f)) {
-            cone_range(c.x, c.z, sin_t, N, x0, x1);
-            cone_range(c.y, c.z, sin_t, N, y0, y1);
-            if (x0 > x1 || y0 > y1) { x0 = N; x1 = -1; y0 = N; y1 = -1; }
-        }
+        int x0, x1, y0, y1;  // this lane's box on face s; empty: the identity of the min / max below
+        if (!cone_box(s, T.Vo, lb.cos_cut, lb.sin_t, N, x0, x1, y0, y1)) { x0 = N; x1 = -1; y0 = N; y1 = -1; }
         if (__builtin_amdgcn_ballot_w64(x0 <= x1) != 0ull) {  // some output of the tile reaches this face
 #pragma unroll
             for (int d = 32; d >= 1; d >>= 1) {
@@ -333,15 +345,7 @@ __global__ void __launch_bounds__(64 * SPLIT) specular_tile_kernel(int N, float 
         const int X0 = __builtin_amdgcn_readfirstlane(s_box[s][0]), X1 = __builtin_amdgcn_readfirstlane(s_box[s][1]);
         const int Y0 = __builtin_amdgcn_readfirstlane(s_box[s][2]), Y1 = __builtin_amdgcn_readfirstlane(s_box[s][3]);
         if (X0 > X1 || Y0 > Y1) continue;
-        float dc, bk, br, ek, er;  // P_o . P_t = (dc fx + (bk + br fy)) + (ek + er fy), see specular_kernel
-        switch (s) {
-            case 0: dc = -Po.z; bk = Po.x; br = -Po.y; ek = 0.f; er = 0.f; break;
-            case 1: dc = Po.z; bk = -Po.x; br = -Po.y; ek = 0.f; er = 0.f; break;
-            case 2: dc = Po.x; bk = Po.y; br = 0.f; ek = 0.f; er = Po.z; break;
-            case 3: dc = Po.x; bk = -Po.y; br = 0.f; ek = 0.f; er = -Po.z; break;
-            case 4: dc = Po.x; bk = 0.f; br = -Po.y; ek = Po.z; er = 0.f; break;
-            default: dc = -Po.x; bk = 0.f; br = -Po.y; ek = -Po.z; er = 0.f; break;
-        }
+        const FaceDot F = face_dot(s, T.Po);
         // The union box in segments of up to 64 texels of one row.  The lane that owns a texel's column loads its colour
         // (one segment ahead of its use), derives fx, 1 / |P_t| and the area factor, and parks the eight floats in LDS; the
         // evaluation reads them back with wave-uniform addresses (broadcasts).  One wave per workgroup, LDS in order.
@@ -359,7 +363,7 @@ __global__ void __launch_bounds__(64 * SPLIT) specular_tile_kernel(int N, float 
             {
                 const int xt = min(xb + lane, X1);
                 const float fxt = org + step * (float)xt;
-                const float rt = __builtin_amdgcn_rsqf((fxt * fxt + fy * fy) + 1.f);
+                const float rt = rcp_len(fxt, fy);
                 const float at = BWD ? 0.f : ax[xt] * (0.25f * ax[y]);
                 s_geo[lane] = make_float4(fxt, rt, at, q0);
                 s_col[lane] = make_float2(q1, q2);
@@ -369,18 +373,10 @@ __global__ void __launch_bounds__(64 * SPLIT) specular_tile_kernel(int N, float 
             if (xn > X1) { xn = X0; yn = y + SPLIT; }
             const bool more = yn <= Y1;
             if (more) fetch(yn, xn, q0, q1, q2);
-            const float b = bk + br * fy, e = ek + er * fy;
+            const float b = F.b(fy), e = F.e(fy);
             const int w = __builtin_amdgcn_readfirstlane(min(64, X1 - xb + 1));
             auto pair = [&](const float4 g, const float2 cl) {
-                const float d = ((dc * g.x + b) + e) * (ro * g.y);
-                if (d >= cos_cut) {
-                    const float den = __builtin_fmaf(1.f + d, a2m1h, 1.f);
-                    // inside the cone d >= cos_cut; for a positive cutoff (every lobe narrower than a hemisphere) max(d, 0) = d
-                    const float k = (pos_cut ? d : fmaxf(d, 0.f)) * pi_inv_a2 * __builtin_amdgcn_rcpf(den * den);
-                    const float wgt = BWD ? k : k * g.z;
-                    a0 = __builtin_fmaf(wgt, g.w, a0); a1 = __builtin_fmaf(wgt, cl.x, a1); a2 = __builtin_fmaf(wgt, cl.y, a2);
-                    ws += wgt;
-                }
+                acc.add<BWD>(lb, F.cosine(g.x, b, e, ro, g.y), g.z, g.w, cl.x, cl.y);
             };
             // four texels per step, all eight broadcast reads in front of the arithmetic: a read issued inside the cone
             // test's branch waits out the LDS latency there
@@ -401,21 +397,16 @@ __global__ void __launch_bounds__(64 * SPLIT) specular_tile_kernel(int N, float 
     }
     if (SPLIT > 1) {  // partial sums of waves 1 .. SPLIT - 1, added in wave order
         __shared__ float4 s_part[SPLIT][64];
-        s_part[wv][lane] = make_float4(a0, a1, a2, ws);
+        s_part[wv][lane] = make_float4(acc.a0, acc.a1, acc.a2, acc.ws);
         gs2m_sync();
         if (wv != 0) return;
 #pragma unroll
         for (int k = 1; k < SPLIT; k++) {
             const float4 q = s_part[k][lane];
-            a0 += q.x; a1 += q.y; a2 += q.z; ws += q.w;
+            acc.a0 += q.x; acc.a1 += q.y; acc.a2 += q.z; acc.ws += q.w;
         }
     }
-    if (BWD) {
-        const float k = ax[ox] * ax[oy] * 0.25f;
-        out[3 * (size_t)o] = a0 * k; out[3 * (size_t)o + 1] = a1 * k; out[3 * (size_t)o + 2] = a2 * k;
-    } else {
-        reinterpret_cast<float4*>(out)[o] = make_float4(a0, a1, a2, ws);
-    }
+    store_result<BWD>(out, T.o, acc, ax, T.ox, T.oy, true);
 }
 
 // the division by the weight sum (render_utils/ops.py:403) and its backward as part of the operator: in PyTorch the slice /
@@ -433,6 +424,11 @@ __global__ void __launch_bounds__(256) specular_prescale_kernel(int n, const flo
     const float w = raw[i].w;  // d(col / w)/d col = 1 / w; w does not depend on the cubemap
     g4[i] = make_float4(g3[3 * (size_t)i] / w, g3[3 * (size_t)i + 1] / w, g3[3 * (size_t)i + 2] / w, 0.f);
 }
+
+int launched() { return hipGetLastError() == hipSuccess ? GS2M_OK : GS2M_ERR_HIP; }  // after every launch
+
+template <class... P>  // a level's resolution and its buffers, checked before anything is launched
+bool valid_level(int res, int max_res, const P*... buffers) { return res >= 1 && res <= max_res && (... && (buffers != nullptr)); }
 
 // The kernel a specular level runs, forward and backward alike (gs2m_specular_cubemap_route returns this number).
 enum { ROUTE_TPO1 = 0, ROUTE_TPO16 = 1, ROUTE_TPO64 = 2, ROUTE_TILE8 = 3, ROUTE_TILE4 = 4 };
@@ -463,7 +459,7 @@ int launch_specular(int res, float roughness, float cos_cut, const float* tab, c
         case ROUTE_TPO16: specular_kernel<BWD, 16><<<(unsigned)((total * 16 + 255) / 256), 256, 0, s>>>(res, roughness, cos_cut, tab, in, out); break;
         default: specular_kernel<BWD, 1><<<(unsigned)((total + 255) / 256), 256, 0, s>>>(res, roughness, cos_cut, tab, in, out); break;
     }
-    return hipGetLastError() == hipSuccess ? GS2M_OK : GS2M_ERR_HIP;
+    return launched();
 }
 
 }  // namespace
@@ -471,60 +467,59 @@ int launch_specular(int res, float roughness, float cos_cut, const float* tab, c
 extern "C" {
 
 int gs2m_specular_cubemap_route(int res, float costheta_cutoff, int out_aligned16) {
-    if (res < 1 || res > 4096) return GS2M_ERR_INVALID_ARG;
+    if (!valid_level(res, 4096)) return GS2M_ERR_INVALID_ARG;
     return specular_route(res, costheta_cutoff, out_aligned16 != 0);
 }
 
 int gs2m_diffuse_cubemap_forward(int res, const float* cubemap, float* out, void* stream) {
-    if (res < 1 || res > 1024 || !cubemap || !out) return GS2M_ERR_INVALID_ARG;
+    if (!valid_level(res, 1024, cubemap, out)) return GS2M_ERR_INVALID_ARG;
     diffuse_kernel<false><<<6 * res * res, 64, 0, (hipStream_t)stream>>>(res, cubemap, out);
-    return hipGetLastError() == hipSuccess ? GS2M_OK : GS2M_ERR_HIP;
+    return launched();
 }
 
 int gs2m_diffuse_cubemap_backward(int res, const float* dL_dout, float* dL_dcubemap, void* stream) {
-    if (res < 1 || res > 1024 || !dL_dout || !dL_dcubemap) return GS2M_ERR_INVALID_ARG;
+    if (!valid_level(res, 1024, dL_dout, dL_dcubemap)) return GS2M_ERR_INVALID_ARG;
     diffuse_kernel<true><<<6 * res * res, 64, 0, (hipStream_t)stream>>>(res, dL_dout, dL_dcubemap);
-    return hipGetLastError() == hipSuccess ? GS2M_OK : GS2M_ERR_HIP;
+    return launched();
 }
 
 int gs2m_cubemap_texel_table(int res, float* table, void* stream) {
-    if (res < 1 || res > 4096 || !table) return GS2M_ERR_INVALID_ARG;
+    if (!valid_level(res, 4096, table)) return GS2M_ERR_INVALID_ARG;
     axis_area_kernel<<<(res + 255) / 256, 256, 0, (hipStream_t)stream>>>(res, table);
-    return hipGetLastError() == hipSuccess ? GS2M_OK : GS2M_ERR_HIP;
+    return launched();
 }
 
 int gs2m_specular_cubemap_forward(int res, float roughness, float costheta_cutoff, const float* texel_table, const float* cubemap,
                                   float* out, void* stream) {
-    if (res < 1 || res > 4096 || !texel_table || !cubemap || !out) return GS2M_ERR_INVALID_ARG;
-    return launch_specular<false>(res, roughness, costheta_cutoff, texel_table, cubemap, out,
-                                  (hipStream_t)stream);
+    if (!valid_level(res, 4096, texel_table, cubemap, out)) return GS2M_ERR_INVALID_ARG;
+    return launch_specular<false>(res, roughness, costheta_cutoff, texel_table, cubemap, out, (hipStream_t)stream);
 }
 
 int gs2m_specular_cubemap_backward(int res, float roughness, float costheta_cutoff, const float* texel_table, const float* dL_dout,
                                    float* dL_dcubemap, void* stream) {
-    if (res < 1 || res > 4096 || !texel_table || !dL_dout || !dL_dcubemap) return GS2M_ERR_INVALID_ARG;
-    return launch_specular<true>(res, roughness, costheta_cutoff, texel_table, dL_dout, dL_dcubemap,
-                                 (hipStream_t)stream);
+    if (!valid_level(res, 4096, texel_table, dL_dout, dL_dcubemap)) return GS2M_ERR_INVALID_ARG;
+    return launch_specular<true>(res, roughness, costheta_cutoff, texel_table, dL_dout, dL_dcubemap, (hipStream_t)stream);
 }
 
 int gs2m_specular_cubemap_normalized_forward(int res, float roughness, float costheta_cutoff, const float* texel_table,
                                              const float* cubemap, float* raw, float* out, void* stream) {
-    if (res < 1 || res > 4096 || !texel_table || !cubemap || !raw || !out || ((uintptr_t)raw & 15)) return GS2M_ERR_INVALID_ARG;
+    if (!valid_level(res, 4096, texel_table, cubemap, raw, out) || ((uintptr_t)raw & 15)) return GS2M_ERR_INVALID_ARG;
     const int rc = launch_specular<false>(res, roughness, costheta_cutoff, texel_table, cubemap, raw, (hipStream_t)stream);
     if (rc != GS2M_OK) return rc;
     const int n = 6 * res * res;
     specular_normalize_kernel<<<(n + 255) / 256, 256, 0, (hipStream_t)stream>>>(n, reinterpret_cast<const float4*>(raw), out);
-    return hipGetLastError() == hipSuccess ? GS2M_OK : GS2M_ERR_HIP;
+    return launched();
 }
 
 int gs2m_specular_cubemap_normalized_backward(int res, float roughness, float costheta_cutoff, const float* texel_table,
                                               const float* raw, const float* dL_dout, float* scratch, float* dL_dcubemap, void* stream) {
-    if (res < 1 || res > 4096 || !texel_table || !raw || !dL_dout || !scratch || !dL_dcubemap || (((uintptr_t)raw | (uintptr_t)scratch) & 15))
+    if (!valid_level(res, 4096, texel_table, raw, dL_dout, scratch, dL_dcubemap) || (((uintptr_t)raw | (uintptr_t)scratch) & 15))
         return GS2M_ERR_INVALID_ARG;
     const int n = 6 * res * res;
     specular_prescale_kernel<<<(n + 255) / 256, 256, 0, (hipStream_t)stream>>>(n, reinterpret_cast<const float4*>(raw), dL_dout,
                                                                              reinterpret_cast<float4*>(scratch));
-    if (hipGetLastError() != hipSuccess) return GS2M_ERR_HIP;
+    const int rc = launched();
+    if (rc != GS2M_OK) return rc;
     return launch_specular<true>(res, roughness, costheta_cutoff, texel_table, scratch, dL_dcubemap, (hipStream_t)stream);
 }
 

@@ -50,25 +50,29 @@ def _texel_table(res, device):
     return _tables[key]
 
 
+def _specular(fn, args, *tensors):
+    """`fn(res, roughness, cutoff, texel table, *tensors)`; the last tensor is the result and fixes device and resolution."""
+    out = tensors[-1]
+    _native.launch(fn, out.device, out.shape[1], args[0], args[1], _texel_table(out.shape[1], out.device).data_ptr(),
+                   *(t.data_ptr() for t in tensors))
+    return out
+
+
+def _like(t, ch):
+    return torch.empty((*t.shape[:3], ch), dtype=torch.float32, device=t.device)
+
+
 class _specular_cubemap(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cubemap, roughness, costheta_cutoff):
         cubemap = _cubemap(cubemap, "cubemap", 3)
-        res = cubemap.shape[1]
-        out = torch.empty((6, res, res, 4), dtype=torch.float32, device=cubemap.device)
-        _native.launch("gs2m_specular_cubemap_forward", cubemap.device, res, float(roughness), float(costheta_cutoff),
-                       _texel_table(res, cubemap.device).data_ptr(), cubemap.data_ptr(), out.data_ptr())
         ctx.args = (float(roughness), float(costheta_cutoff))
-        return out
+        return _specular("gs2m_specular_cubemap_forward", ctx.args, cubemap, _like(cubemap, 4))
 
     @staticmethod
     def backward(ctx, dout):
         dout = _cubemap(dout, "grad", 4)
-        res = dout.shape[1]
-        g = torch.empty((6, res, res, 3), dtype=torch.float32, device=dout.device)
-        _native.launch("gs2m_specular_cubemap_backward", dout.device, res, ctx.args[0], ctx.args[1], _texel_table(res, dout.device).data_ptr(),
-                       dout.data_ptr(), g.data_ptr())
-        return g, None, None
+        return _specular("gs2m_specular_cubemap_backward", ctx.args, dout, _like(dout, 3)), None, None
 
 
 class _specular_cubemap_normalized(torch.autograd.Function):
@@ -78,25 +82,18 @@ class _specular_cubemap_normalized(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cubemap, roughness, costheta_cutoff):
         cubemap = _cubemap(cubemap, "cubemap", 3)
-        res = cubemap.shape[1]
-        raw = torch.empty((6, res, res, 4), dtype=torch.float32, device=cubemap.device)
-        out = torch.empty_like(cubemap)
-        _native.launch("gs2m_specular_cubemap_normalized_forward", cubemap.device, res, float(roughness), float(costheta_cutoff),
-                       _texel_table(res, cubemap.device).data_ptr(), cubemap.data_ptr(), raw.data_ptr(), out.data_ptr())
-        ctx.save_for_backward(raw)
+        raw = _like(cubemap, 4)
         ctx.args = (float(roughness), float(costheta_cutoff))
+        out = _specular("gs2m_specular_cubemap_normalized_forward", ctx.args, cubemap, raw, torch.empty_like(cubemap))
+        ctx.save_for_backward(raw)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         (raw,) = ctx.saved_tensors
         dout = _cubemap(dout, "grad", 3)
-        res = dout.shape[1]
-        scratch = torch.empty_like(raw)
-        g = torch.empty_like(dout)
-        _native.launch("gs2m_specular_cubemap_normalized_backward", dout.device, res, ctx.args[0], ctx.args[1],
-                       _texel_table(res, dout.device).data_ptr(), raw.data_ptr(), dout.data_ptr(), scratch.data_ptr(), g.data_ptr())
-        return g, None, None
+        scratch, g = torch.empty_like(raw), torch.empty_like(dout)
+        return _specular("gs2m_specular_cubemap_normalized_backward", ctx.args, raw, dout, scratch, g), None, None
 
 
 _cutoff_cache = {}

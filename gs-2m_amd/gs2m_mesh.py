@@ -671,12 +671,14 @@ def add_simplify_arguments(ap):
 
 
 def add_texture_arguments(ap):
-    """--texture-size N [--normal-map].  SUPPRESSed defaults: without the flags the namespace is what it was (and gs2m_mesh_texture
+    """--texture-size N [--normal-map] [--ao].  SUPPRESSed defaults: without the flags the namespace is what it was (and gs2m_mesh_texture
     is not imported)."""
     ap.add_argument("--texture-size", type=int, default=argparse.SUPPRESS, metavar="N",
                     help="also write tsdf_textured.glb: the simplified (else the post-processed) mesh with an atlas at most N texels wide")
     ap.add_argument("--normal-map", action="store_true", default=argparse.SUPPRESS,
                     help="with --texture-size: the views' normals as a tangent-space normal map in tsdf_textured.glb")
+    ap.add_argument("--ao", action="store_true", default=argparse.SUPPRESS,
+                    help="with --texture-size: ambient occlusion traced against the mesh in the ORM image's R channel (gs2m_mesh_ao.py)")
 
 
 def simplify_keywords(a, ap=None):
@@ -717,6 +719,8 @@ def parse_args(argv=None):
     a = ap.parse_args(argv)
     if hasattr(a, "normal_map") and not hasattr(a, "texture_size"):
         ap.error("--normal-map needs --texture-size")
+    if hasattr(a, "ao") and not hasattr(a, "texture_size"):
+        ap.error("--ao needs --texture-size")
     simplify_keywords(a, ap)
     if a.dtu and a.tnt:
         ap.error("--dtu and --tnt are two presets: choose one")
@@ -756,7 +760,8 @@ def main(argv=None):
         from gs2m_mesh_texture import texture_mesh
         source = "tsdf_simplified.ply" if simplify_keywords(a) else "tsdf_post.ply"
         texture_mesh(model, cams, read_mesh(os.path.join(a.output, source)), os.path.join(a.output, "tsdf_textured.glb"),
-                     texture_size=a.texture_size, **({"normal_map": True} if hasattr(a, "normal_map") else {}))
+                     texture_size=a.texture_size, **({"normal_map": True} if hasattr(a, "normal_map") else {}),
+                     **({"ao": True} if hasattr(a, "ao") else {}))
 
 
 if __name__ == "__main__":

@@ -210,17 +210,24 @@ def _host(t, dtype):
     return np.asarray(t.detach().cpu().numpy() if torch.is_tensor(t) else t, dtype)
 
 
-def write_material_mesh(file, vertices, triangles, values, seen=None):
+def write_material_mesh(file, vertices, triangles, values, seen=None, occlusion=None):
     """Binary little-endian PLY: float x y z, uchar red green blue (albedo * 255 rounded to nearest, as gs2m_mesh.write_mesh
     rounds), float roughness, float metallic, uchar seen, int32 face lists.  values (V, 5): albedo rgb, roughness, metallic.
-    gs2m_mesh.read_mesh reads the file as a mesh whose vertex colours are the albedo."""
+    gs2m_mesh.read_mesh reads the file as a mesh whose vertex colours are the albedo.  occlusion (V,): the ambient occlusion of
+    gs2m_mesh_ao.vertex_occlusion (1 = open) as a float property `occlusion` after `seen`; without it the file is byte for byte
+    what it was before the property existed."""
     v = _host(vertices, np.float32).reshape(-1, 3)
     t = _host(triangles, np.int32).reshape(-1, 3)
     a = _host(values, np.float32).reshape(-1, 5)
     s = np.ones(len(v), np.uint8) if seen is None else _host(seen, np.uint8).reshape(-1)
     if len(a) != len(v) or len(s) != len(v):
         raise ValueError(f"write_material_mesh: {len(a)} values and {len(s)} flags for {len(v)} vertices")
-    va = np.zeros(len(v), _PLY_VERTEX)
+    ao = None if occlusion is None else _host(occlusion, np.float32).reshape(-1)
+    if ao is not None and len(ao) != len(v):
+        raise ValueError(f"write_material_mesh: {len(ao)} occlusion values for {len(v)} vertices")
+    va = np.zeros(len(v), _PLY_VERTEX if ao is None else np.dtype(_PLY_VERTEX.descr + [("occlusion", "<f4")]))
+    if ao is not None:
+        va["occlusion"] = ao
     for k, n in enumerate("xyz"):
         va[n] = v[:, k]
     for k, n in enumerate(("red", "green", "blue")):
@@ -232,7 +239,7 @@ def write_material_mesh(file, vertices, triangles, values, seen=None):
     head = ("ply\nformat binary_little_endian 1.0\ncomment gs2m_mesh_bake material mesh\n"
             f"element vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\n"
             "property uchar red\nproperty uchar green\nproperty uchar blue\n"
-            "property float roughness\nproperty float metallic\nproperty uchar seen\n"
+            "property float roughness\nproperty float metallic\nproperty uchar seen\n" + ("" if ao is None else "property float occlusion\n") +
             f"element face {len(t)}\nproperty list uchar int vertex_indices\nend_header\n")
     with open(str(file), "wb") as f:
         f.write(head.encode("ascii"))
@@ -242,7 +249,7 @@ def write_material_mesh(file, vertices, triangles, values, seen=None):
 
 def read_material_mesh(file):
     """-> dict(vertices (V, 3) float32, triangles (F, 3) int32, albedo (V, 3) float32 = the bytes / 255, roughness (V,) float32,
-    metallic (V,) float32, seen (V,) bool).  ValueError, naming what is absent, for a PLY without the material properties."""
+    metallic (V,) float32, seen (V,) bool, and occlusion (V,) float32 where the file has the property).  ValueError, naming what is absent, for a PLY without the material properties."""
     from gs2m_mesh import _ply_columns, _ply_elements
     out = {}
     for name, a, is_list in _ply_elements(file):
@@ -256,6 +263,8 @@ def read_material_mesh(file):
             out["vertices"], out["albedo"] = _ply_columns(a, "xyz"), _ply_columns(a, ("red", "green", "blue"), 255.0)
             out["roughness"], out["metallic"] = a["roughness"].astype(np.float32), a["metallic"].astype(np.float32)
             out["seen"] = a["seen"].astype(bool) if "seen" in a.dtype.names else np.ones(len(a), bool)
+            if "occlusion" in a.dtype.names:
+                out["occlusion"] = a["occlusion"].astype(np.float32)
     if "vertices" not in out:
         raise ValueError(f"{file}: no vertex element")
     out.setdefault("triangles", np.zeros((0, 3), np.int32))
@@ -279,9 +288,18 @@ def parser():
     ap.add_argument("--eps", type=float, default=EPS, help="a vertex is in front when z < depth + eps")
     ap.add_argument("--min-weight", type=float, default=MIN_WEIGHT, help="summed cosines a vertex needs to count as seen")
     ap.add_argument("--view-batch", type=int, default=VIEW_BATCH)
+    add_ao_arguments(ap, "a float `occlusion` vertex property")
     from gs2m_ingest import add_ingest_arguments
     add_ingest_arguments(ap)
     return ap
+
+
+def add_ao_arguments(ap, what):
+    """--ao, --ao-rays, --ao-radius of the tools that can trace ambient occlusion (gs2m_mesh_ao.py)"""
+    ap.add_argument("--ao", action="store_true", help=f"trace ambient occlusion against the mesh: {what}")
+    ap.add_argument("--ao-rays", type=int, default=64, metavar="K", help="rays per point")
+    ap.add_argument("--ao-radius", type=float, default=None, metavar="X",
+                    help="how far a ray is followed (default: a quarter of the mesh's bounding-box diagonal)")
 
 
 def main(argv=None):
@@ -300,7 +318,11 @@ def main(argv=None):
     model.load_ply(a.ply)
     mesh = M.read_mesh(a.mesh)
     values, seen, _ = bake_materials(model, cams, mesh, a.metallic, eps=a.eps, view_batch=a.view_batch, min_weight=a.min_weight)
-    write_material_mesh(a.output, mesh.vertices, mesh.triangles, values, seen)
+    occlusion = None
+    if a.ao:
+        from gs2m_mesh_ao import vertex_occlusion
+        occlusion = vertex_occlusion(mesh, rays=a.ao_rays, radius=a.ao_radius, device=model.get_xyz.device)[1]
+    write_material_mesh(a.output, mesh.vertices, mesh.triangles, values, seen, occlusion)
     print(f"[>] {len(cams)} views: {int(seen.sum())} of {len(seen)} vertices seen -> {a.output}")
     return {"out": a.output, "n_views": len(cams), "n_vertices": int(len(seen)), "n_seen": int(seen.sum())}
 

@@ -5,8 +5,8 @@ include/gs2m_simplify.h; gs2m_mesh.simplify_mesh_gpu).
 
 IN is a plain mesh (gs2m_mesh.write_mesh: positions and colours) or a material mesh (gs2m_mesh_bake.py: albedo, roughness,
 metallic, seen), told apart by its vertex properties.  A material mesh keeps its five channels, averaged within a cell over
-the vertices that were `seen` (over all of them where none was: that vertex comes out unseen), and is written as a material
-mesh again, so that gs2m_mesh_view.py --colour pbr loads the result as it loads the input.
+the vertices that were `seen` (over all of them where none was: that vertex comes out unseen) -- an `occlusion` property
+(gs2m_mesh_bake.py --ao) is a sixth channel, averaged like the roughness --, and is written as a material mesh again, so that gs2m_mesh_view.py --colour pbr loads the result as it loads the input.
 """
 import argparse
 import os
@@ -40,13 +40,14 @@ def is_material_ply(file):
 
 
 def load(file):
-    """-> (TriangleMesh, values (V, 5) or None, seen (V,) float32 or None)."""
+    """-> (TriangleMesh, values (V, 5) or None -- (V, 6) with an occlusion property, the last column --, seen (V,) float32 or None)."""
     import gs2m_mesh as M
     if not is_material_ply(file):
         return M.read_mesh(file), None, None
     from gs2m_mesh_bake import read_material_mesh
     m = read_material_mesh(file)
-    values = np.concatenate([m["albedo"], m["roughness"][:, None], m["metallic"][:, None]], axis=1).astype(np.float32)
+    values = np.concatenate([m["albedo"], m["roughness"][:, None], m["metallic"][:, None]] +
+                            ([m["occlusion"][:, None]] if "occlusion" in m else []), axis=1).astype(np.float32)
     return M.TriangleMesh(m["vertices"], m["triangles"], m["albedo"]), values, m["seen"].astype(np.float32)
 
 
@@ -58,7 +59,9 @@ def save(file, mesh, values=None, weight=None):
         return
     from gs2m_mesh_bake import write_material_mesh
     host = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
-    write_material_mesh(file, host(mesh.vertices), host(mesh.triangles), host(values), host(weight) > 0)
+    values = host(values)
+    write_material_mesh(file, host(mesh.vertices), host(mesh.triangles), values[:, :5], host(weight) > 0,
+                        values[:, 5] if values.shape[1] == 6 else None)
 
 
 def main(argv=None):

@@ -274,12 +274,15 @@ def _pad(b, fill):
     return b + fill * (-len(b) % 4)
 
 
-def write_glb(file, positions, normals, uvs, indices, images, tangents=None, normal_image=None):
+def write_glb(file, positions, normals, uvs, indices, images, tangents=None, normal_image=None, occlusion=False):
     """One mesh, one primitive: positions, normals (n, 3) and uvs (n, 2) float32, indices (m,) uint32, images = the PNG files
     (bytes) of the base-colour texture and, optionally, of the metallic-roughness texture, embedded as buffer views.  Buffer
     views and chunks are aligned to 4 bytes; POSITION carries min / max.  tangents (n, 4) float32 and normal_image (a PNG file),
     both or neither: the TANGENT accessor (xyz and the handedness w) and the material's normalTexture; they come after everything
-    else in the buffer, and without them the file is byte for byte what it was before they existed.  -> the bytes written."""
+    else in the buffer, and without them the file is byte for byte what it was before they existed.  occlusion: the second
+    image's R channel is the ambient occlusion: the material's occlusionTexture names the texture of the
+    metallicRoughnessTexture, glTF's ORM packing (two images then); without it, again, the bytes of before.
+    -> the bytes written."""
     pos = np.ascontiguousarray(positions, "<f4").reshape(-1, 3)
     nrm = np.ascontiguousarray(normals, "<f4").reshape(-1, 3)
     uv = np.ascontiguousarray(uvs, "<f4").reshape(-1, 2)
@@ -291,6 +294,8 @@ def write_glb(file, positions, normals, uvs, indices, images, tangents=None, nor
         raise ValueError("write_glb: an index names no vertex")
     if (tangents is None) != (normal_image is None):
         raise ValueError("write_glb: `tangents` and `normal_image` come together")
+    if occlusion and len(images) != 2:
+        raise ValueError("write_glb: the occlusion is the R channel of the second image")
     blobs = [pos.tobytes(), nrm.tobytes(), uv.tobytes(), idx.tobytes()] + images
     if tangents is not None:
         tan = np.ascontiguousarray(tangents, "<f4").reshape(-1, 4)
@@ -324,6 +329,8 @@ def write_glb(file, positions, normals, uvs, indices, images, tangents=None, nor
         "images": [{"bufferView": 4 + k, "mimeType": "image/png"} for k in range(len(images))],
         "accessors": accessors, "bufferViews": views, "buffers": [{"byteLength": len(body)}],
     }
+    if occlusion:
+        doc["materials"][0]["occlusionTexture"] = {"index": 1}
     if tangents is not None:
         n = len(images)
         accessors.append({"bufferView": 4 + n, "componentType": _FLOAT, "count": len(tan), "type": "VEC4"})
@@ -342,7 +349,8 @@ def write_glb(file, positions, normals, uvs, indices, images, tangents=None, nor
 def read_glb(file):
     """What write_glb wrote -> dict(positions, normals (n, 3) float32, uvs (n, 2) float32, indices (m,) uint32, images: list of
     PNG files as bytes -- the base colour and, where the material has one, the metallic-roughness texture --, tangents (n, 4)
-    float32 or None, normal_image: the normal map's PNG file or None, json: the document).  ValueError for anything but a version-2 .glb of one mesh with one primitive."""
+    float32 or None, normal_image: the normal map's PNG file or None, occlusion: whether the material has an occlusionTexture
+    (the R channel of images[1]), json: the document).  ValueError for anything but a version-2 .glb of one mesh with one primitive."""
     with open(str(file), "rb") as f:
         data = f.read()
     if len(data) < 20 or struct.unpack_from("<III", data, 0)[:2] != (GLB_MAGIC, 2) or struct.unpack_from("<I", data, 8)[0] != len(data):
@@ -380,7 +388,7 @@ def read_glb(file):
         images = [b for k, b in enumerate(images) if k != source]
     return dict(positions=accessor(att["POSITION"], "<f4", 3), normals=accessor(att["NORMAL"], "<f4", 3), uvs=accessor(att["TEXCOORD_0"], "<f4", 2),
                 indices=accessor(prim["indices"], "<u4", 1), images=images, tangents=accessor(att["TANGENT"], "<f4", 4) if "TANGENT" in att else None,
-                normal_image=normal_image, json=doc)
+                normal_image=normal_image, occlusion="occlusionTexture" in material, json=doc)
 
 
 def decode_png(data):
@@ -449,9 +457,10 @@ def unwelded_tangents(atlas):
     return out.reshape(-1, 4).float().cpu().numpy()
 
 
-def export_glb(file, atlas, base_color, orm=None, device_png=False, textures_dir=None, normal_map=None):
+def export_glb(file, atlas, base_color, orm=None, device_png=False, textures_dir=None, normal_map=None, occlusion=False):
     """The mesh of `atlas` with its textures (pack_textures's images, and pack_normal_map's as `normal_map`: then with tangents)
-    as one .glb; textures_dir: also the PNG files."""
+    as one .glb; textures_dir: also the PNG files.  occlusion: the R channel of `orm` holds the ambient occlusion
+    (gs2m_mesh_ao.apply_occlusion): the material gets an occlusionTexture."""
     if len(atlas.triangles) == 0:
         raise RuntimeError("export_glb: the mesh has no triangle")
     pngs = encode_png([base_color] + ([orm] if orm is not None else []) + ([normal_map] if normal_map is not None else []), device_png)
@@ -461,9 +470,10 @@ def export_glb(file, atlas, base_color, orm=None, device_png=False, textures_dir
         for name, b in zip(names, pngs):
             with open(os.path.join(textures_dir, name), "wb") as f:
                 f.write(b)
+    more = {"occlusion": True} if occlusion else {}
     if normal_map is None:
-        return write_glb(file, *unwelded(atlas), pngs)
-    return write_glb(file, *unwelded(atlas), pngs[:-1], tangents=unwelded_tangents(atlas), normal_image=pngs[-1])
+        return write_glb(file, *unwelded(atlas), pngs, **more)
+    return write_glb(file, *unwelded(atlas), pngs[:-1], tangents=unwelded_tangents(atlas), normal_image=pngs[-1], **more)
 
 
 # ---- command line ------------------------------------------------------------------------------------------------------------
@@ -491,6 +501,8 @@ def parser():
     ap.add_argument("--eps", type=float, default=EPS, help="a texel is in front when z < depth + eps")
     ap.add_argument("--min-weight", type=float, default=MIN_WEIGHT, help="summed cosines a texel needs to count as seen")
     ap.add_argument("--view-batch", type=int, default=VIEW_BATCH)
+    from gs2m_mesh_bake import add_ao_arguments
+    add_ao_arguments(ap, "the R channel of the ORM image and an occlusionTexture in the .glb (with --rgb: an ORM image of roughness 1, metallic 0)")
     from gs2m_ingest import add_ingest_arguments
     from gs2m_png import add_png_argument
     add_ingest_arguments(ap)
@@ -514,11 +526,14 @@ def read_source_mesh(file):
 
 
 def texture_mesh(model, cams, mesh, output, density=None, texture_size=None, metallic=False, rgb=False, linear=False, device_png=False,
-                 textures_dir=None, eps=EPS, min_weight=MIN_WEIGHT, view_batch=None, vertex_values=None, normal_map=False):
+                 textures_dir=None, eps=EPS, min_weight=MIN_WEIGHT, view_batch=None, vertex_values=None, normal_map=False, ao=False,
+                 ao_rays=64, ao_radius=None):
     """Atlas, bake, pack and export in one call -> dict(out, width, height, density, n_views, n_texels, n_seen).  Texels no view
     reached interpolate `vertex_values` (V, 5): albedo rgb, roughness, metallic, the vertex bake's output; without them the mesh's
     vertex colours, taken as they are for the linear albedo (a PLY says nothing of their transfer), with roughness 1 and metallic 0;
-    a mesh without colours leaves the fallback.  normal_map: the views' normals too, as a tangent-space normal map."""
+    a mesh without colours leaves the fallback.  normal_map: the views' normals too, as a tangent-space normal map.  ao: ambient
+    occlusion traced against the mesh at every texel (gs2m_mesh_ao.texel_occlusion: ao_rays rays followed for ao_radius) into the
+    R channel of the ORM image -- with rgb=True, which has none, one of roughness 1 and metallic 0 is made for it."""
     atlas = build_atlas(mesh, density=density, texture_size=texture_size, device=model.get_xyz.device)
     colours = getattr(mesh, "vertex_colors", None)
     attributes = None
@@ -532,6 +547,13 @@ def texture_mesh(model, cams, mesh, output, density=None, texture_size=None, met
                                     min_weight=min_weight, attributes=attributes, **({"normal_map": True} if normal_map else {}))
     base, orm = pack_textures(values, srgb=not linear)
     extra = {"normal_map": pack_normal_map(atlas, values)} if normal_map else {}
+    if ao:
+        from gs2m_mesh_ao import apply_occlusion, texel_occlusion
+        if orm is None:
+            orm = torch.tensor([255, 255, 0], dtype=torch.uint8, device=base.device).repeat(atlas.height, atlas.width, 1).contiguous()
+        visible, owner = texel_occlusion(atlas, rays=ao_rays, radius=ao_radius)
+        apply_occlusion(orm, owner, visible, ao_rays)
+        extra["occlusion"] = True
     export_glb(output, atlas, base, orm, device_png=device_png, textures_dir=textures_dir, **extra)
     print(f"[>] {len(cams)} views: atlas {atlas.width} x {atlas.height} at {atlas.density:.6g} texels per unit, "
           f"{int(seen.sum())} of {atlas.width * atlas.height} texels seen -> {output}")
@@ -556,7 +578,7 @@ def main(argv=None):
     mesh, vertex_values = read_source_mesh(a.mesh)
     return texture_mesh(model, cams, mesh, a.output, vertex_values=vertex_values, density=a.density, texture_size=a.texture_size, metallic=a.metallic, rgb=a.rgb,
                         linear=a.linear, device_png=a.device_png, textures_dir=a.textures_dir, eps=a.eps, min_weight=a.min_weight,
-                        view_batch=a.view_batch, normal_map=a.normal_map)
+                        view_batch=a.view_batch, normal_map=a.normal_map, **({"ao": True, "ao_rays": a.ao_rays, "ao_radius": a.ao_radius} if a.ao else {}))
 
 
 if __name__ == "__main__":

@@ -10,9 +10,11 @@ encoded as straight-alpha sRGB bytes.  Everything is fp64 on device tensors owne
     python gs-2m_amd/gs2m_mesh_view.py --ply-path MATERIAL.ply -s SCENE --rendering --colour pbr --envmap studio.hdr [--background env]
     python gs-2m_amd/gs2m_mesh_view.py --glb ASSET.glb -s SCENE --rendering --colour texture [--shading smooth]
     python gs-2m_amd/gs2m_mesh_view.py --glb ASSET.glb -s SCENE --rendering --colour pbr --envmap studio.hdr
+    python gs-2m_amd/gs2m_mesh_view.py (--ply-path M.ply | --glb ASSET.glb) -s SCENE --rendering --colour ao
 (the third: a material mesh of gs2m_mesh_bake.py under an environment map; the last two: the textured .glb of
 gs2m_mesh_texture.py, its base colour under the headlight or its materials under an environment map, with its normal map where
-it has one)
+it has one; the last: the ambient occlusion as grey, unlit -- a PLY's `occlusion` property (gs2m_mesh_bake.py --ao) or,
+without one, gs2m_mesh_ao.vertex_occlusion on the fly; a .glb's occlusionTexture (gs2m_mesh_texture.py --ao))
 write views/<stem>.png, still.png, frames/000.png .. 119.png, anim.gif and anim.webp under --out-dir (default: visual/ beside the
 mesh's directory).
 """
@@ -21,6 +23,7 @@ import json
 import math
 import os
 import sys
+import types
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 if _HERE not in sys.path:
@@ -412,9 +415,14 @@ def view_files(a):
 
 def _view_files(a, dev, mesh, tex):
     if tex is not None:
-        if a.colour not in ("texture", "pbr"):
-            raise RuntimeError("--glb is drawn with --colour texture or --colour pbr")
+        if a.colour not in ("texture", "pbr", "ao"):
+            raise RuntimeError("--glb is drawn with --colour texture or --colour pbr, or its occlusion with --colour ao")
         v, f = tex["vertices"], tex["triangles"]
+        if a.colour == "ao":  # the occlusion as a linear grey base colour, drawn unlit
+            from gs2m_mesh_texture import read_glb
+            if tex["orm"] is None or not read_glb(a.glb)["occlusion"]:
+                raise RuntimeError(f"{a.glb}: --colour ao needs a .glb with an occlusionTexture (gs2m_mesh_texture.py --ao writes one)")
+            tex = dict(tex, base_color=tex["orm"][..., :1].expand(-1, -1, 3).contiguous(), normal_map=None)
     else:
         v, f = _mesh_on_device(mesh, dev, "view_files")
     col = None
@@ -422,6 +430,17 @@ def _view_files(a, dev, mesh, tex):
         if mesh.vertex_colors is None:
             raise RuntimeError(f"{a.ply_path}: --colour vertex needs a mesh with vertex colours")
         col = torch.as_tensor(np.asarray(mesh.vertex_colors, np.float32).reshape(-1, 3)).to(dev)
+    if a.colour == "ao" and tex is None:  # the file's occlusion property, else traced here
+        from gs2m_mesh_bake import read_material_mesh
+        try:
+            ao = read_material_mesh(a.ply_path).get("occlusion")
+        except ValueError:
+            ao = None
+        if ao is None:
+            from gs2m_mesh_ao import vertex_occlusion
+            ao = vertex_occlusion(types.SimpleNamespace(vertices=v, triangles=f), device=dev)[1]
+        col = torch.as_tensor(np.asarray(ao.cpu() if torch.is_tensor(ao) else ao, np.float32)).to(dev).reshape(-1, 1).expand(-1, 3).contiguous()
+    unlit = {"ambient": 1.0, "diffuse": 0.0} if a.colour == "ao" else {}
     views = read_cameras_json(a.cameras) if a.cameras else read_colmap_views(a.source_path)
     if not views:
         raise RuntimeError("no camera to render from")
@@ -457,8 +476,9 @@ def _view_files(a, dev, mesh, tex):
                                    background=a.background, **material)
         if tex is not None:
             return shade_views_textured(v, f, tex["uvs"], m, k["fx"], k["fy"], k["cx"], k["cy"], H, W, tex["base_color"], tex["normal_map"],
-                                        not getattr(a, "linear_texture", False), ss=a.ss, normals=tex["normals"] if a.shading == "smooth" else None)
-        return shade_views(v, f, m, k["fx"], k["fy"], k["cx"], k["cy"], H, W, ss=a.ss, shading=a.shading, colors=col)
+                                        not getattr(a, "linear_texture", False) and a.colour != "ao", ss=a.ss,
+                                        normals=tex["normals"] if a.shading == "smooth" else None, **unlit)
+        return shade_views(v, f, m, k["fx"], k["fy"], k["cx"], k["cy"], H, W, ss=a.ss, shading=a.shading, colors=col, **unlit)
 
     if a.rendering:
         os.makedirs(os.path.join(out_dir, "views"), exist_ok=True)
@@ -516,9 +536,10 @@ def parser():
     ap.add_argument("--frames", type=int, default=FRAMES, help=argparse.SUPPRESS)  # for the tests
     ap.add_argument("--shift", type=float, nargs=3, default=(0.0, 0.0, 0.0), metavar=("X", "Y", "Z"), help="moves the mesh (still, animation)")
     ap.add_argument("--shading", choices=("flat", "smooth"), default="flat")
-    ap.add_argument("--colour", choices=("grey", "vertex", "pbr", "texture"), default="grey",
+    ap.add_argument("--colour", choices=("grey", "vertex", "pbr", "texture", "ao"), default="grey",
                     help="pbr: a material mesh (gs2m_mesh_bake.py), or the textures of --glb, shaded under --envmap; the options below "
-                         "belong to it.  texture: the base colour of --glb under the headlight")
+                         "belong to it.  texture: the base colour of --glb under the headlight.  ao: the ambient occlusion as grey, unlit: a PLY's "
+                         "occlusion property or one traced here, a .glb's occlusionTexture")
     ap.add_argument("--envmap", default="", help="lat-long Radiance file (.hdr), as gs2m_relight.py takes it")
     ap.add_argument("--env-res", type=int, default=512, help="cube-map resolution: a power of two >= 64")
     ap.add_argument("--env-samples", type=int, default=None, help="S x S taps per texel, 1 .. 16")

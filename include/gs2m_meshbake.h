@@ -62,8 +62,9 @@ int gs2m_meshbake_resolve(long long n_verts, int C, const double* sums, const do
  *                  cell or corners are out of range, fallback[c].  An empty texel takes fallback[c].
  *   Pack           x = the fp32 value widened, clamped to [0, 1] (NaN -> 0).  base_color[p][d] = floor(255 enc(x_d) + 0.5),
  *                  d < 3, enc the sRGB encode of gs2m_meshview.h when srgb != 0, else the identity.  With C == 5 also
- *                  orm[p] = (255, floor(255 x_3 + 0.5), floor(255 x_4 + 0.5)): occlusion unused, roughness in G, metallic in
- *                  B, glTF's metallicRoughnessTexture layout.  C == 3 (a plain colour bake) takes orm == NULL.
+ *                  orm[p] = (255, floor(255 x_3 + 0.5), floor(255 x_4 + 0.5)): occlusion 1 (gs2m_texture_occlusion of
+ *                  gs2m_meshao.h overwrites R where it is traced), roughness in G, metallic in B, glTF's ORM layout.
+ *                  C == 3 (a plain colour bake) takes orm == NULL.
  *
  * ---- the tangent-space normal map (csrc/tangent_frame.h, shared with gs2m_meshview.h) ----
  *

@@ -1,9 +1,11 @@
-// Ray casting against a triangle mesh (include/gs2m_meshao.h): an LBVH built on the device, a stackless any-hit
-// traversal, ambient occlusion.  fp64 throughout, evaluated as written (-ffp-contract=off): the triangle test and the AO frame
-// are a contract that tests/mesh_ao_ref.py restates bit for bit.
+// Ray casting against a triangle mesh (include/gs2m_meshao.h): an LBVH built on the device, a stackless
+// any-hit and closest-hit traversal, ambient occlusion, and the transfer of a source mesh's detail to the points of another
+// (include/gs2m_meshtransfer.h).  fp64 throughout, evaluated as written (-ffp-contract=off): the triangle test, the AO frame and
+// the transfer's interpolation are a contract that tests/mesh_ao_ref.py and tests/mesh_transfer_ref.py restate bit for bit.
 #include <cmath>
 #include "eval_common.h"
 #include "../../include/gs2m_meshao.h"
+#include "../../include/gs2m_meshtransfer.h"
 
 namespace {
 
@@ -31,8 +33,9 @@ __device__ __forceinline__ void ray_finish(Ray& r) {
     for (int k = 0; k < 3; k++) r.inv[k] = 1.0 / r.d[k];
 }
 
-// the Triangle paragraph
-__device__ __forceinline__ bool hits_triangle(const Ray& r, const double* a, const double* b, const double* c) {
+// the Triangle paragraph up to t, whatever the range says
+__device__ __forceinline__ bool triangle_tuv(const Ray& r, const double* a, const double* b, const double* c, double& det, double& t, double& u,
+                                             double& v) {
     double e1[3], e2[3], T[3], P[3], Q[3];
 #pragma unroll
     for (int k = 0; k < 3; k++) {
@@ -41,15 +44,27 @@ __device__ __forceinline__ bool hits_triangle(const Ray& r, const double* a, con
         T[k] = r.o[k] - a[k];
     }
     cross3(r.d, e2, P);
-    const double det = dot3(e1, P);
+    det = dot3(e1, P);
     if (det == 0.0 || !std::isfinite(det)) return false;
-    const double u = dot3(T, P) / det;
+    u = dot3(T, P) / det;
     if (!(u >= 0.0 && u <= 1.0)) return false;
     cross3(T, e1, Q);
-    const double v = dot3(r.d, Q) / det;
+    v = dot3(r.d, Q) / det;
     if (!(v >= 0.0 && u + v <= 1.0)) return false;
-    const double t = dot3(e2, Q) / det;
-    return t > r.tmin && t <= r.tmax;
+    t = dot3(e2, Q) / det;
+    return true;
+}
+__device__ __forceinline__ bool hits_triangle(const Ray& r, const double* a, const double* b, const double* c) {
+    double det, t, u, v;
+    return triangle_tuv(r, a, b, c, det, t, u, v) && t > r.tmin && t <= r.tmax;
+}
+// the Candidate and Facing paragraphs: closed at both ends
+__device__ __forceinline__ bool candidate(const Ray& r, int facing, const double* a, const double* b, const double* c, double& t, double& u,
+                                          double& v) {
+    double det;
+    if (!triangle_tuv(r, a, b, c, det, t, u, v)) return false;
+    if ((facing > 0 && !(det > 0.0)) || (facing < 0 && !(det < 0.0))) return false;
+    return t >= r.tmin && t <= r.tmax;
 }
 
 __device__ __forceinline__ bool finite3(const double* p) { return std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]); }
@@ -110,6 +125,37 @@ __device__ bool occluded(const Node* __restrict__ nodes, long long n, long long 
         }
     }
     return false;
+}
+
+// the Answer and Closest traversal paragraphs: the same walk, the box test against the best t so far.  The ray is a copy: its tmax
+// shrinks.  A candidate beyond the best fails `t <= r.tmax`; one at the best is kept for the index rule.
+struct Closest {
+    double t, u, v;
+    int tri;
+};
+__device__ Closest closest(const Node* __restrict__ nodes, long long n, long long nv, const double* __restrict__ verts,
+                           const int* __restrict__ tris, Ray r, int skip, int facing) {
+    Closest best = {INFINITY, 0.0, 0.0, -1};
+    const long long total = 2 * n - 1;
+    long long node = 0;
+    for (long long step = 0; step < total && node >= 0 && node < total; step++) {
+        const Node nd = nodes[node];
+        if (!box_maybe_hit(r, nd)) {
+            node = nd.miss;
+        } else if (node >= n - 1) {  // leaf
+            const long long t = nd.left;
+            double a[3], b[3], c[3], ht, hu, hv;
+            if (t >= 0 && t < n && t != skip && load_live(nv, verts, tris, t, a, b, c) && candidate(r, facing, a, b, c, ht, hu, hv) &&
+                (ht < best.t || (ht == best.t && (best.tri < 0 || (int)t < best.tri)))) {
+                best = {ht, hu, hv, (int)t};
+                r.tmax = ht;
+            }
+            node = nd.miss;
+        } else {
+            node = nd.left;
+        }
+    }
+    return best;
 }
 
 // ---- build ----
@@ -295,13 +341,8 @@ __global__ void __launch_bounds__(256) refit_kernel(long long n, Node* __restric
 }
 
 // ---- queries ----
-__global__ void __launch_bounds__(256) occluded_kernel(const Node* __restrict__ nodes, long long n, long long nv, const double* __restrict__ verts,
-                                                       const int* __restrict__ tris, long long n_rays, const double* __restrict__ origins,
-                                                       const double* __restrict__ dirs, double tmin, double tmax,
-                                                       const int* __restrict__ skip, unsigned char* __restrict__ hit) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_rays) return;
-    Ray r;
+__device__ __forceinline__ void load_ray(long long i, const double* __restrict__ origins, const double* __restrict__ dirs, double tmin,
+                                         double tmax, Ray& r) {
 #pragma unroll
     for (int k = 0; k < 3; k++) {
         r.o[k] = origins[3 * i + k];
@@ -310,6 +351,16 @@ __global__ void __launch_bounds__(256) occluded_kernel(const Node* __restrict__ 
     r.tmin = tmin;
     r.tmax = tmax;
     ray_finish(r);
+}
+
+__global__ void __launch_bounds__(256) occluded_kernel(const Node* __restrict__ nodes, long long n, long long nv, const double* __restrict__ verts,
+                                                       const int* __restrict__ tris, long long n_rays, const double* __restrict__ origins,
+                                                       const double* __restrict__ dirs, double tmin, double tmax,
+                                                       const int* __restrict__ skip, unsigned char* __restrict__ hit) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_rays) return;
+    Ray r;
+    load_ray(i, origins, dirs, tmin, tmax, r);
     hit[i] = n > 0 && occluded(nodes, n, nv, verts, tris, r, skip ? skip[i] : -1) ? 1 : 0;
 }
 
@@ -395,6 +446,87 @@ __global__ void __launch_bounds__(256) texture_occlusion_kernel(long long n, con
     orm[3 * p] = (unsigned char)(x < 0.0 ? 0.0 : (x > 255.0 ? 255.0 : x));
 }
 
+__global__ void __launch_bounds__(256) closest_kernel(const Node* __restrict__ nodes, long long n, long long nv, const double* __restrict__ verts,
+                                                      const int* __restrict__ tris, long long n_rays, const double* __restrict__ origins,
+                                                      const double* __restrict__ dirs, double tmin, double tmax, const int* __restrict__ skip,
+                                                      int facing, int* __restrict__ tri, double* __restrict__ t, double* __restrict__ uv) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_rays) return;
+    Closest best = {INFINITY, 0.0, 0.0, -1};
+    if (n > 0) {
+        Ray r;
+        load_ray(i, origins, dirs, tmin, tmax, r);
+        best = closest(nodes, n, nv, verts, tris, r, skip ? skip[i] : -1, facing);
+    }
+    tri[i] = best.tri;
+    t[i] = best.t;
+    uv[2 * i] = best.u;
+    uv[2 * i + 1] = best.v;
+}
+
+// gs2m_meshtransfer.h: one lane per point casts both rays
+__global__ void __launch_bounds__(256) transfer_kernel(const Node* __restrict__ nodes, long long n, long long nv, const double* __restrict__ verts,
+                                                       const int* __restrict__ tris, long long n_points, const double* __restrict__ points,
+                                                       const double* __restrict__ normals, const int* __restrict__ owner, double distance,
+                                                       int two_sided, int channels, const float* __restrict__ att,
+                                                       const double* __restrict__ src_normals, int want_normal, int stride,
+                                                       float* __restrict__ values, int* __restrict__ hit_tri, double* __restrict__ offset) {
+    const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= n_points) return;
+    Closest best = {INFINITY, 0.0, 0.0, -1};
+    double off = 0.0;
+    Ray r;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        r.o[k] = points[3 * p + k];
+        r.d[k] = normals[3 * p + k];
+    }
+    const double nn = dot3(r.d, r.d);
+    if (n > 0 && !(owner && owner[p] < 0) && nn > 0.0 && std::isfinite(nn) && finite3(r.o)) {
+        r.tmin = 0.0;
+        r.tmax = distance;
+        ray_finish(r);
+        best = closest(nodes, n, nv, verts, tris, r, -1, two_sided ? 0 : -1);
+        off = best.t;
+#pragma unroll
+        for (int k = 0; k < 3; k++) r.d[k] = -r.d[k];
+        r.tmax = best.t < distance ? best.t : distance;  // B wins only with a smaller t: nothing beyond t_F is looked at
+        ray_finish(r);
+        const Closest back = closest(nodes, n, nv, verts, tris, r, -1, two_sided ? 0 : 1);
+        if (back.tri >= 0 && (best.tri < 0 || back.t < best.t)) {
+            best = back;
+            off = -back.t;
+        }
+        if (best.tri < 0) off = 0.0;
+    }
+    hit_tri[p] = best.tri;
+    if (offset) offset[p] = off;
+    if (best.tri < 0) return;
+    double a[3], b[3], c[3];
+    if (!load_live(nv, verts, tris, best.tri, a, b, c)) return;  // never: it was hit, so it is live and its indices are in range
+    const size_t i0 = (size_t)tris[3 * (size_t)best.tri], i1 = (size_t)tris[3 * (size_t)best.tri + 1], i2 = (size_t)tris[3 * (size_t)best.tri + 2];
+    const double u = best.u, v = best.v, w = (1.0 - u) - v;
+    float* row = values + (size_t)p * stride;
+    for (int ch = 0; ch < channels; ch++)
+        row[ch] = (float)((w * (double)att[i0 * channels + ch] + u * (double)att[i1 * channels + ch]) + v * (double)att[i2 * channels + ch]);
+    if (!want_normal) return;
+    if (src_normals) {
+#pragma unroll
+        for (int k = 0; k < 3; k++)
+            row[channels + k] = (float)((w * src_normals[3 * i0 + k] + u * src_normals[3 * i1 + k]) + v * src_normals[3 * i2 + k]);
+    } else {
+        double e1[3], e2[3], face[3];
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            e1[k] = b[k] - a[k];
+            e2[k] = c[k] - a[k];
+        }
+        cross3(e1, e2, face);
+#pragma unroll
+        for (int k = 0; k < 3; k++) row[channels + k] = (float)face[k];
+    }
+}
+
 // the checks every query shares
 int query_status(const void* bvh, long long bvh_bytes, long long nv, const double* verts, long long nt, const int* tris) {
     if (nv < 0 || nt < 0) return GS2M_ERR_INVALID_ARG;
@@ -451,6 +583,20 @@ int gs2m_bvh_occluded(const void* bvh, long long bvh_bytes, long long n_verts, c
     return gs2m_status(hipGetLastError());
 }
 
+int gs2m_bvh_closest(const void* bvh, long long bvh_bytes, long long n_verts, const double* verts, long long n_triangles,
+                     const int* triangles, long long n_rays, const double* origins, const double* dirs, double tmin, double tmax,
+                     const int* skip, int facing, int* tri, double* t, double* uv, void* stream) {
+    const int st = query_status(bvh, bvh_bytes, n_verts, verts, n_triangles, triangles);
+    if (st != GS2M_OK) return st;
+    if (n_rays < 0 || tmin != tmin || tmax != tmax || facing < -1 || facing > 1 || (n_rays > 0 && (!origins || !dirs || !tri || !t || !uv)))
+        return GS2M_ERR_INVALID_ARG;
+    if (n_rays == 0) return GS2M_OK;
+    if (n_rays > MAX_LAUNCH) return GS2M_ERR_UNSUPPORTED;
+    closest_kernel<<<blocks_of(n_rays), 256, 0, (hipStream_t)stream>>>((const Node*)bvh, n_triangles, n_verts, verts, triangles, n_rays, origins,
+                                                                       dirs, tmin, tmax, skip, facing, tri, t, uv);
+    return gs2m_status(hipGetLastError());
+}
+
 int gs2m_bvh_ao(const void* bvh, long long bvh_bytes, long long n_verts, const double* verts, long long n_triangles, const int* triangles,
                 long long n_points, const double* points, const double* normals, const int* skip, int R, int K, const double* dirs, double bias,
                 double radius, long long index0, long long seed, int* visible, void* stream) {
@@ -471,6 +617,25 @@ int gs2m_texture_occlusion(long long n_texels, const int* owner, const int* visi
     if (n_texels == 0) return GS2M_OK;
     if (n_texels > MAX_LAUNCH) return GS2M_ERR_UNSUPPORTED;
     texture_occlusion_kernel<<<blocks_of(n_texels), 256, 0, (hipStream_t)stream>>>(n_texels, owner, visible, K, orm);
+    return gs2m_status(hipGetLastError());
+}
+
+int gs2m_mesh_transfer(const void* bvh, long long bvh_bytes, long long n_src_verts, const double* src_verts, long long n_src_triangles,
+                       const int* src_triangles, long long n_points, const double* points, const double* normals, const int* owner,
+                       double distance, int two_sided, int channels, const float* src_attributes, const double* src_normals, int want_normal,
+                       int stride, float* values, int* hit_tri, double* offset, void* stream) {
+    const int st = query_status(bvh, bvh_bytes, n_src_verts, src_verts, n_src_triangles, src_triangles);
+    if (st != GS2M_OK) return st;
+    const long long columns = (long long)channels + (want_normal ? 3 : 0);
+    if (n_points < 0 || !(distance >= 0.0) || channels < 0 || (channels > 0 && !src_attributes) || stride < columns ||
+        (n_points > 0 && (!points || !normals || !hit_tri || (columns > 0 && !values))))
+        return GS2M_ERR_INVALID_ARG;
+    if (n_points == 0) return GS2M_OK;
+    if (n_points > MAX_LAUNCH) return GS2M_ERR_UNSUPPORTED;
+    transfer_kernel<<<blocks_of(n_points), 256, 0, (hipStream_t)stream>>>((const Node*)bvh, n_src_triangles, n_src_verts, src_verts, src_triangles,
+                                                                          n_points, points, normals, owner, distance, two_sided != 0, channels,
+                                                                          src_attributes, src_normals, want_normal != 0, stride, values, hit_tri,
+                                                                          offset);
     return gs2m_status(hipGetLastError());
 }
 

@@ -1,7 +1,7 @@
 """Ray casting against a mesh and ambient occlusion (csrc/mesh_bvh.hip; include/gs2m_meshao.h).
 
 A bounding-volume hierarchy over the mesh is built on the device (`build_bvh`); `occluded` answers "is this segment blocked?" for
-explicit rays; `ambient_occlusion` counts, per point, how many of K cosine-weighted directions about its normal leave the
+explicit rays and `closest` "which triangle does it meet first, and where?" (its user: gs2m_mesh_transfer.py); `ambient_occlusion` counts, per point, how many of K cosine-weighted directions about its normal leave the
 neighbourhood unblocked.  `vertex_occlusion` works at the vertices of a mesh, `texel_occlusion` at the texels of an atlas, whose
 counts `apply_occlusion` writes into the R channel of the ORM image.  The direction tables are data, made on the host
 (`direction_table`); every ray is traced by the library, on device tensors owned here; there is no CPU path.
@@ -55,10 +55,8 @@ def build_bvh(vertices, triangles):
     return Bvh(buf, v, f)
 
 
-def occluded(bvh, origins, dirs, tmin=0.0, tmax=math.inf, skip=None):
-    """Per ray: does origin + t dir, tmin < t <= tmax, hit a triangle other than skip[ray]?  origins, dirs (n, 3); skip (n,) int32
-    triangle ids (negative: none) or None -> (n,) bool on the device."""
-    who = "occluded"
+def _rays(who, origins, dirs, skip):
+    """The checked device tensors of a ray query -> (origins, dirs, skip or None)"""
     o = _on_device(origins, "origins", who, torch.float64, (3,))
     d = _on_device(dirs, "dirs", who, torch.float64, (3,))
     if len(o) != len(d):
@@ -66,9 +64,30 @@ def occluded(bvh, origins, dirs, tmin=0.0, tmax=math.inf, skip=None):
     sk = None if skip is None else _on_device(skip, "skip", who, torch.int32, ())
     if sk is not None and len(sk) != len(o):
         raise RuntimeError(f"{who}: {len(sk)} skip ids for {len(o)} rays")
+    return o, d, sk
+
+
+def occluded(bvh, origins, dirs, tmin=0.0, tmax=math.inf, skip=None):
+    """Per ray: does origin + t dir, tmin < t <= tmax, hit a triangle other than skip[ray]?  origins, dirs (n, 3); skip (n,) int32
+    triangle ids (negative: none) or None -> (n,) bool on the device."""
+    o, d, sk = _rays("occluded", origins, dirs, skip)
     hit = torch.zeros(len(o), dtype=torch.uint8, device=o.device)
     N.launch("gs2m_bvh_occluded", o.device, *bvh._args(), len(o), _ptr(o), _ptr(d), float(tmin), float(tmax), _ptr(sk), _ptr(hit))
     return hit.bool()
+
+
+def closest(bvh, origins, dirs, tmin=0.0, tmax=math.inf, skip=None, facing=0):
+    """Per ray the nearest triangle other than skip[ray] that origin + t dir meets with tmin <= t <= tmax (closed at both ends: a
+    ray that starts on the surface finds it), the smallest index among equal t.  facing: 0 both sides, +1 only the side the
+    triangle's cross(e1, e2) points out of, -1 only the other.  -> (tri (n,) int32, -1 for a miss; t (n,) float64, inf for a miss;
+    uv (n, 2) float64: the hit point is (1 - u - v) a + u b + v c) on the device."""
+    o, d, sk = _rays("closest", origins, dirs, skip)
+    tri = torch.full((len(o),), -1, dtype=torch.int32, device=o.device)
+    t = torch.full((len(o),), math.inf, dtype=torch.float64, device=o.device)
+    uv = torch.zeros((len(o), 2), dtype=torch.float64, device=o.device)
+    N.launch("gs2m_bvh_closest", o.device, *bvh._args(), len(o), _ptr(o), _ptr(d), float(tmin), float(tmax), _ptr(sk), int(facing), _ptr(tri),
+             _ptr(t), _ptr(uv))
+    return tri, t, uv
 
 
 def direction_table(rays, tables, seed=0):

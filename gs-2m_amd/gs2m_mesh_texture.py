@@ -9,10 +9,14 @@ written with the unwelded mesh as one .glb (`export_glb`, `write_glb`; `read_glb
 files runs on device tensors owned here; there is no CPU path.
 
     python gs-2m_amd/gs2m_mesh_texture.py --ply point_cloud.ply -s SCENE --mesh tsdf_simplified.ply -o asset.glb \\
-        (--texture-size N | --density D) [--metallic] [--rgb] [--linear] [--normal-map] [--device-png] [--textures-dir DIR]
+        (--texture-size N | --density D) [--metallic] [--rgb] [--linear] [--normal-map | --normal-map-from SOURCE.ply] [--device-png]
+        [--textures-dir DIR]
 
 With --normal-map the views' world-space normals are baked beside the materials and encoded per texel in the tangent frame of its
 triangle (`pack_normal_map`; csrc/tangent_frame.h): the .glb then carries a TANGENT accessor and a normalTexture.
+With --normal-map-from the colours are still baked from the views, but the normal map's three planes are the geometry of
+SOURCE.ply -- the full mesh this one was simplified from -- found by a ray along each texel's normal
+(gs2m_mesh_transfer.transfer_texels).
 """
 import argparse
 import ctypes as C
@@ -490,8 +494,12 @@ def parser():
     ap.add_argument("--metallic", action="store_true", help="the model's metallic map (default: estimated from the roughness)")
     ap.add_argument("--rgb", action="store_true", help="bake the plain render into a base colour only (a model without materials)")
     ap.add_argument("--linear", action="store_true", help="store the base colour without the sRGB transfer")
-    ap.add_argument("--normal-map", action="store_true",
-                    help="also bake the views' normals into a tangent-space normal map: TANGENT and normalTexture in the .glb")
+    normal = ap.add_mutually_exclusive_group()
+    normal.add_argument("--normal-map", action="store_true",
+                        help="also bake the views' normals into a tangent-space normal map: TANGENT and normalTexture in the .glb")
+    normal.add_argument("--normal-map-from", default=None, metavar="SOURCE.ply",
+                        help="the normal map from the geometry of SOURCE.ply, the full mesh --mesh was simplified from, instead of the "
+                        "views' rendered normals (gs2m_mesh_transfer.py); the colours are baked from the views as without it")
     ap.add_argument("--textures-dir", default=None, metavar="DIR",
                     help="also write base_color.png and metallic_roughness.png (with --normal-map: normal.png) there")
     ap.add_argument("--blender", action="store_true")
@@ -527,13 +535,17 @@ def read_source_mesh(file):
 
 def texture_mesh(model, cams, mesh, output, density=None, texture_size=None, metallic=False, rgb=False, linear=False, device_png=False,
                  textures_dir=None, eps=EPS, min_weight=MIN_WEIGHT, view_batch=None, vertex_values=None, normal_map=False, ao=False,
-                 ao_rays=64, ao_radius=None):
+                 ao_rays=64, ao_radius=None, normal_source=None):
     """Atlas, bake, pack and export in one call -> dict(out, width, height, density, n_views, n_texels, n_seen).  Texels no view
     reached interpolate `vertex_values` (V, 5): albedo rgb, roughness, metallic, the vertex bake's output; without them the mesh's
     vertex colours, taken as they are for the linear albedo (a PLY says nothing of their transfer), with roughness 1 and metallic 0;
     a mesh without colours leaves the fallback.  normal_map: the views' normals too, as a tangent-space normal map.  ao: ambient
     occlusion traced against the mesh at every texel (gs2m_mesh_ao.texel_occlusion: ao_rays rays followed for ao_radius) into the
-    R channel of the ORM image -- with rgb=True, which has none, one of roughness 1 and metallic 0 is made for it."""
+    R channel of the ORM image -- with rgb=True, which has none, one of roughness 1 and metallic 0 is made for it.
+    normal_source: a mesh (the full one `mesh` was simplified from) whose geometric normals, found along each texel's normal by
+    gs2m_mesh_transfer.transfer_texels with its defaults, make the normal map in the place of the views' (not with normal_map)."""
+    if normal_map and normal_source is not None:
+        raise ValueError("texture_mesh: `normal_map` bakes the views' normals, `normal_source` transfers a mesh's: give one of the two")
     atlas = build_atlas(mesh, density=density, texture_size=texture_size, device=model.get_xyz.device)
     colours = getattr(mesh, "vertex_colors", None)
     attributes = None
@@ -547,6 +559,9 @@ def texture_mesh(model, cams, mesh, output, density=None, texture_size=None, met
                                     min_weight=min_weight, attributes=attributes, **({"normal_map": True} if normal_map else {}))
     base, orm = pack_textures(values, srgb=not linear)
     extra = {"normal_map": pack_normal_map(atlas, values)} if normal_map else {}
+    if normal_source is not None:
+        from gs2m_mesh_transfer import transfer_texels
+        extra["normal_map"] = pack_normal_map(atlas, transfer_texels(atlas, normal_source, normal=True)[0])
     if ao:
         from gs2m_mesh_ao import apply_occlusion, texel_occlusion
         if orm is None:
@@ -578,7 +593,8 @@ def main(argv=None):
     mesh, vertex_values = read_source_mesh(a.mesh)
     return texture_mesh(model, cams, mesh, a.output, vertex_values=vertex_values, density=a.density, texture_size=a.texture_size, metallic=a.metallic, rgb=a.rgb,
                         linear=a.linear, device_png=a.device_png, textures_dir=a.textures_dir, eps=a.eps, min_weight=a.min_weight,
-                        view_batch=a.view_batch, normal_map=a.normal_map, **({"ao": True, "ao_rays": a.ao_rays, "ao_radius": a.ao_radius} if a.ao else {}))
+                        view_batch=a.view_batch, normal_map=a.normal_map, **({"ao": True, "ao_rays": a.ao_rays, "ao_radius": a.ao_radius} if a.ao else {}),
+                        **({"normal_source": M.read_mesh(a.normal_map_from)} if a.normal_map_from else {}))
 
 
 if __name__ == "__main__":

@@ -235,8 +235,11 @@ SIGNATURES = {
     "gs2m_bvh_bytes": (i, [ll, p]),
     "gs2m_bvh_build": (i, [ll, p, ll, p, p, ll, s]),
     "gs2m_bvh_occluded": (i, [p, ll, ll, p, ll, p, ll, p, p, d, d, p, p, s]),
+    "gs2m_bvh_closest": (i, [p, ll, ll, p, ll, p, ll, p, p, d, d, p, i, p, p, p, s]),
     "gs2m_bvh_ao": (i, [p, ll, ll, p, ll, p, ll, p, p, p, i, i, p, d, d, ll, ll, p, s]),
     "gs2m_texture_occlusion": (i, [ll, p, p, i, p, s]),
+    # include/gs2m_meshtransfer.h
+    "gs2m_mesh_transfer": (i, [p, ll, ll, p, ll, p, ll, p, p, p, d, i, i, p, p, i, i, p, p, p, s]),
     # include/gs2m_atlas.h
     "gs2m_atlas_workspace_bytes": (i, [ll, p]),
     "gs2m_atlas_count": (i, [ll, ll, p, p, d, p, p, p, s]),

@@ -1,6 +1,7 @@
 /* gs2m_meshao.h -- C ABI of the mesh ray casting (mesh_bvh.hip), part of libgs2m_raster.so: a bounding-volume hierarchy over a
- * triangle mesh, built on the device, a stackless any-hit traversal, and ambient occlusion as its first user.  DESIGN.md §26
- * has the kernel plan; tests/mesh_ao_ref.py restates this contract in fp64 numpy.  The reference has no such step: the
+ * triangle mesh, built on the device, a stackless any-hit traversal with ambient occlusion as its first user, and a closest-hit
+ * query on the same walk (its first user: gs2m_meshtransfer.h).  DESIGN.md §26 and §27 have the kernel plan; tests/mesh_ao_ref.py
+ * and tests/mesh_transfer_ref.py restate this contract in fp64 numpy.  The reference has no such step: the
  * contract is this project's own.  Every expression is fp64 and evaluated as written (-ffp-contract=off) with + - * / and
  * comparisons alone, so the host, the device and numpy give the same bits.  Vertices are double (n_verts, 3), triangles int
  * (n_triangles, 3), the layout gs2m_meshbake_accumulate takes.
@@ -51,6 +52,25 @@
  *                1e-13 of its products, is held to equality).  A ray in the plane of a box face, a ray grazing a box edge and a hit at exactly tmax are
  *                inside the widened box.  A ray with a NaN anywhere accepts every box and misses every triangle.
  *
+ *   Candidate    (gs2m_bvh_closest) e1, e2, P, det, u, Q, v, t exactly as in the Triangle paragraph: the same products in the same
+ *                order, the same misses on det, u and v, the same Dead and skip rules.  The range is CLOSED AT BOTH ENDS: a
+ *                triangle is a candidate iff t >= tmin && t <= tmax, so a ray that starts exactly on the surface (t == 0 with
+ *                tmin = 0) finds it.  This predicate belongs to the closest-hit query alone; Occluded keeps t > tmin.
+ *   Facing       det = -dot(d, cross(e1, e2)).  facing == 0 accepts both signs of det; facing == +1 only det > 0 (the ray meets
+ *                the side cross(e1, e2) points out of); facing == -1 only det < 0.  Any other value: GS2M_ERR_INVALID_ARG.
+ *   Answer       of all candidates the one with the smallest t, among equal t the one with the smallest triangle index:
+ *                tri, t, uv = (u, v) of that candidate; without a candidate tri = -1, t = +inf, u = v = 0.  This does not depend
+ *                on the order of visits: the answer of the traversal is DEFINED as the answer of the loop over all triangles,
+ *                bit for bit, in all four outputs.
+ *   Closest      the Traversal above with tmax replaced, for the box test and the range alike, by the best t so far; a leaf is
+ *   traversal    never left early.  A candidate replaces the best when t < best, or t == best and its index is smaller.  The order
+ *                stays fixed (left first, miss links; not front to back).  The box test is closed at tmax and padded -- "a hit
+ *                at exactly tmax is inside the widened box" -- and the best t is the t of a triangle test, whose rounding the
+ *                margin argument of the Box test paragraph covers: the box of a triangle whose t equals the best so far is not
+ *                rejected, so an equal-t neighbour with a smaller index is never culled, and neither is any nearer candidate.
+ *                The same guards: every index is tested before it is followed, the walk stops after 2 n - 1 nodes, a ray with
+ *                a NaN finds nothing.
+ *
  *   mix32        x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16 on 32-bit unsigned x.
  *   AO           per point p of the call, with its unit normal n (the CALLER normalises: the kernel takes no square root):
  *                r = mix32(the low 32 bits of (index0 + p + seed)) % R picks one of the R tables of K local directions
@@ -67,7 +87,8 @@
  *
  * Every buffer is the caller's and on the device, except `bytes` (HOST).  No call waits for the stream.  Return GS2M_OK (0) or
  * a negative GS2M_ERR_* code (gs2m_raster.h): GS2M_ERR_INVALID_ARG, without a launch, for a negative count, a missing buffer,
- * a bvh buffer smaller than gs2m_bvh_bytes says, K or R < 1, a NaN tmin, tmax, bias or radius; GS2M_ERR_UNSUPPORTED for
+ * a bvh buffer smaller than gs2m_bvh_bytes says, K or R < 1, a NaN tmin, tmax, bias or radius, a facing outside -1 .. 1;
+ * GS2M_ERR_UNSUPPORTED for
  * n_triangles >= 2^30 (the radix sort's bound) or n_verts >= 2^31.  The traversal tests every node and triangle index it
  * reads against the counts it was given before it follows it, and stops after 2 n - 1 nodes. */
 #ifndef GS2M_MESHAO_H
@@ -96,6 +117,12 @@ int gs2m_bvh_build(long long n_verts, const double* verts, long long n_triangles
 int gs2m_bvh_occluded(const void* bvh, long long bvh_bytes, long long n_verts, const double* verts, long long n_triangles,
                       const int* triangles, long long n_rays, const double* origins, const double* dirs, double tmin, double tmax,
                       const int* skip, unsigned char* hit, void* stream);
+
+/* The closest hit per ray (Candidate, Facing, Answer): origins, dirs, skip as above; tri: int (n_rays); t: double (n_rays);
+ * uv: double (n_rays, 2).  One lane per ray.  n_triangles == 0: every ray misses. */
+int gs2m_bvh_closest(const void* bvh, long long bvh_bytes, long long n_verts, const double* verts, long long n_triangles,
+                     const int* triangles, long long n_rays, const double* origins, const double* dirs, double tmin, double tmax,
+                     const int* skip, int facing, int* tri, double* t, double* uv, void* stream);
 
 /* points, normals: double (n_points, 3); skip: int (n_points) or NULL; dirs: double (R, K, 3); visible: int (n_points). */
 int gs2m_bvh_ao(const void* bvh, long long bvh_bytes, long long n_verts, const double* verts, long long n_triangles,

@@ -16,14 +16,38 @@
 // pairs out of a component-wise LDS layout (5 fewer vector instructions per entry, but 76 VGPRs = 6 waves per SIMD
 // and the LDS reads right in front of their use: 0.30 instead of 0.27 ms), and the scalar-load form with the record
 // lines touched ahead by a vector load (no better: the scalar path itself is the latency).
+// What goes through which path (profiles/blend_fwd_scalar_ab.md):
+//   geometry (6 dwords) and the channel quads (12 at fc 9): global -> VGPR -> LDS a chunk ahead, read back per entry as
+//     broadcast ds_read_b128 / one ds_read_b64: 19 LDS-array cycles per entry and wave;
+//   the entry's id: stays in a VGPR of the wave (lane = entry of the chunk), read by v_readlane on the observe path only;
+//   the entry's position in the tile list: not carried.  A pixel's last contributor is kept as (slot in the chunk, an
+//     inline constant of the select; list index, folded once per chunk) and becomes a position by ONE gather from the
+//     list behind the loop.  Before, {id, position + 1} was a fourth LDS read per entry which the compiler fused with
+//     the geometry's second read into a ds_read2_b64 (8 LDS cycles for 16 bytes): 25 cycles per entry, the LDS array
+//     78 % busy and 12 % of the wave time spent waiting to issue an LDS instruction (now 2 %).  0.268 -> 0.255 ms.
+//   Channel quads as the packed FMAs' scalar operands (scalar loads two entries ahead, geometry alone in LDS) were built
+//     and lost, 0.373 ms: profiles/blend_fwd_scalar_ab.md, NOTEBOOK.md.
 // `observe` (forward.cu:348-350: one atomicAdd per pixel) is one integer atomic per (list entry, quadrant) that sees
 // a pixel with T > 0.5, straight into the output tensor (zeroed by the preprocess kernel): only the first few
 // entries of a list do, and the wave stops looking once no live pixel has T > 0.5.
 #include "common.h"
 
+#include <type_traits>
+
 namespace {
 
 typedef float v2f __attribute__((ext_vector_type(2)));
+
+// f(integral_constant<J>), J = 0 .. N - 1, fully unrolled with J a compile-time constant; stops when f returns true
+template <int J, int N, class F>
+__device__ __forceinline__ bool unrolled_until(F&& f) {
+    if constexpr (J < N) {
+        if (f(std::integral_constant<int, J>{})) return true;
+        return unrolled_until<J + 1, N>(f);
+    } else {
+        return false;
+    }
+}
 
 template <int FC>  // feature channels blended (compile time); runtime fc <= FC
 __global__ void __launch_bounds__(64) blend_fwd_q_kernel(
@@ -55,21 +79,23 @@ __global__ void __launch_bounds__(64) blend_fwd_q_kernel(
     // record quads parked per entry: geo0, geo1, channel quads (the bin quad is only needed on the rare observe path)
     constexpr int CH = 16;       // entries per chunk
     constexpr int NS = 2 + KQ;   // quads staged
-    // one LDS block, [buffer][NS quads + the chunk's list entries {Gaussian id, position in the tile list + 1}][CH],
-    // addressed from ONE per-buffer base kept in a VGPR the compiler cannot rematerialise: with separate arrays at
-    // known addresses it re-creates two address registers from SGPRs for every entry (2 of 32 vector instructions)
-    constexpr int BUFQ = NS * CH + CH / 2;  // float4 per buffer
+    // one LDS block, [buffer][NS quads][CH], addressed from ONE per-buffer base kept in a VGPR the compiler cannot
+    // rematerialise: with separate arrays at known addresses it re-creates two address registers from SGPRs for every
+    // entry (2 of 32 vector instructions).  The chunk's Gaussian ids stay in a VGPR (lane = entry), read by v_readlane on the
+    // rare observe path; list positions are not carried at all (see last_slot)
+    constexpr int BUFQ = NS * CH;  // float4 per buffer
     __shared__ float4 s_buf[2 * BUFQ];
     uint32_t lds_zero;
     asm volatile("v_mov_b32 %0, 0" : "=v"(lds_zero));  // opaque 0
     float4* const s_base = s_buf + lds_zero;
     auto q_at = [&](int buf, int slot, int jj) -> float4& { return s_base[buf * BUFQ + slot * CH + jj]; };
-    auto e_at = [&](int buf, int jj) -> uint2& { return reinterpret_cast<uint2*>(s_base + buf * BUFQ + NS * CH)[jj]; };
     const int ej = lane & 15, eq = lane >> 4;  // staging role: entry ej of the chunk, quad slot eq (and eq + 4)
     auto quad_of = [](int slot) { return slot < 2 ? slot : slot + 1; };  // staged slot -> record quad (skips REC_BIN)
 
     float T = 1.0f;
-    uint32_t last_contributor = 0;
+    // the last contributor in two levels, so that the per-entry select takes an inline constant and nothing is read for it:
+    uint32_t last_slot = 0;   // slot + 1 in the CURRENT chunk of the last entry this pixel accepted, 0: none in this chunk
+    uint32_t last_index = 0;  // list index + 1 of the last entry of an EARLIER chunk this pixel accepted, 0: none
     v2f acc[NP];  // acc[k] = channels 2k, 2k + 1
 #pragma unroll
     for (int k = 0; k < NP; k++) acc[k] = v2f{0.f, 0.f};
@@ -81,14 +107,15 @@ __global__ void __launch_bounds__(64) blend_fwd_q_kernel(
     bool watch = true;  // some live pixel may still have T > 0.5 (wave-uniform)
     int ilast = 0;      // list entries up to and including the last one some pixel accepted (wave-uniform)
 
-    // one list entry (index i of the list, slot jj of LDS buffer `buf`): returns true when every pixel has finished
-    auto eval = [&](const int i, const int buf, const int jj) {
+    // one list entry (index i of the list, slot jj of LDS buffer `buf`, the chunk's ids in `ids`): returns true when every
+    // pixel has finished
+    auto eval = [&](const int i, const int buf, auto jc, const uint32_t ids) {
+        constexpr int jj = decltype(jc)::value;
         const float4 a = q_at(buf, 0, jj);
         const float2 b = *reinterpret_cast<const float2*>(&q_at(buf, 1, jj));
         float4 c[KQ];
 #pragma unroll
         for (int q = 0; q < KQ; q++) c[q] = q_at(buf, 2 + q, jj);
-        const uint2 ec = e_at(buf, jj);
         const float dx = a.x - pxf, dy = a.y - pyf;
         const float p2 = gs2m_power(dx, dy, a.z, a.w, b.x);
         const float alpha = fminf(0.99f, b.y * gs2m_exp(p2));
@@ -100,64 +127,72 @@ __global__ void __launch_bounds__(64) blend_fwd_q_kernel(
         if (contrib != 0ull) ilast = i + 1;
         float tw;  // contrib ? T : 0 -- branch-free: non-contributing lanes add 0
         asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(tw) : "v"(T), "s"(contrib));
-        const float w = alpha * tw;
-        const v2f ww = {w, w};
+        // w and test_T share one register PAIR whose halves are both written here: a packed FMA names the pair (it reads w for
+        // both halves, op_sel), and with the upper half left undefined the allocator may put it on the destination of a load
+        // still in flight -- the compiler then waits for that load (the next chunk's records) in front of the first entry
+        v2f wt = {alpha * tw, test_T};
+        asm("" : "+v"(wt));
+        const v2f ww = __builtin_shufflevector(wt, wt, 0, 0);
 #pragma unroll
         for (int q = 0; q < KQ; q++) {
             if (4 * q < NC) acc[2 * q] = __builtin_elementwise_fma(v2f{c[q].x, c[q].y}, ww, acc[2 * q]);
             if (4 * q + 2 < NC) acc[2 * q + 1] = __builtin_elementwise_fma(v2f{c[q].z, c[q].w}, ww, acc[2 * q + 1]);
         }
-        const uint32_t pos1 = ec.y;  // position in the tile list + 1 (parked that way), as the reference counts contributors
-        asm("v_cndmask_b32_e64 %0, %0, %1, %2" : "+v"(last_contributor) : "v"(pos1), "s"(contrib));
+        asm("v_cndmask_b32_e64 %0, %0, %1, %2" : "+v"(last_slot) : "n"(jj + 1), "s"(contrib));
         if (watch) {
             const mask_t half = contrib & __builtin_amdgcn_ballot_w64(T > 0.5f);
             if (half != 0ull) {  // rare: only the front of a list
-                if (lane == 0) atomicAdd(&observe[__builtin_amdgcn_readfirstlane(ec.x)], (int)__popcll(half));  // integer: the order does not matter
+                const uint32_t gid = (uint32_t)__builtin_amdgcn_readlane((int)ids, jj) & GS2M_GID_MASK;
+                if (lane == 0) atomicAdd(&observe[gid], (int)__popcll(half));  // integer: the order does not matter
             }
             // T only falls: once no live pixel is above 0.5 nothing later can be
             watch = (live & __builtin_amdgcn_ballot_w64(T > 0.5f)) != 0ull;
         }
-        asm("v_cndmask_b32_e64 %0, %0, %1, %2" : "+v"(T) : "v"(test_T), "s"(contrib));
+        asm("v_cndmask_b32_e64 %0, %0, %1, %2" : "+v"(T) : "v"(wt.y), "s"(contrib));
         return live == 0ull;
     };
 
     // Software pipeline by chunks of 16 entries: while chunk c is evaluated out of LDS buffer c & 1, the record quads
-    // of chunk c + 1 are in flight towards registers (written to the other buffer after the evaluation) and the list
-    // entries of chunk c + 2 are being fetched.  One wave, in-order LDS: no barriers.
+    // of chunk c + 1 are in flight towards registers (written to the other buffer after the evaluation) and the ids
+    // of chunk c + 2 are being fetched.  One wave, in-order LDS: no barriers.
     const int nchunks = (n + CH - 1) / CH;
-    auto load_entry = [&](int c) {  // entry ej of chunk c (clamped inside the list: the surplus lanes are never evaluated)
-        return list[min(c * CH + ej, n - 1)];
+    auto load_entry = [&](int c) {  // id of entry ej of chunk c (clamped inside the list: the surplus lanes are never evaluated)
+        return list[min(c * CH + ej, n - 1)].x;
     };
     struct Stage { float4 a, b; };
-    auto load_quads = [&](const uint2 e) {  // this lane's two quads of its entry's record
+    auto load_quads = [&](const uint32_t e) {  // this lane's two quads of its entry's record
         Stage st;
-        const float4* p = rec + (size_t)(e.x & GS2M_GID_MASK) * REC_Q;  // the entry carries the quadrant-hit mask above the id
+        const float4* p = rec + (size_t)(e & GS2M_GID_MASK) * REC_Q;  // the entry carries the quadrant-hit mask above the id
         st.a = p[quad_of(eq)];
         st.b = eq + 4 < NS ? p[quad_of(eq + 4)] : make_float4(0.f, 0.f, 0.f, 0.f);
         return st;
     };
-    auto park = [&](int buf, const uint2 e, const Stage& st) {
+    auto park = [&](int buf, const Stage& st) {
         q_at(buf, eq, ej) = st.a;
         if (eq + 4 < NS) q_at(buf, eq + 4, ej) = st.b;
-        if (eq == 0) e_at(buf, ej) = make_uint2(e.x & GS2M_GID_MASK, e.y + 1u);
     };
     if (nchunks > 0) {
-        uint2 e1 = load_entry(0);
-        park(0, e1, load_quads(e1));
-        e1 = nchunks > 1 ? load_entry(1) : e1;
+        uint32_t ids = load_entry(0);  // chunk c
+        park(0, load_quads(ids));
+        uint32_t e1 = nchunks > 1 ? load_entry(1) : ids;
         bool stop = false;
         for (int c = 0; c < nchunks && !stop; c++) {
             Stage st;
-            const uint2 ecur = e1;
+            const uint32_t ecur = e1;  // chunk c + 1
             if (c + 1 < nchunks) st = load_quads(ecur);
             if (c + 2 < nchunks) e1 = load_entry(c + 2);
             const int base = c * CH, buf = c & 1;
-#pragma unroll
-            for (int jj = 0; jj < CH; jj++) {
-                if (base + jj >= n) break;
-                if (eval(base + jj, buf, jj)) { stop = true; break; }
-            }
-            if (c + 1 < nchunks && !stop) park(buf ^ 1, ecur, st);
+            bool every = false;  // every pixel has finished
+            unrolled_until<0, CH>([&](auto jc) {
+                if (base + decltype(jc)::value >= n) return true;
+                every = eval(base + decltype(jc)::value, buf, jc, ids);
+                return every;
+            });
+            stop = every;
+            last_index = last_slot != 0u ? (uint32_t)base + last_slot : last_index;
+            last_slot = 0u;
+            if (c + 1 < nchunks && !stop) park(buf ^ 1, st);
+            ids = ecur;
         }
     }
 
@@ -166,7 +201,8 @@ __global__ void __launch_bounds__(64) blend_fwd_q_kernel(
         const size_t HW = (size_t)H * W;
         const size_t pix = (size_t)py * W + px;
         final_T[pix] = T;
-        n_contrib[pix] = last_contributor;
+        // position in the tile list + 1 of the last contributor, as the reference counts contributors: one gather
+        n_contrib[pix] = last_index != 0u ? list[last_index - 1u].y + 1u : 0u;
         out_color[pix] = acc[0][0] + T * bg[0];
         out_color[HW + pix] = acc[0][1] + T * bg[1];
         out_color[2 * HW + pix] = acc[1][0] + T * bg[2];

@@ -69,16 +69,23 @@ __device__ __forceinline__ bool candidate(const Ray& r, int facing, const double
 
 __device__ __forceinline__ bool finite3(const double* p) { return std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]); }
 
+// a mesh of n triangles over nv vertices and the 2 n - 1 nodes of its hierarchy, as the entry points got them
+struct Mesh {
+    const Node* nodes;
+    long long n, nv;
+    const double* verts;
+    const int* tris;
+};
+
 // the corners of triangle t, or false for a dead one (no vertex is read through an index that has not been tested)
-__device__ __forceinline__ bool load_live(long long nv, const double* __restrict__ verts, const int* __restrict__ tris, long long t, double* a,
-                                          double* b, double* c) {
-    const int ia = tris[3 * t], ib = tris[3 * t + 1], ic = tris[3 * t + 2];
-    if (!ids_in_range(ia, ib, ic, nv)) return false;
+__device__ __forceinline__ bool load_live(const Mesh& m, long long t, double* a, double* b, double* c) {
+    const int ia = m.tris[3 * t], ib = m.tris[3 * t + 1], ic = m.tris[3 * t + 2];
+    if (!ids_in_range(ia, ib, ic, m.nv)) return false;
 #pragma unroll
     for (int k = 0; k < 3; k++) {
-        a[k] = verts[3 * (size_t)ia + k];
-        b[k] = verts[3 * (size_t)ib + k];
-        c[k] = verts[3 * (size_t)ic + k];
+        a[k] = m.verts[3 * (size_t)ia + k];
+        b[k] = m.verts[3 * (size_t)ib + k];
+        c[k] = m.verts[3 * (size_t)ic + k];
     }
     return finite3(a) && finite3(b) && finite3(c);
 }
@@ -106,55 +113,51 @@ __device__ __forceinline__ bool box_maybe_hit(const Ray& r, const Node& n) {
 }
 
 // the Traversal paragraph.  Every index is tested before it is followed and the walk stops after 2 n - 1 nodes: a buffer that
-// was never built gives a wrong answer, not a wild read.
-__device__ bool occluded(const Node* __restrict__ nodes, long long n, long long nv, const double* __restrict__ verts,
-                         const int* __restrict__ tris, const Ray& r, int skip) {
-    const long long total = 2 * n - 1;
+// was never built gives a wrong answer, not a wild read.  at_leaf(triangle, a, b, c) gets every live triangle other than `skip`
+// whose leaf box the ray may hit, and ends the walk by returning true; it may shrink r.tmax, which the box test reads anew.
+// Not __forceinline__: inlined before its callers' other calls, the any-hit loop gets another register allocation and the
+// AO kernel loses 0.75 % (profiles/mesh_bvh_refactor_resources.md); the inliner takes it anyway, no kernel has a call.
+template <class Leaf>
+__device__ void walk(const Mesh& m, const Ray& r, int skip, Leaf at_leaf) {
+    const long long total = 2 * m.n - 1;
     long long node = 0;
     for (long long step = 0; step < total && node >= 0 && node < total; step++) {
-        const Node nd = nodes[node];
+        const Node nd = m.nodes[node];
         if (!box_maybe_hit(r, nd)) {
             node = nd.miss;
-        } else if (node >= n - 1) {  // leaf
+        } else if (node >= m.n - 1) {  // leaf
             const long long t = nd.left;
             double a[3], b[3], c[3];
-            if (t >= 0 && t < n && t != skip && load_live(nv, verts, tris, t, a, b, c) && hits_triangle(r, a, b, c)) return true;
+            if (t >= 0 && t < m.n && t != skip && load_live(m, t, a, b, c) && at_leaf((int)t, a, b, c)) return;
             node = nd.miss;
         } else {
             node = nd.left;
         }
     }
-    return false;
 }
 
-// the Answer and Closest traversal paragraphs: the same walk, the box test against the best t so far.  The ray is a copy: its tmax
-// shrinks.  A candidate beyond the best fails `t <= r.tmax`; one at the best is kept for the index rule.
+__device__ bool occluded(const Mesh& m, const Ray& r, int skip) {
+    bool hit = false;
+    walk(m, r, skip, [&](int, const double* a, const double* b, const double* c) { return hit = hits_triangle(r, a, b, c); });
+    return hit;
+}
+
+// the Answer and Closest traversal paragraphs: no leaf ends the walk, and the ray, a copy, has its tmax shrunk to the best t so
+// far.  A candidate beyond the best fails `t <= r.tmax`; one at the best is kept for the index rule.
 struct Closest {
     double t, u, v;
     int tri;
 };
-__device__ Closest closest(const Node* __restrict__ nodes, long long n, long long nv, const double* __restrict__ verts,
-                           const int* __restrict__ tris, Ray r, int skip, int facing) {
+__device__ Closest closest(const Mesh& m, Ray r, int skip, int facing) {
     Closest best = {INFINITY, 0.0, 0.0, -1};
-    const long long total = 2 * n - 1;
-    long long node = 0;
-    for (long long step = 0; step < total && node >= 0 && node < total; step++) {
-        const Node nd = nodes[node];
-        if (!box_maybe_hit(r, nd)) {
-            node = nd.miss;
-        } else if (node >= n - 1) {  // leaf
-            const long long t = nd.left;
-            double a[3], b[3], c[3], ht, hu, hv;
-            if (t >= 0 && t < n && t != skip && load_live(nv, verts, tris, t, a, b, c) && candidate(r, facing, a, b, c, ht, hu, hv) &&
-                (ht < best.t || (ht == best.t && (best.tri < 0 || (int)t < best.tri)))) {
-                best = {ht, hu, hv, (int)t};
-                r.tmax = ht;
-            }
-            node = nd.miss;
-        } else {
-            node = nd.left;
+    walk(m, r, skip, [&](int tri, const double* a, const double* b, const double* c) {
+        double t, u, v;
+        if (candidate(r, facing, a, b, c, t, u, v) && (t < best.t || (t == best.t && (best.tri < 0 || tri < best.tri)))) {
+            best = {t, u, v, tri};
+            r.tmax = t;
         }
-    }
+        return false;
+    });
     return best;
 }
 
@@ -190,12 +193,11 @@ BvhWs carve(char* base, long long nt) {
 }
 
 // centroid of a live triangle, NaN marks a dead one
-__global__ void __launch_bounds__(256) centroid_kernel(long long nv, long long n, const double* __restrict__ verts, const int* __restrict__ tris,
-                                                       double* __restrict__ cen) {
+__global__ void __launch_bounds__(256) centroid_kernel(const Mesh m, double* __restrict__ cen) {
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (t >= n) return;
+    if (t >= m.n) return;
     double a[3], b[3], c[3];
-    if (load_live(nv, verts, tris, t, a, b, c)) {
+    if (load_live(m, t, a, b, c)) {
 #pragma unroll
         for (int k = 0; k < 3; k++) cen[3 * t + k] = ((a[k] + b[k]) + c[k]) / 3.0;
     } else {
@@ -243,15 +245,14 @@ __global__ void __launch_bounds__(256) key_kernel(long long n, const double* __r
 }
 
 // leaves: box, triangle; the refit's counters; the root has no parent (Karras's kernel writes every other parent)
-__global__ void __launch_bounds__(256) leaf_kernel(long long nv, long long n, const double* __restrict__ verts, const int* __restrict__ tris,
-                                                   const uint32_t* __restrict__ sorted_tri, Node* __restrict__ nodes,
+__global__ void __launch_bounds__(256) leaf_kernel(const Mesh m, const uint32_t* __restrict__ sorted_tri, Node* __restrict__ nodes,
                                                    uint32_t* __restrict__ arrived) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
+    if (i >= m.n) return;
     const long long t = sorted_tri[i];
-    Node& nd = nodes[n - 1 + i];
+    Node& nd = nodes[m.n - 1 + i];
     double a[3], b[3], c[3];
-    if (t < n && load_live(nv, verts, tris, t, a, b, c)) {
+    if (t < m.n && load_live(m, t, a, b, c)) {
 #pragma unroll
         for (int k = 0; k < 3; k++) {
             const double m0 = b[k] < a[k] ? b[k] : a[k], m1 = b[k] > a[k] ? b[k] : a[k];
@@ -353,15 +354,30 @@ __device__ __forceinline__ void load_ray(long long i, const double* __restrict__
     ray_finish(r);
 }
 
-__global__ void __launch_bounds__(256) occluded_kernel(const Node* __restrict__ nodes, long long n, long long nv, const double* __restrict__ verts,
-                                                       const int* __restrict__ tris, long long n_rays, const double* __restrict__ origins,
+__global__ void __launch_bounds__(256) occluded_kernel(const Mesh m, long long n_rays, const double* __restrict__ origins,
                                                        const double* __restrict__ dirs, double tmin, double tmax,
                                                        const int* __restrict__ skip, unsigned char* __restrict__ hit) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n_rays) return;
     Ray r;
     load_ray(i, origins, dirs, tmin, tmax, r);
-    hit[i] = n > 0 && occluded(nodes, n, nv, verts, tris, r, skip ? skip[i] : -1) ? 1 : 0;
+    hit[i] = m.n > 0 && occluded(m, r, skip ? skip[i] : -1) ? 1 : 0;
+}
+
+// point p and its normal, or false for "no point here": a negative entry of `gate` (the skip or owner array; may be null), a
+// normal whose dot(n, n) is not positive and finite, or a coordinate that is not finite.  Such a point casts no ray.  `entry` gets
+// the gate's entry as read, -1 without a gate.
+__device__ __forceinline__ bool load_point(long long p, const double* __restrict__ points, const double* __restrict__ normals,
+                                           const int* __restrict__ gate, double* pt, double* n, int& entry) {
+    entry = gate ? gate[p] : -1;
+    if (gate && entry < 0) return false;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        pt[k] = points[3 * p + k];
+        n[k] = normals[3 * p + k];
+    }
+    const double nn = dot3(n, n);
+    return nn > 0.0 && std::isfinite(nn) && finite3(pt);
 }
 
 __device__ __forceinline__ uint32_t mix32(uint32_t x) {
@@ -378,16 +394,8 @@ struct AoPoint {
 __device__ __forceinline__ bool ao_point(long long p, const double* __restrict__ points, const double* __restrict__ normals,
                                          const int* __restrict__ skip, int R, int K, const double* __restrict__ dirs, double bias, long long index0,
                                          long long seed, AoPoint& a) {
-    a.skip = skip ? skip[p] : -1;
-    if (skip && a.skip < 0) return false;
     double pt[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        pt[k] = points[3 * p + k];
-        a.n[k] = normals[3 * p + k];
-    }
-    const double nn = dot3(a.n, a.n);
-    if (!(nn > 0.0) || !std::isfinite(nn) || !finite3(pt)) return false;
+    if (!load_point(p, points, normals, skip, pt, a.n, a.skip)) return false;
     const uint32_t r = mix32((uint32_t)((u64)index0 + (u64)p + (u64)seed)) % (uint32_t)R;
     a.table = dirs + (size_t)r * K * 3;
     const double s = copysign(1.0, a.n[2]);
@@ -412,8 +420,7 @@ __device__ __forceinline__ void ao_ray(const AoPoint& a, int k, double radius, R
 }
 
 // one wave per point: the lanes take 64 directions per step; the rays share their origin and the top of the tree
-__global__ void __launch_bounds__(256) ao_wave_kernel(const Node* __restrict__ nodes, long long n, long long nv, const double* __restrict__ verts,
-                                                      const int* __restrict__ tris, long long n_points, const double* __restrict__ points,
+__global__ void __launch_bounds__(256) ao_wave_kernel(const Mesh m, long long n_points, const double* __restrict__ points,
                                                       const double* __restrict__ normals, const int* __restrict__ skip, int R, int K,
                                                       const double* __restrict__ dirs, double bias, double radius, long long index0, long long seed,
                                                       int* __restrict__ visible) {
@@ -422,7 +429,7 @@ __global__ void __launch_bounds__(256) ao_wave_kernel(const Node* __restrict__ n
     if (p >= n_points) return;
     AoPoint a;
     int count = K;
-    if (n > 0 && ao_point(p, points, normals, skip, R, K, dirs, bias, index0, seed, a)) {
+    if (m.n > 0 && ao_point(p, points, normals, skip, R, K, dirs, bias, index0, seed, a)) {
         count = 0;
         for (int k0 = 0; k0 < K; k0 += 64) {
             const int k = k0 + lane;
@@ -430,7 +437,7 @@ __global__ void __launch_bounds__(256) ao_wave_kernel(const Node* __restrict__ n
             if (k < K) {
                 Ray r;
                 ao_ray(a, k, radius, r);
-                open = !occluded(nodes, n, nv, verts, tris, r, a.skip);
+                open = !occluded(m, r, a.skip);
             }
             count += __popcll(__ballot(open));
         }
@@ -446,17 +453,16 @@ __global__ void __launch_bounds__(256) texture_occlusion_kernel(long long n, con
     orm[3 * p] = (unsigned char)(x < 0.0 ? 0.0 : (x > 255.0 ? 255.0 : x));
 }
 
-__global__ void __launch_bounds__(256) closest_kernel(const Node* __restrict__ nodes, long long n, long long nv, const double* __restrict__ verts,
-                                                      const int* __restrict__ tris, long long n_rays, const double* __restrict__ origins,
+__global__ void __launch_bounds__(256) closest_kernel(const Mesh m, long long n_rays, const double* __restrict__ origins,
                                                       const double* __restrict__ dirs, double tmin, double tmax, const int* __restrict__ skip,
                                                       int facing, int* __restrict__ tri, double* __restrict__ t, double* __restrict__ uv) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n_rays) return;
     Closest best = {INFINITY, 0.0, 0.0, -1};
-    if (n > 0) {
+    if (m.n > 0) {
         Ray r;
         load_ray(i, origins, dirs, tmin, tmax, r);
-        best = closest(nodes, n, nv, verts, tris, r, skip ? skip[i] : -1, facing);
+        best = closest(m, r, skip ? skip[i] : -1, facing);
     }
     tri[i] = best.tri;
     t[i] = best.t;
@@ -465,8 +471,7 @@ __global__ void __launch_bounds__(256) closest_kernel(const Node* __restrict__ n
 }
 
 // gs2m_meshtransfer.h: one lane per point casts both rays
-__global__ void __launch_bounds__(256) transfer_kernel(const Node* __restrict__ nodes, long long n, long long nv, const double* __restrict__ verts,
-                                                       const int* __restrict__ tris, long long n_points, const double* __restrict__ points,
+__global__ void __launch_bounds__(256) transfer_kernel(const Mesh m, long long n_points, const double* __restrict__ points,
                                                        const double* __restrict__ normals, const int* __restrict__ owner, double distance,
                                                        int two_sided, int channels, const float* __restrict__ att,
                                                        const double* __restrict__ src_normals, int want_normal, int stride,
@@ -476,23 +481,18 @@ __global__ void __launch_bounds__(256) transfer_kernel(const Node* __restrict__ 
     Closest best = {INFINITY, 0.0, 0.0, -1};
     double off = 0.0;
     Ray r;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        r.o[k] = points[3 * p + k];
-        r.d[k] = normals[3 * p + k];
-    }
-    const double nn = dot3(r.d, r.d);
-    if (n > 0 && !(owner && owner[p] < 0) && nn > 0.0 && std::isfinite(nn) && finite3(r.o)) {
+    int own;
+    if (m.n > 0 && load_point(p, points, normals, owner, r.o, r.d, own)) {
         r.tmin = 0.0;
         r.tmax = distance;
         ray_finish(r);
-        best = closest(nodes, n, nv, verts, tris, r, -1, two_sided ? 0 : -1);
+        best = closest(m, r, -1, two_sided ? 0 : -1);
         off = best.t;
 #pragma unroll
         for (int k = 0; k < 3; k++) r.d[k] = -r.d[k];
         r.tmax = best.t < distance ? best.t : distance;  // B wins only with a smaller t: nothing beyond t_F is looked at
         ray_finish(r);
-        const Closest back = closest(nodes, n, nv, verts, tris, r, -1, two_sided ? 0 : 1);
+        const Closest back = closest(m, r, -1, two_sided ? 0 : 1);
         if (back.tri >= 0 && (best.tri < 0 || back.t < best.t)) {
             best = back;
             off = -back.t;
@@ -503,8 +503,8 @@ __global__ void __launch_bounds__(256) transfer_kernel(const Node* __restrict__ 
     if (offset) offset[p] = off;
     if (best.tri < 0) return;
     double a[3], b[3], c[3];
-    if (!load_live(nv, verts, tris, best.tri, a, b, c)) return;  // never: it was hit, so it is live and its indices are in range
-    const size_t i0 = (size_t)tris[3 * (size_t)best.tri], i1 = (size_t)tris[3 * (size_t)best.tri + 1], i2 = (size_t)tris[3 * (size_t)best.tri + 2];
+    if (!load_live(m, best.tri, a, b, c)) return;  // never: it was hit, so it is live and its indices are in range
+    const size_t i0 = (size_t)m.tris[3 * (size_t)best.tri], i1 = (size_t)m.tris[3 * (size_t)best.tri + 1], i2 = (size_t)m.tris[3 * (size_t)best.tri + 2];
     const double u = best.u, v = best.v, w = (1.0 - u) - v;
     float* row = values + (size_t)p * stride;
     for (int ch = 0; ch < channels; ch++)
@@ -534,6 +534,15 @@ int query_status(const void* bvh, long long bvh_bytes, long long nv, const doubl
     if (nt > 0 && (!bvh || !tris || (nv > 0 && !verts) || bvh_bytes < (long long)carve(nullptr, nt).bytes)) return GS2M_ERR_INVALID_ARG;
     return GS2M_OK;
 }
+// ... and, behind them, the checks of a query's `count` rays or points: `valid` says that its other arguments are, `buffers` that
+// every per-row buffer is there.  GS2M_OK with count == 0: nothing to launch.
+int rows_status(long long count, bool valid, bool buffers, long long limit) {
+    if (count < 0 || !valid || (count > 0 && !buffers)) return GS2M_ERR_INVALID_ARG;
+    return count > limit ? GS2M_ERR_UNSUPPORTED : GS2M_OK;
+}
+int rays_status(long long n_rays, const double* origins, const double* dirs, double tmin, double tmax, bool outputs) {
+    return rows_status(n_rays, tmin == tmin && tmax == tmax, origins && dirs && outputs, MAX_LAUNCH);
+}
 
 }  // namespace
 
@@ -555,13 +564,14 @@ int gs2m_bvh_build(long long n_verts, const double* verts, long long n_triangles
     hipStream_t s = (hipStream_t)stream;
     const BvhWs w = carve((char*)bvh, n);
     const SortBufs& b = w.sort;
-    centroid_kernel<<<blocks_of(n), 256, 0, s>>>(n_verts, n, verts, triangles, w.cen);
+    const Mesh m = {nullptr, n, n_verts, verts, triangles};  // no nodes to read yet: the kernels below write them through w.nodes
+    centroid_kernel<<<blocks_of(n), 256, 0, s>>>(m, w.cen);
     reduce_fixed_order<6, BoundsOp>(n, BoundsTerm{w.cen}, w.part, nullptr, w.bounds, nullptr, s);
     key_kernel<<<blocks_of(n), 256, 0, s>>>(n, w.cen, w.bounds, w.keys);
     if (hipGetLastError() != hipSuccess ||
         gs2m_radix_sort_pairs(w.temp, w.temp_bytes, w.keys, nullptr, b.kA, b.vA, b.kB, b.vB, (size_t)n, SORT_BITS, false, s) != hipSuccess)
         return GS2M_ERR_HIP;
-    leaf_kernel<<<blocks_of(n), 256, 0, s>>>(n_verts, n, verts, triangles, b.vB, w.nodes, w.arrived);
+    leaf_kernel<<<blocks_of(n), 256, 0, s>>>(m, b.vB, w.nodes, w.arrived);
     if (n > 1) {
         hierarchy_kernel<<<blocks_of(n - 1), 256, 0, s>>>(n, b.kB, w.nodes, w.rightof, w.last);
         refit_kernel<<<blocks_of(n), 256, 0, s>>>(n, w.nodes, w.arrived);
@@ -573,42 +583,36 @@ int gs2m_bvh_build(long long n_verts, const double* verts, long long n_triangles
 int gs2m_bvh_occluded(const void* bvh, long long bvh_bytes, long long n_verts, const double* verts, long long n_triangles,
                       const int* triangles, long long n_rays, const double* origins, const double* dirs, double tmin, double tmax,
                       const int* skip, unsigned char* hit, void* stream) {
-    const int st = query_status(bvh, bvh_bytes, n_verts, verts, n_triangles, triangles);
-    if (st != GS2M_OK) return st;
-    if (n_rays < 0 || tmin != tmin || tmax != tmax || (n_rays > 0 && (!origins || !dirs || !hit))) return GS2M_ERR_INVALID_ARG;
-    if (n_rays == 0) return GS2M_OK;
-    if (n_rays > MAX_LAUNCH) return GS2M_ERR_UNSUPPORTED;
-    occluded_kernel<<<blocks_of(n_rays), 256, 0, (hipStream_t)stream>>>((const Node*)bvh, n_triangles, n_verts, verts, triangles, n_rays, origins,
-                                                                        dirs, tmin, tmax, skip, hit);
+    int st = query_status(bvh, bvh_bytes, n_verts, verts, n_triangles, triangles);
+    if (st == GS2M_OK) st = rays_status(n_rays, origins, dirs, tmin, tmax, hit != nullptr);
+    if (st != GS2M_OK || n_rays == 0) return st;
+    const Mesh m = {(const Node*)bvh, n_triangles, n_verts, verts, triangles};
+    occluded_kernel<<<blocks_of(n_rays), 256, 0, (hipStream_t)stream>>>(m, n_rays, origins, dirs, tmin, tmax, skip, hit);
     return gs2m_status(hipGetLastError());
 }
 
 int gs2m_bvh_closest(const void* bvh, long long bvh_bytes, long long n_verts, const double* verts, long long n_triangles,
                      const int* triangles, long long n_rays, const double* origins, const double* dirs, double tmin, double tmax,
                      const int* skip, int facing, int* tri, double* t, double* uv, void* stream) {
-    const int st = query_status(bvh, bvh_bytes, n_verts, verts, n_triangles, triangles);
-    if (st != GS2M_OK) return st;
-    if (n_rays < 0 || tmin != tmin || tmax != tmax || facing < -1 || facing > 1 || (n_rays > 0 && (!origins || !dirs || !tri || !t || !uv)))
-        return GS2M_ERR_INVALID_ARG;
-    if (n_rays == 0) return GS2M_OK;
-    if (n_rays > MAX_LAUNCH) return GS2M_ERR_UNSUPPORTED;
-    closest_kernel<<<blocks_of(n_rays), 256, 0, (hipStream_t)stream>>>((const Node*)bvh, n_triangles, n_verts, verts, triangles, n_rays, origins,
-                                                                       dirs, tmin, tmax, skip, facing, tri, t, uv);
+    int st = query_status(bvh, bvh_bytes, n_verts, verts, n_triangles, triangles);
+    if (st == GS2M_OK && (facing < -1 || facing > 1)) st = GS2M_ERR_INVALID_ARG;
+    if (st == GS2M_OK) st = rays_status(n_rays, origins, dirs, tmin, tmax, tri && t && uv);
+    if (st != GS2M_OK || n_rays == 0) return st;
+    const Mesh m = {(const Node*)bvh, n_triangles, n_verts, verts, triangles};
+    closest_kernel<<<blocks_of(n_rays), 256, 0, (hipStream_t)stream>>>(m, n_rays, origins, dirs, tmin, tmax, skip, facing, tri, t, uv);
     return gs2m_status(hipGetLastError());
 }
 
 int gs2m_bvh_ao(const void* bvh, long long bvh_bytes, long long n_verts, const double* verts, long long n_triangles, const int* triangles,
                 long long n_points, const double* points, const double* normals, const int* skip, int R, int K, const double* dirs, double bias,
                 double radius, long long index0, long long seed, int* visible, void* stream) {
-    const int st = query_status(bvh, bvh_bytes, n_verts, verts, n_triangles, triangles);
-    if (st != GS2M_OK) return st;
-    if (n_points < 0 || R < 1 || K < 1 || !dirs || bias != bias || radius != radius || (n_points > 0 && (!points || !normals || !visible)))
-        return GS2M_ERR_INVALID_ARG;
-    if (n_points == 0) return GS2M_OK;
-    if (n_points > 0x7FFFFFFFll) return GS2M_ERR_UNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
-    ao_wave_kernel<<<(unsigned)((n_points + 3) / 4), 256, 0, s>>>((const Node*)bvh, n_triangles, n_verts, verts, triangles, n_points, points,
-                                                                  normals, skip, R, K, dirs, bias, radius, index0, seed, visible);
+    int st = query_status(bvh, bvh_bytes, n_verts, verts, n_triangles, triangles);
+    if (st == GS2M_OK)
+        st = rows_status(n_points, R >= 1 && K >= 1 && dirs && bias == bias && radius == radius, points && normals && visible, 0x7FFFFFFFll);
+    if (st != GS2M_OK || n_points == 0) return st;
+    const Mesh m = {(const Node*)bvh, n_triangles, n_verts, verts, triangles};
+    ao_wave_kernel<<<(unsigned)((n_points + 3) / 4), 256, 0, (hipStream_t)stream>>>(m, n_points, points, normals, skip, R, K, dirs, bias, radius,
+                                                                                    index0, seed, visible);
     return gs2m_status(hipGetLastError());
 }
 
@@ -624,16 +628,14 @@ int gs2m_mesh_transfer(const void* bvh, long long bvh_bytes, long long n_src_ver
                        const int* src_triangles, long long n_points, const double* points, const double* normals, const int* owner,
                        double distance, int two_sided, int channels, const float* src_attributes, const double* src_normals, int want_normal,
                        int stride, float* values, int* hit_tri, double* offset, void* stream) {
-    const int st = query_status(bvh, bvh_bytes, n_src_verts, src_verts, n_src_triangles, src_triangles);
-    if (st != GS2M_OK) return st;
+    int st = query_status(bvh, bvh_bytes, n_src_verts, src_verts, n_src_triangles, src_triangles);
     const long long columns = (long long)channels + (want_normal ? 3 : 0);
-    if (n_points < 0 || !(distance >= 0.0) || channels < 0 || (channels > 0 && !src_attributes) || stride < columns ||
-        (n_points > 0 && (!points || !normals || !hit_tri || (columns > 0 && !values))))
-        return GS2M_ERR_INVALID_ARG;
-    if (n_points == 0) return GS2M_OK;
-    if (n_points > MAX_LAUNCH) return GS2M_ERR_UNSUPPORTED;
-    transfer_kernel<<<blocks_of(n_points), 256, 0, (hipStream_t)stream>>>((const Node*)bvh, n_src_triangles, n_src_verts, src_verts, src_triangles,
-                                                                          n_points, points, normals, owner, distance, two_sided != 0, channels,
+    if (st == GS2M_OK)
+        st = rows_status(n_points, distance >= 0.0 && channels >= 0 && (channels == 0 || src_attributes) && stride >= columns,
+                         points && normals && hit_tri && (columns == 0 || values), MAX_LAUNCH);
+    if (st != GS2M_OK || n_points == 0) return st;
+    const Mesh m = {(const Node*)bvh, n_src_triangles, n_src_verts, src_verts, src_triangles};
+    transfer_kernel<<<blocks_of(n_points), 256, 0, (hipStream_t)stream>>>(m, n_points, points, normals, owner, distance, two_sided != 0, channels,
                                                                           src_attributes, src_normals, want_normal != 0, stride, values, hit_tri,
                                                                           offset);
     return gs2m_status(hipGetLastError());

@@ -3,7 +3,7 @@ include/gs2m_meshao.h).
 
 The mesh pipeline ends in the full TSDF mesh, which carries the vertex bake's albedo, roughness and metallic, and its simplified
 copy, which is what is exported.  `transfer_texels` casts, for every texel of the simplified mesh's atlas, a short ray along the
-texel's normal, forth and back, against a hierarchy of the SOURCE mesh (`gs2m_mesh_ao.build_bvh`, the closest-hit query), and
+texel's normal, forth and back, against a hierarchy of the SOURCE mesh (`gs2m_mesh_bvh.build_bvh`, the closest-hit query), and
 copies what the source has where the nearer ray meets it: its vertex values, and with `normal=True` its geometric normal, which
 `gs2m_mesh_texture.pack_normal_map` turns into the tangent-space normal map of the detail the simplification removed.  Texturing a
 simplified mesh this way needs the two PLY files and nothing else: no model, no dataset.  Every ray is traced by the library, on
@@ -29,8 +29,8 @@ import torch
 
 import gs2m_native as N
 from gs2m_eval_util import ptr as _ptr
-from gs2m_mesh_ao import BAND_TEXELS, Bvh, _unit, build_bvh, live_diagonal
 from gs2m_mesh_bake import FALLBACK
+from gs2m_mesh_bvh import BAND_TEXELS, OWNER_ROWS, Bvh, atlas_normals, bands, build_bvh, checked_rows, live_diagonal, texels, unit_rows
 from gs2m_mesh_cull import _mesh_on_device, _on_device
 
 DISTANCE_SHARE = 0.02   # of the diagonal of the target's live vertices' bounding box: how far a ray is followed, each way
@@ -44,13 +44,7 @@ def transfer(bvh, points, normals, values, owner=None, distance=0.0, two_sided=F
     interpolated, or for None the hit triangle's cross(e1, e2); every other element stays.  owner (n,) int32: negative = no point
     here.  -> (hit (n,) int32: the source triangle or -1; offset (n,) float64: the signed distance along the normal, 0 for a miss)"""
     who = "transfer"
-    p = _on_device(points, "points", who, torch.float64, (3,))
-    n = _on_device(normals, "normals", who, torch.float64, (3,))
-    if len(p) != len(n):
-        raise RuntimeError(f"{who}: {len(p)} points for {len(n)} normals")
-    ow = None if owner is None else _on_device(owner, "owner", who, torch.int32, ())
-    if ow is not None and len(ow) != len(p):
-        raise RuntimeError(f"{who}: {len(ow)} owners for {len(p)} points")
+    p, n, ow = checked_rows(who, OWNER_ROWS, points, normals, owner)
     att = None if source_values is None else N.f32(source_values, "source_values", who=who)
     if att is not None and (att.dim() != 2 or len(att) != len(bvh.vertices)):
         raise RuntimeError(f"{who}: `source_values` must have shape ({len(bvh.vertices)}, C), got {tuple(att.shape)}")
@@ -63,21 +57,17 @@ def transfer(bvh, points, normals, values, owner=None, distance=0.0, two_sided=F
         raise RuntimeError(f"{who}: `values` must be a contiguous ({len(p)}, stride) float32 tensor on {p.device}")
     hit = torch.full((len(p),), -1, dtype=torch.int32, device=p.device)
     offset = torch.zeros(len(p), dtype=torch.float64, device=p.device)
-    N.launch("gs2m_mesh_transfer", p.device, *bvh._args(), len(p), _ptr(p), _ptr(n), _ptr(ow), float(distance), int(bool(two_sided)), channels,
+    N.launch("gs2m_mesh_transfer", p.device, *bvh.args(), len(p), _ptr(p), _ptr(n), _ptr(ow), float(distance), int(bool(two_sided)), channels,
              _ptr(att), _ptr(sn), int(bool(normal)), int(values.shape[1]), _ptr(values), _ptr(hit), _ptr(offset))
     return hit, offset
 
 
 def texel_rays(atlas, vertex_normals=None, row0=0, n_rows=None):
     """Where the transfer's rays start and run, for rows row0 .. row0 + n_rows of the atlas: the texels as points of the low mesh
-    and its interpolated vertex normals (gs2m_mesh_texture.atlas_texels, what the texel bake sees), normalised as
-    gs2m_mesh_ao._unit does -> (owner (n, W) int32, points (n, W, 3), normals (n, W, 3) float64)"""
-    from gs2m_mesh_texture import atlas_texels
-    if vertex_normals is None and len(atlas.triangles):
-        from gs2m_mesh_view import vertex_normals as normals_of
-        vertex_normals = normals_of(atlas.vertices, atlas.triangles)[0]
-    owner, _, points, tn = atlas_texels(atlas, vertex_normals, row0, n_rows)
-    return owner, points, _unit(tn.reshape(-1, 3)).reshape(tn.shape).contiguous()
+    and its interpolated vertex normals (gs2m_mesh_bvh.texels), normalised as gs2m_mesh_bvh.unit_rows does
+    -> (owner (n, W) int32, points (n, W, 3), normals (n, W, 3) float64)"""
+    owner, points, tn = texels(atlas, vertex_normals, row0, n_rows)
+    return owner, points, unit_rows(tn.reshape(-1, 3)).reshape(tn.shape).contiguous()
 
 
 def _fill(atlas, channels, attributes):
@@ -125,13 +115,8 @@ def transfer_texels(atlas, source_mesh, source_values=None, distance=None, two_s
     values = torch.cat(planes, 2).contiguous()
     hit = torch.full((a.height, a.width), -1, dtype=torch.int32, device=dev)
     offset = torch.zeros((a.height, a.width), dtype=torch.float64, device=dev)
-    vn = None
-    if len(a.triangles):
-        from gs2m_mesh_view import vertex_normals
-        vn = vertex_normals(a.vertices, a.triangles)[0]
-    rows = max(1, int(band_texels) // max(a.width, 1))
-    for row0 in range(0, a.height, rows):
-        n = min(rows, a.height - row0)
+    vn = atlas_normals(a)
+    for row0, n in bands(a, band_texels):
         owner, points, normals = texel_rays(a, vn, row0, n)
         band = values[row0:row0 + n].reshape(n * a.width, -1)            # a view: whole rows of a contiguous tensor
         h, o = transfer(bvh, points.reshape(-1, 3), normals.reshape(-1, 3), band, owner.reshape(-1), distance, two_sided, att, sn, normal)

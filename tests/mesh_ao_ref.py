@@ -13,8 +13,9 @@ def cross(a, b):
                      a[..., 0] * b[..., 1] - a[..., 1] * b[..., 0]], -1)
 
 
-def triangle_hits(o, d, a, b, c, tmin, tmax):
-    """The Triangle paragraph, broadcasting: o, d (..., 3) rays against a, b, c (..., 3) corners -> bool"""
+def triangle_tuv(o, d, a, b, c):
+    """The Triangle paragraph up to t, broadcasting: o, d (..., 3) rays against a, b, c (..., 3) corners -> (ok: what det, u and v
+    say, before any range of t; t, u, v, det, computed whatever ok says)"""
     o, d, a, b, c = (np.asarray(x, np.float64) for x in (o, d, a, b, c))
     with np.errstate(all="ignore"):
         e1, e2 = b - a, c - a
@@ -28,16 +29,24 @@ def triangle_hits(o, d, a, b, c, tmin, tmax):
         v = dot(d, Q) / det
         ok &= (v >= 0) & (u + v <= 1)
         t = dot(e2, Q) / det
-        ok &= (t > tmin) & (t <= tmax)
-    return ok
+    return ok, t, u, v, det
+
+
+def in_range(t, tmin, tmax, closed):
+    """tmin < t <= tmax of the any-hit query; closed: tmin <= t <= tmax of the closest-hit query"""
+    with np.errstate(all="ignore"):
+        return ((t >= tmin) if closed else (t > tmin)) & (t <= tmax)
+
+
+def triangle_hits(o, d, a, b, c, tmin, tmax):
+    """The Triangle paragraph, broadcasting -> bool"""
+    ok, t = triangle_tuv(o, d, a, b, c)[:2]
+    return ok & in_range(t, tmin, tmax, False)
 
 
 def hit_parameter(o, d, a, b, c):
     """t of the Triangle paragraph (whatever u and v say), for building rays that end exactly on a triangle"""
-    with np.errstate(all="ignore"):
-        e1, e2 = b - a, c - a
-        det = dot(e1, cross(d, e2))
-        return dot(e2, cross(o - a, e1)) / det
+    return triangle_tuv(o, d, a, b, c)[1]
 
 
 def live_triangles(vertices, triangles):
@@ -50,29 +59,43 @@ def live_triangles(vertices, triangles):
     return ok & fin
 
 
-def hit_matrix(vertices, triangles, origins, dirs, tmin=0.0, tmax=np.inf):
-    """(n_rays, F) bool: ray i hits the live triangle j"""
+def triangle_table(vertices, triangles, origins, dirs):
+    """triangle_tuv of every ray against every triangle -> (ok (n_rays, F) bool, false for a dead triangle; t, u, v, det
+    (n_rays, F) float64, NaN for a dead triangle)"""
     v, f = np.asarray(vertices, np.float64).reshape(-1, 3), np.asarray(triangles).reshape(-1, 3).astype(np.int64)
     o, d = np.asarray(origins, np.float64).reshape(-1, 3), np.asarray(dirs, np.float64).reshape(-1, 3)
     live = live_triangles(v, f)
-    out = np.zeros((len(o), len(f)), bool)
+    ok = np.zeros((len(o), len(f)), bool)
+    t, u, w, det = (np.full((len(o), len(f)), np.nan) for _ in range(4))
     if not live.any() or len(o) == 0:
-        return out
+        return ok, t, u, w, det
     p = v[f[live]]
     for r0 in range(0, len(o), 128):
-        oo, dd = o[r0:r0 + 128, None], d[r0:r0 + 128, None]
-        out[r0:r0 + 128, live] = triangle_hits(oo, dd, p[None, :, 0], p[None, :, 1], p[None, :, 2], tmin, tmax)
-    return out
+        s = slice(r0, r0 + 128)
+        ok[s, live], t[s, live], u[s, live], w[s, live], det[s, live] = triangle_tuv(o[s, None], d[s, None], p[None, :, 0], p[None, :, 1],
+                                                                                     p[None, :, 2])
+    return ok, t, u, w, det
+
+
+def hit_matrix(vertices, triangles, origins, dirs, tmin=0.0, tmax=np.inf):
+    """(n_rays, F) bool: ray i hits the live triangle j"""
+    ok, t = triangle_table(vertices, triangles, origins, dirs)[:2]
+    return ok & in_range(t, tmin, tmax, False)
+
+
+def without_skipped(ok, skip):
+    """The skip rule on a table (n_rays, F) bool, in place: ray i does not see triangle skip[i]; an id that names no triangle
+    skips nothing"""
+    if skip is not None:
+        sk = np.asarray(skip).reshape(-1)
+        rows = np.nonzero((sk >= 0) & (sk < ok.shape[1]))[0]
+        ok[rows, sk[rows]] = False
+    return ok
 
 
 def occluded(vertices, triangles, origins, dirs, tmin=0.0, tmax=np.inf, skip=None):
     """The Occluded paragraph by the loop over all triangles -> (n_rays,) bool"""
-    m = hit_matrix(vertices, triangles, origins, dirs, tmin, tmax)
-    if skip is not None:
-        sk = np.asarray(skip).reshape(-1)
-        rows = np.nonzero((sk >= 0) & (sk < m.shape[1]))[0]
-        m[rows, sk[rows]] = False
-    return m.any(1)
+    return without_skipped(hit_matrix(vertices, triangles, origins, dirs, tmin, tmax), skip).any(1)
 
 
 def mix32(x):

@@ -12,33 +12,8 @@ def triangle_table(vertices, triangles, origins, dirs, tmin=0.0, tmax=np.inf):
     """Every ray against every triangle, the Candidate paragraph with facing = 0 and no skip -> (ok (n_rays, F) bool; t, u, v,
     det (n_rays, F) float64, defined where ok).  `select` narrows ok by facing and skip, `answer` picks the winner: a test that
     needs several facings of one set of rays pays for the products once."""
-    v, f = np.asarray(vertices, np.float64).reshape(-1, 3), np.asarray(triangles).reshape(-1, 3).astype(np.int64)
-    o, d = np.asarray(origins, np.float64).reshape(-1, 3), np.asarray(dirs, np.float64).reshape(-1, 3)
-    live = A.live_triangles(v, f)
-    ok = np.zeros((len(o), len(f)), bool)
-    t, u, w, dt = (np.full((len(o), len(f)), np.nan) for _ in range(4))
-    if not live.any() or len(o) == 0:
-        return ok, t, u, w, dt
-    p = v[f[live]]
-    a, b, c = p[None, :, 0], p[None, :, 1], p[None, :, 2]
-    for r0 in range(0, len(o), 128):
-        oo, dd = o[r0:r0 + 128, None], d[r0:r0 + 128, None]
-        with np.errstate(all="ignore"):
-            e1, e2 = b - a, c - a
-            P = A.cross(dd, e2)
-            det = A.dot(e1, P)
-            good = (det != 0) & np.isfinite(det)
-            T = oo - a
-            uu = A.dot(T, P) / det
-            good &= (uu >= 0) & (uu <= 1)
-            Q = A.cross(T, e1)
-            vv = A.dot(dd, Q) / det
-            good &= (vv >= 0) & (uu + vv <= 1)
-            tt = A.dot(e2, Q) / det
-            good &= (tt >= tmin) & (tt <= tmax)
-        s = slice(r0, r0 + 128)
-        ok[s, live], t[s, live], u[s, live], w[s, live], dt[s, live] = good, tt, uu, vv, det
-    return ok, t, u, w, dt
+    ok, t, u, v, det = A.triangle_table(vertices, triangles, origins, dirs)
+    return ok & A.in_range(t, tmin, tmax, True), t, u, v, det
 
 
 def select(ok, det, skip=None, facing=0):
@@ -51,11 +26,7 @@ def select(ok, det, skip=None, facing=0):
             ok &= det > 0
         elif facing < 0:
             ok &= det < 0
-    if skip is not None:
-        sk = np.asarray(skip).reshape(-1)
-        rows = np.nonzero((sk >= 0) & (sk < ok.shape[1]))[0]
-        ok[rows, sk[rows]] = False
-    return ok
+    return A.without_skipped(ok, skip)
 
 
 def answer(ok, t, u, v):

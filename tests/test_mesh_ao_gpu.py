@@ -1,4 +1,4 @@
-"""The LBVH, the any-hit traversal and the ambient occlusion on the GPU (csrc/mesh_bvh.hip, gs2m_mesh_ao.py) against the numpy
+"""The LBVH, the any-hit traversal and the ambient occlusion on the GPU (csrc/mesh_bvh.hip, gs2m_mesh_bvh.py, gs2m_mesh_ao.py) against the numpy
 restatement of tests/mesh_ao_ref.py.  Everything is held to equality: the traversal's answer is defined as the brute-force
 loop's, the AO count as the restatement's, and the tree's invariants are read back from the buffer.  All data is synthetic."""
 import functools
@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import gs2m_mesh_ao as AO
+import gs2m_mesh_bvh as BV
 import gs2m_native as N
 import mesh_ao_ref as A
 
@@ -25,11 +26,11 @@ def _cuda(a, dtype=None):
 @functools.lru_cache(maxsize=None)
 def _scene(name):
     v, f = A.MESHES[name]()
-    return v, f, AO.build_bvh(_cuda(v, torch.float64), _cuda(f, torch.int32))
+    return v, f, BV.build_bvh(_cuda(v, torch.float64), _cuda(f, torch.int32))
 
 
 def _device_occluded(bvh, r):
-    return AO.occluded(bvh, _cuda(r["origins"]), _cuda(r["dirs"]), r["tmin"], r["tmax"],
+    return BV.occluded(bvh, _cuda(r["origins"]), _cuda(r["dirs"]), r["tmin"], r["tmax"],
                        None if r["skip"] is None else _cuda(r["skip"], torch.int32)).cpu().numpy()
 
 
@@ -38,7 +39,7 @@ def test_bvh_invariants_and_two_builds(name):
     v, f, bvh = _scene(name)
     lo, hi, links = bvh.nodes()
     A.check_bvh(lo, hi, links, v, f)
-    again = AO.build_bvh(_cuda(v, torch.float64), _cuda(f, torch.int32))
+    again = BV.build_bvh(_cuda(v, torch.float64), _cuda(f, torch.int32))
     m = 64 * max(2 * len(f) - 1, 0)
     assert torch.equal(bvh.buffer[:m], again.buffer[:m])
     if name in ("identical257", "collinear200", "n1000"):   # ties are split by position: no chain
@@ -81,30 +82,30 @@ def test_occluded_ray_counts(name, n_rays):
 def test_empty_and_dead_meshes_occlude_nothing():
     o, d = _cuda(np.random.default_rng(0).random((65, 3))), _cuda(np.random.default_rng(1).standard_normal((65, 3)))
     v, f, bvh = _scene("n0")
-    assert not AO.occluded(bvh, o, d).any()
+    assert not BV.occluded(bvh, o, d).any()
     vd = np.array([[0, 0, 0], [1, 0, 0], [np.nan, 1, 0]])
     fd = np.array([[0, 1, 2], [0, 1, 5], [-1, 0, 1]], np.int32)
-    dead = AO.build_bvh(_cuda(vd), _cuda(fd))
+    dead = BV.build_bvh(_cuda(vd), _cuda(fd))
     A.check_bvh(*dead.nodes(), vd, fd)
-    assert not AO.occluded(dead, o, d).any()
+    assert not BV.occluded(dead, o, d).any()
     vis, ao = AO.ambient_occlusion(dead, o, d, rays=64, tables=2, radius=1.0, bias=0.0)
     assert (vis == 64).all() and (ao == 1).all()
     # a ray with a NaN misses everything, whatever the tree
     v, f, bvh = _scene("n64")
     bad = d.clone()
     bad[::2, 1] = float("nan")
-    assert not AO.occluded(bvh, o, bad)[::2].any()
+    assert not BV.occluded(bvh, o, bad)[::2].any()
 
 
 def _ao_case(v, f, pts, nrm, skip, K, R, radius, bias, seed=0, index0=0):
-    bvh = AO.build_bvh(_cuda(v, torch.float64), _cuda(f, torch.int32))
+    bvh = BV.build_bvh(_cuda(v, torch.float64), _cuda(f, torch.int32))
     if radius is None:
-        diag = AO.live_diagonal(bvh.vertices, bvh.triangles)
+        diag = BV.live_diagonal(bvh.vertices, bvh.triangles)
         assert diag == float(np.linalg.norm(v.max(0) - v.min(0)))
         radius_ref, bias_ref = 0.25 * diag, 1e-4 * diag
     else:
         radius_ref, bias_ref = radius, bias
-    unit = AO._unit(_cuda(nrm, torch.float64)).cpu().numpy()   # the caller's part of the contract, as the wrapper does it
+    unit = BV.unit_rows(_cuda(nrm, torch.float64)).cpu().numpy()   # the caller's part of the contract, as the wrapper does it
     got, ao = AO.ambient_occlusion(bvh, _cuda(pts), _cuda(nrm), None if skip is None else _cuda(skip, torch.int32), rays=K, tables=R,
                                    radius=radius, bias=bias, seed=seed, index0=index0)
     want = A.ambient_occlusion(v, f, pts, unit, skip, AO.direction_table(K, R, seed), bias_ref, radius_ref, index0, seed)
@@ -156,7 +157,7 @@ def test_ao_fixed_cases_splits_and_repeats():
     closed = _ao_case(v, f, inside[12:], nrm[12:], None, table_K, 16, np.inf, 1e-4)
     assert (closed == 0).all()                                                                # inside a closed box
     # two calls split at an odd point, with index0, are one call; two runs are the same bits
-    bvh = AO.build_bvh(_cuda(v, torch.float64), _cuda(f, torch.int32))
+    bvh = BV.build_bvh(_cuda(v, torch.float64), _cuda(f, torch.int32))
     p, n, s = _cuda(inside), _cuda(nrm), _cuda(skip)
     kw = dict(rays=100, tables=16, radius=0.7, bias=1e-4, seed=9)
     whole = AO.ambient_occlusion(bvh, p, n, s, index0=1000, **kw)[0]
@@ -184,7 +185,7 @@ def test_texel_and_vertex_occlusion_under_an_overhang():
     assert torch.equal(visible, whole)                                         # the bands do not show
     own, pts, nrm = AO.texel_points(atlas)
     assert torch.equal(own, owner)
-    unit = AO._unit(nrm.reshape(-1, 3)).cpu().numpy()
+    unit = BV.unit_rows(nrm.reshape(-1, 3)).cpu().numpy()
     want = A.ambient_occlusion(v, f, pts.reshape(-1, 3).cpu().numpy(), unit, owner.reshape(-1).cpu().numpy(), AO.direction_table(K, 16, 2),
                                1e-6, np.inf, 0, 2)
     assert np.array_equal(visible.reshape(-1).cpu().numpy(), want)
@@ -423,5 +424,5 @@ def test_error_paths():
     assert N.lib().gs2m_bvh_bytes(-1, C.byref(C.c_longlong())) == -1 and N.lib().gs2m_bvh_bytes(4, None) == -1
     torch.cuda.synchronize()
     assert (vis == -7).all() and (hit == 9).all() and (orm == 3).all()   # nothing was launched
-    again = AO.build_bvh(bvh.vertices, bvh.triangles)
+    again = BV.build_bvh(bvh.vertices, bvh.triangles)
     assert torch.equal(again.buffer[:64 * 127], bvh.buffer[:64 * 127])

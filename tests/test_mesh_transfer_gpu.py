@@ -1,4 +1,4 @@
-"""The closest-hit query and the detail transfer on the GPU (csrc/mesh_bvh.hip, gs2m_mesh_ao.closest, gs2m_mesh_transfer.py) against
+"""The closest-hit query and the detail transfer on the GPU (csrc/mesh_bvh.hip, gs2m_mesh_bvh.closest, gs2m_mesh_transfer.py) against
 the numpy restatement of tests/mesh_transfer_ref.py.  Everything is held to equality with no exception budget: the traversal's
 answer is defined as the brute-force loop's in all four outputs, the transfer's as the restatement's.  All data is synthetic."""
 import functools
@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-import gs2m_mesh_ao as AO
+import gs2m_mesh_bvh as BV
 import gs2m_mesh_transfer as T
 import gs2m_native as N
 import mesh_ao_ref as A
@@ -21,11 +21,11 @@ pytestmark = pytest.mark.gpu
 @functools.lru_cache(maxsize=None)
 def _scene(name):
     v, f = R.layered_grid() if name == "layered" else A.MESHES[name]()
-    return v, f, AO.build_bvh(_cuda(v, torch.float64), _cuda(f, torch.int32))
+    return v, f, BV.build_bvh(_cuda(v, torch.float64), _cuda(f, torch.int32))
 
 
 def _device_closest(bvh, r, skip=None, facing=0):
-    got = AO.closest(bvh, _cuda(r["origins"]), _cuda(r["dirs"]), r["tmin"], r["tmax"], None if skip is None else _cuda(skip, torch.int32), facing)
+    got = BV.closest(bvh, _cuda(r["origins"]), _cuda(r["dirs"]), r["tmin"], r["tmax"], None if skip is None else _cuda(skip, torch.int32), facing)
     return tuple(x.cpu().numpy() for x in got)
 
 
@@ -102,13 +102,13 @@ def test_nan_rays_and_dead_meshes_find_nothing():
     o, d = rng.random((65, 3)), rng.standard_normal((65, 3))
     vd = np.array([[0, 0, 0], [1, 0, 0], [np.nan, 1, 0]])
     fd = np.array([[0, 1, 2], [0, 1, 5], [-1, 0, 1]], np.int32)
-    dead = AO.build_bvh(_cuda(vd), _cuda(fd))
-    tri, t, uv = AO.closest(dead, _cuda(o), _cuda(d))
+    dead = BV.build_bvh(_cuda(vd), _cuda(fd))
+    tri, t, uv = BV.closest(dead, _cuda(o), _cuda(d))
     assert (tri == -1).all() and torch.isposinf(t).all() and (uv == 0).all()
     v, f, bvh = _scene("n64")
     bad = d.copy()
     bad[::2, 1] = np.nan
-    tri, t, uv = AO.closest(bvh, _cuda(o), _cuda(bad))
+    tri, t, uv = BV.closest(bvh, _cuda(o), _cuda(bad))
     assert (tri[::2] == -1).all() and torch.isposinf(t[::2]).all() and (uv[::2] == 0).all()
     _same((tri.cpu().numpy(), t.cpu().numpy(), uv.cpu().numpy()), R.closest(v, f, o, bad), "nan")
 
@@ -161,7 +161,7 @@ def test_transfer_texels_equal_the_restatement():
     assert (fill[~owned, :5] == np.array(T.FALLBACK, np.float32)).all() and (fill[owned & kept, :5] != np.array(T.FALLBACK, np.float32)).any()
     assert (np.sign(want[2][want[3] == 2]) >= 0).all() and (want[2][want[3] == 3] <= 0).all() and np.abs(want[2]).max() <= D
     # bands of three rows, one call and a second run: the same bits
-    for kw in (dict(band_texels=3 * a.width), dict(), dict(bvh=AO.build_bvh(_cuda(s["v"]), _cuda(s["f"], torch.int32)))):
+    for kw in (dict(band_texels=3 * a.width), dict(), dict(bvh=BV.build_bvh(_cuda(s["v"]), _cuda(s["f"], torch.int32)))):
         again = T.transfer_texels(a, _mesh(s["v"], s["f"]), s["att"], distance=D, normal=True, attributes=s["low"], **kw)
         assert all(torch.equal(x, y) for x, y in zip(again, (values, hit, offset)))
     # face normals, no attributes: three planes, cross(e1, e2) of the hit triangle
@@ -171,7 +171,7 @@ def test_transfer_texels_equal_the_restatement():
     assert (want_flat[0][want[1] >= 0][:, 2] > 0).all()
     # attributes alone, and the default distance: 0.02 of the low mesh's diagonal
     lv = R.tilted_plane()[0]
-    default = 0.02 * AO.live_diagonal(a.vertices, a.triangles)
+    default = 0.02 * BV.live_diagonal(a.vertices, a.triangles)
     assert abs(default - 0.02 * float(np.linalg.norm(lv.max(0) - lv.min(0)))) <= 1e-15
     only = T.transfer_texels(a, _mesh(s["v"], s["f"]), s["att"], attributes=s["low"])
     want_only = R.transfer(s["v"], s["f"], s["points"], s["normals"], s["owner"], default, False, fill[:, :5], s["att"])
@@ -208,7 +208,7 @@ def test_transfer_points_stride_owner_and_splits():
     nrm[7], nrm[8, 0], pts[9, 2], pts[10, 1] = 0.0, np.nan, np.nan, np.inf
     owner = np.zeros(601, np.int32)
     owner[11::50] = -1
-    bvh = AO.build_bvh(_cuda(s["v"]), _cuda(s["f"], torch.int32))
+    bvh = BV.build_bvh(_cuda(s["v"]), _cuda(s["f"], torch.int32))
     fill = np.random.default_rng(1).random((601, 11)).astype(np.float32)
     kw = dict(distance=R.TRANSFER_DISTANCE, source_values=_cuda(s["att"]), source_normals=_cuda(s["sn"]), normal=True)
     for own in (owner, None):
@@ -223,7 +223,7 @@ def test_transfer_points_stride_owner_and_splits():
         h2, o2 = T.transfer(bvh, _cuda(pts[333:]), _cuda(nrm[333:]), parts[333:], None if own is None else _cuda(own[333:]), **kw)
         assert torch.equal(parts, values) and torch.equal(torch.cat([h1, h2]), hit) and torch.equal(torch.cat([o1, o2]), offset)
     # a source without a triangle: every point misses
-    empty = AO.build_bvh(_cuda(s["v"]), _cuda(s["f"][:0], torch.int32))
+    empty = BV.build_bvh(_cuda(s["v"]), _cuda(s["f"][:0], torch.int32))
     values = _cuda(fill)
     hit, offset = T.transfer(empty, _cuda(pts), _cuda(nrm), values, None, distance=1.0, normal=True)
     assert (hit == -1).all() and (offset == 0).all() and np.array_equal(values.cpu().numpy(), fill)
@@ -371,12 +371,12 @@ def test_error_paths():
     torch.cuda.synchronize()
     for x in (tri, t, uv, values, hit, off):
         assert (x == -7).all()                                                     # nothing was launched
-    again = AO.build_bvh(bvh.vertices, bvh.triangles)
+    again = BV.build_bvh(bvh.vertices, bvh.triangles)
     assert torch.equal(again.buffer[:64 * 127], bvh.buffer[:64 * 127])
     # the wrappers' own checks
     with pytest.raises(RuntimeError, match="no CPU path"):
-        AO.closest(bvh, torch.zeros(4, 3, dtype=torch.float64), d)
+        BV.closest(bvh, torch.zeros(4, 3, dtype=torch.float64), d)
     with pytest.raises(RuntimeError, match="3 origins for 4"):
-        AO.closest(bvh, o[:3], d)
+        BV.closest(bvh, o[:3], d)
     with pytest.raises(RuntimeError, match="float32"):
         T.transfer(bvh, o, d, values.double(), distance=1.0, normal=True)

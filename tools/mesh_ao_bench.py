@@ -21,6 +21,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import torch  # noqa: E402
 
 import gs2m_mesh_ao as AO  # noqa: E402
+import gs2m_mesh_bvh as BV  # noqa: E402
 import gs2m_mesh_texture as MT  # noqa: E402
 from mesh_bake_bench import H, W, timed  # noqa: E402
 
@@ -75,8 +76,8 @@ def main():
     ms = lambda t: {"median_ms": round(t[0], 3), "min_ms": round(t[1], 3), "max_ms": round(t[2], 3)}
     result = {"workload": f"voxel {a.voxel} simplified at 8 voxels, atlas {atlas.width} x {atlas.height}, K = {K}, 16 tables, default radius and bias, "
                           "synthetic surface scene", "n_vertices": len(mesh.vertices), "n_triangles": len(mesh.triangles), "repeats": a.repeats}
-    bvh = AO.build_bvh(mesh.vertices, mesh.triangles)
-    result["build"] = ms(timed(lambda: AO.build_bvh(mesh.vertices, mesh.triangles), a.repeats))
+    bvh = BV.build_bvh(mesh.vertices, mesh.triangles)
+    result["build"] = ms(timed(lambda: BV.build_bvh(mesh.vertices, mesh.triangles), a.repeats))
     result["bvh_bytes"] = bvh.buffer.numel()
     # the traversal alone: the texels' points are made once, outside the clock
     owner, points, normals = AO.texel_points(atlas)
@@ -95,7 +96,7 @@ def main():
     # the yardstick: a subset of owned texels, every ray against every triangle in torch operators
     pick = torch.nonzero(owner >= 0).reshape(-1)
     pick = pick[torch.linspace(0, len(pick) - 1, min(SUBSET, len(pick)), device=dev).long()]
-    unit = AO._unit(normals[pick])
+    unit = BV.unit_rows(normals[pick])
     table = sampler.dirs
     x = (pick + sampler.seed) & 0xFFFFFFFF                 # mix32 of the header, index0 = 0
     x = x ^ (x >> 16)

@@ -21,7 +21,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import torch  # noqa: E402
 
-import gs2m_mesh_ao as AO  # noqa: E402
+import gs2m_mesh_bvh as BV  # noqa: E402
 import gs2m_mesh_texture as MT  # noqa: E402
 import gs2m_mesh_transfer as T  # noqa: E402
 from mesh_bake_bench import H, W, timed  # noqa: E402
@@ -74,13 +74,13 @@ def main():
     source = types.SimpleNamespace(vertices=full.vertices.to(torch.float64).contiguous(), triangles=full.triangles.to(torch.int32).contiguous())
     low = types.SimpleNamespace(vertices=simple.vertices.to(torch.float64).contiguous(), triangles=simple.triangles.to(torch.int32).contiguous())
     atlas = MT.build_atlas(low, texture_size=a.size)
-    distance = T.DISTANCE_SHARE * AO.live_diagonal(atlas.vertices, atlas.triangles)
+    distance = T.DISTANCE_SHARE * BV.live_diagonal(atlas.vertices, atlas.triangles)
     ms = lambda t: {"median_ms": round(t[0], 3), "min_ms": round(t[1], 3), "max_ms": round(t[2], 3)}
     result = {"workload": f"source: voxel {a.voxel}; target: its simplification at 8 voxels, atlas {atlas.width} x {atlas.height}; default distance, "
                           "one-sided, synthetic surface scene", "source_vertices": len(source.vertices), "source_triangles": len(source.triangles),
               "target_vertices": len(low.vertices), "target_triangles": len(low.triangles), "distance": distance, "repeats": a.repeats}
-    bvh = AO.build_bvh(source.vertices, source.triangles)
-    result["build"] = ms(timed(lambda: AO.build_bvh(source.vertices, source.triangles), a.repeats))
+    bvh = BV.build_bvh(source.vertices, source.triangles)
+    result["build"] = ms(timed(lambda: BV.build_bvh(source.vertices, source.triangles), a.repeats))
     result["bvh_bytes"] = bvh.buffer.numel()
     # the two queries on the same rays: the owned texels' forward rays, made once, outside the clock
     owner, points, normals = T.texel_rays(atlas)
@@ -88,10 +88,10 @@ def main():
     origins, dirs = points.reshape(-1, 3)[keep].contiguous(), normals.reshape(-1, 3)[keep].contiguous()
     n = len(origins)
     result.update(n_texels=owner.numel(), n_owned=n)
-    blocked = AO.occluded(bvh, origins, dirs, 0.0, distance)
-    tri, t_hit, _ = AO.closest(bvh, origins, dirs, 0.0, distance)
-    t0 = timed(lambda: AO.occluded(bvh, origins, dirs, 0.0, distance), a.repeats)
-    t1 = timed(lambda: AO.closest(bvh, origins, dirs, 0.0, distance), a.repeats)
+    blocked = BV.occluded(bvh, origins, dirs, 0.0, distance)
+    tri, t_hit, _ = BV.closest(bvh, origins, dirs, 0.0, distance)
+    t0 = timed(lambda: BV.occluded(bvh, origins, dirs, 0.0, distance), a.repeats)
+    t1 = timed(lambda: BV.closest(bvh, origins, dirs, 0.0, distance), a.repeats)
     result["occluded"] = dict(ms(t0), rays_per_s=round(n / (t0[0] * 1e-3)), hit_share=round(float(blocked.double().mean()), 4))
     result["closest"] = dict(ms(t1), rays_per_s=round(n / (t1[0] * 1e-3)), hit_share=round(float((tri >= 0).double().mean()), 4))
     result["closest_over_occluded"] = round(t1[0] / t0[0], 3)
